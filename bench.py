@@ -20,8 +20,14 @@ same C loop on one host core.
 Multi-GPU: the windowed binpack path does not shard; each rank
 runs its own evaluations on its own GPU (replicas, weak scaling).
 
-Beside the headline line's C2 numbers, the JSON carries one object per other
-BASELINE.json config (sections, --sections to choose):
+A plain run sets up, warms up, times the --steps evaluations and prints the
+headline line; --dump-outputs DIR also writes what the last timed evaluation
+returned (its placements' node rows) and the loop's totals as .npy files. The
+CPU baselines, the AllocMetric-on leg, the kernel split, the rooflines and the
+sections below run with --full only.
+
+With --full, beside the headline line's C2 numbers, the JSON carries one object
+per other BASELINE.json config (sections, --sections to choose):
   c2_100k     the drop-in protocol on a 100k-node cluster (the metric's second size)
   c2_batch    4096 concurrent evaluations per launch sharing one k_base pass
   c2_workers  NumSchedulers-style worker threads, one engine handle each, each
@@ -82,8 +88,25 @@ def parse():
                    help="nodes of the scoring-sweep roofline measurement (0 = skip)")
     p.add_argument("--sections", default="c1,c2_100k,c2_batch,c2_workers,c3,c4,c4_drop_in,c5,c3_sharded,c3_sharded_1m,"
                                          "plan_apply,ingest,multi_loopback",
-                   help="comma list of extra config sections (empty = none)")
+                   help="comma list of extra config sections of a --full run (empty = none)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the AllocMetric-on leg, the kernel split and rooflines, the CPU "
+                        "baselines and the --sections (a plain run times the headline steps only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one returned to the caller as DIR/<name>.npy")
     return p.parse_args()
+
+
+def dump_outputs(path, rank, world, rows, placed, evals, selects):
+    """What the timed caller loop handed back, as float64 .npy files: the node
+    row of every placement of the last timed evaluation (-1: no node) and the
+    loop's totals over the timed steps (placements, evaluations, Selects).
+    The cluster, the job and the visit orders are seeded, so two builds given
+    the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(path, "rows%s.npy" % tag), np.asarray(rows, dtype=np.float64))
+    np.save(os.path.join(path, "totals%s.npy" % tag), np.array([placed, evals, selects], dtype=np.float64))
 
 
 def dist_init():
@@ -1243,6 +1266,50 @@ def main():
     elapsed = reduce(pg, elapsed, lambda d: d.ReduceOp.MAX)
     total_placed = reduce(pg, placed, lambda d: d.ReduceOp.SUM)
     total_evals = reduce(pg, evals, lambda d: d.ReduceOp.SUM)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, rows, placed, evals, selects)
+
+    line = None
+    if rank == 0:
+        value = total_placed / elapsed
+        line = {
+            "metric": "placements/sec (count=1000 service job, 10k nodes, binpack)",
+            "value": value,
+            "unit": "placements/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1000.0,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "int64+f64",
+            "data": "synthetic (seeded 10k-node cluster, SURVEY.md §8d C2)",
+            "config": {"workload": "C2 drop-in: per step one evaluation of a count=%d binpack service job on %d "
+                                   "heterogeneous nodes (limit 14): ResetPlan + SetJob + SetNodes + %d x "
+                                   "(Select, Commit) from a C caller loop, %s"
+                                   % (args.count, args.nodes, args.count,
+                                      "every call through the C ABI" if args.no_view else
+                                      "predicted pairs from the served-Select view (pe_spec_view)"),
+                       "evals_per_step": 1,
+                       "parallelism": "replicas x%d (windowed binpack does not shard)" % world},
+            "drop_in": {"placements": placed, "evaluations": evals, "selects": selects,
+                        "selects_from_view": view_served,
+                        "c_loop_seconds": c_secs,
+                        "speculation": dict(zip(("runs", "served", "rollbacks", "records"),
+                                                (b - a for a, b in zip(spec0, spec1)))),
+                        "us_per_placement": elapsed / max(1, placed) * 1e6,
+                        "us_per_eval_by_phase": {k: v / max(1, evals) * 1e6 for k, v in phases.items()}},
+        }
+    if not args.full:
+        # a plain run: the headline steps alone
+        st.close()
+        if rank == 0:
+            json_out.write(json.dumps(line) + "\n")
+            json_out.flush()
+        if pg is not None:
+            pg.destroy_process_group()
+        return
 
     # The same caller loop with AllocMetric on: every placement's
     # Allocation.Metrics (generic_sched.go:558, 587), the maps copied out from
@@ -1288,38 +1355,10 @@ def main():
     st.close()
 
     if rank == 0:
-        value = total_placed / elapsed
         achieved = node_evals * BYTES_PER_NODE_EVAL / (loop_kernel_ms / 1000.0) / 1e9
-        line = {
-            "metric": "placements/sec (count=1000 service job, 10k nodes, binpack)",
-            "value": value,
-            "unit": "placements/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1000.0,
+        line.update({
             "nodes_scored_per_s": node_evals * total_evals / elapsed,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int64+f64",
-            "data": "synthetic (seeded 10k-node cluster, SURVEY.md §8d C2)",
-            "config": {"workload": "C2 drop-in: per step one evaluation of a count=%d binpack service job on %d "
-                                   "heterogeneous nodes (limit 14): ResetPlan + SetJob + SetNodes + %d x "
-                                   "(Select, Commit) from a C caller loop, %s"
-                                   % (args.count, args.nodes, args.count,
-                                      "every call through the C ABI" if args.no_view else
-                                      "predicted pairs from the served-Select view (pe_spec_view)"),
-                       "evals_per_step": 1,
-                       "parallelism": "replicas x%d (windowed binpack does not shard)" % world},
             "metrics_on": metrics_on,
-            "drop_in": {"placements": placed, "evaluations": evals, "selects": selects,
-                        "selects_from_view": view_served,
-                        "c_loop_seconds": c_secs,
-                        "speculation": dict(zip(("runs", "served", "rollbacks", "records"),
-                                                (b - a for a, b in zip(spec0, spec1)))),
-                        "us_per_placement": elapsed / max(1, placed) * 1e6,
-                        "us_per_eval_by_phase": {k: v / max(1, evals) * 1e6 for k, v in phases.items()}},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": headline_traffic(node_evals)[0],
                          "traffic_source": headline_traffic(node_evals)[1],
@@ -1332,7 +1371,7 @@ def main():
                                              "(pe_last_kernel_split), median of 5 evaluations",
                          "evaluation_kernels_ms": dict(split_ms, all_launches=loop_all_ms),
                          "node_evals_per_launch": node_evals, "bytes_per_node_eval": BYTES_PER_NODE_EVAL},
-        }
+        })
         if args.sweep_nodes > 0:
             line["sweep_roofline"] = sweep_roofline(args.sweep_nodes, local)
         if not args.no_cpu:

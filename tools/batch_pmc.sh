@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/batch_pmc
 mkdir -p "$OUT"
 cd "$ROOT"
-ARGS="--no-cpu --steps 1 --warmup 0 --sweep-nodes 0 --sections c2_batch"
+ARGS="--full --no-cpu --steps 1 --warmup 0 --sweep-nodes 0 --sections c2_batch"
 timeout -k 10 300 python -u bench.py $ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"
 cd /tmp
 export TMPDIR=/tmp

@@ -14,9 +14,9 @@ mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o fetch -- \
-  python3 "$ROOT/bench.py" --no-cpu --steps 3 --warmup 0 --sweep-nodes 0 --sections "" > "$OUT/f.json" 2> "$OUT/f.err"
+  python3 "$ROOT/bench.py" --full --no-cpu --steps 3 --warmup 0 --sweep-nodes 0 --sections "" > "$OUT/f.json" 2> "$OUT/f.err"
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o write -- \
-  python3 "$ROOT/bench.py" --no-cpu --steps 3 --warmup 0 --sweep-nodes 0 --sections "" > "$OUT/w.json" 2> "$OUT/w.err"
+  python3 "$ROOT/bench.py" --full --no-cpu --steps 3 --warmup 0 --sweep-nodes 0 --sections "" > "$OUT/w.json" 2> "$OUT/w.err"
 cd "$ROOT"
 F=$(find "$OUT/fetch" -name "*counter_collection.csv" -print -quit)
 W=$(find "$OUT/write" -name "*counter_collection.csv" -print -quit)

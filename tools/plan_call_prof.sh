@@ -13,7 +13,7 @@ cd "$ROOT"
 echo "nproc $(nproc) cpu.max $(cat /sys/fs/cgroup/cpu.max 2>/dev/null || echo n/a) affinity $(python3 -c 'import os;print(len(os.sched_getaffinity(0)))')"
 for V in ${PLAN_AB:-default}; do
   if [ "$V" = default ]; then E=""; else E="${V//,/ }"; fi
-  env $E PE_PLAN_PROF=1 timeout -k 10 300 python -u bench.py --no-cpu --steps 2 --warmup 1 --sweep-nodes 0 --sections plan_apply \
+  env $E PE_PLAN_PROF=1 timeout -k 10 300 python -u bench.py --full --no-cpu --steps 2 --warmup 1 --sweep-nodes 0 --sections plan_apply \
     > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
   echo "== $V"
   grep "planner evaluate" "$OUT/bench.err" | tail -2

@@ -11,7 +11,7 @@ for G in 4 8 16 64; do
   PE_PLAN_GROUP=$G timeout -k 10 200 python -u -m pytest tests/test_plan_apply.py -x -q -m gpu --timeout 120 \
     --timeout-method thread > "$OUT/pytest_$G.log" 2>&1
   tail -1 "$OUT/pytest_$G.log"
-  PE_PLAN_GROUP=$G timeout -k 10 200 python -u bench.py --no-cpu --steps 1 --warmup 0 --evals 1 --sweep-nodes 0 \
+  PE_PLAN_GROUP=$G timeout -k 10 200 python -u bench.py --full --no-cpu --steps 1 --warmup 0 --evals 1 --sweep-nodes 0 \
     --sections plan_apply > "$OUT/bench_$G.json" 2> "$OUT/bench_$G.err"
   python3 -c "import json;d=json.load(open('$OUT/bench_$G.json'))['configs']['plan_apply'];print($G, 'kernel_ms', d['kernel_ms'], 'nodes/s %.3g' % d['plan_nodes_per_s'])"
 done

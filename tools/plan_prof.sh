@@ -8,12 +8,12 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-timeout -k 10 300 python -u bench.py --steps 2 --warmup 1 --evals 1 --sweep-nodes 0 --sections plan_apply \
+timeout -k 10 300 python -u bench.py --full --steps 2 --warmup 1 --evals 1 --sweep-nodes 0 --sections plan_apply \
   > "$OUT/bench.json" 2> "$OUT/bench.err"
 python3 -c "import json;d=json.load(open('$OUT/bench.json'));print(json.dumps(d['configs']['plan_apply'],indent=1))"
 cd /tmp
 export TMPDIR=/tmp
-ARGS="--no-cpu --steps 1 --warmup 0 --evals 1 --sweep-nodes 0 --sections plan_apply"
+ARGS="--full --no-cpu --steps 1 --warmup 0 --evals 1 --sweep-nodes 0 --sections plan_apply"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o plan -- \
   python3 "$ROOT/bench.py" $ARGS > "$OUT/trace.log" 2>&1
 timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o fetch -- \

@@ -17,14 +17,14 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
 if [ "$MODE" = bench ]; then
-  timeout -k 10 900 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 900 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   cat "$OUT/bench.json"
   exit 0
 fi
 cd /tmp
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- \
-  python3 "$ROOT/bench.py" --no-cpu --steps 10 --warmup 2 --sections "" > "$OUT/trace.log" 2>&1
+  python3 "$ROOT/bench.py" --full --no-cpu --steps 10 --warmup 2 --sections "" > "$OUT/trace.log" 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c5trace" -o c5 -- \
   python3 "$ROOT/tools/c5_prof.py" 4 > "$OUT/c5trace.log" 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c3trace" -o c3 -- \
