@@ -40,6 +40,7 @@
 #include "engine_types.h"
 #include "gomath_dev.h"
 #include "gosort.h"
+#include "launchers.h"
 
 // ---- RCCL, bound at run time ------------------------------------------------
 // The engine's collectives (pe_comm_init / pe_place_sharded, the one-handle
@@ -130,95 +131,6 @@ const char* rc_GetErrorString(ncclResult_t r) {
     return rccl().ok ? rccl().GetErrorString(r) : rccl().error.c_str();
 }
 }  // namespace
-
-size_t pe_place_lds_bytes(bool full, int hash_bits, bool packed, size_t pset_bytes);
-hipError_t pe_launch_place(const pe::BatchArgs* a, uint32_t n_evals, bool full, hipStream_t st);
-hipError_t pe_launch_system(const pe::SystemArgs* a, hipStream_t st);
-hipError_t pe_launch_rank_of(const uint32_t* list, uint32_t n_list, uint32_t* rank_of, uint32_t n_rows, hipStream_t st);
-hipError_t pe_launch_upload(void* dst, const void* src_mapped, size_t bytes, hipStream_t st);
-hipError_t pe_launch_scatter_rows(void* dst, uint32_t words, const void* payload_mapped, uint32_t n, hipStream_t st);
-hipError_t pe_launch_counts(const pe::CountDsts* d, uint32_t nd, uint32_t n, const uint2* ents, uint32_t m,
-                            const pe::ResetArgs* r, hipStream_t st);
-size_t pe_fullpass_lds_bytes(uint32_t n);
-hipError_t pe_launch_fullpass_svc(const pe::SweepArgs* a_dev, int np, bool lean, const uint32_t* visit, uint32_t n,
-                                  uint32_t count, pe_ranked_node* out, uint32_t* state, hipStream_t st);
-hipError_t pe_launch_fullpass_lds(const pe::SweepArgs* a_dev, int np, const uint32_t* visit, uint32_t n,
-                                  uint32_t count, pe_ranked_node* out, uint32_t* state, unsigned long long* prof,
-                                  hipStream_t st);
-hipError_t pe_launch_sweep_only(const pe::SweepArgs* a, uint32_t blocks, hipStream_t st);
-hipError_t pe_launch_sweep_local(const pe::SweepArgs* a, uint32_t blocks, hipStream_t st);
-hipError_t pe_launch_trace_top(const uint32_t* codes, const double* sc, const pe::TraceSrc* src, uint32_t flags,
-                               pe_metric_score* out, uint8_t* n_out, hipStream_t st, uint32_t n_entries,
-                               uint32_t* n_other = nullptr, uint2* other_list = nullptr);
-hipError_t pe_launch_step_only(const pe::SweepArgs* a, uint32_t nrecs, const uint32_t* visit, uint32_t n,
-                               uint32_t offset, pe_ranked_node* out, uint32_t* state, hipStream_t st);
-hipError_t pe_launch_commit_rows(const pe::NodeSoA* s, const pe::TgTables* t, const pe::Ask* a, const uint32_t* rows,
-                                 uint32_t n, hipStream_t st);
-hipError_t pe_launch_evict_trace(const pe::PreemptArgs* a, const uint32_t* rows, uint32_t n, uint32_t* code,
-                                 double* named, hipStream_t st);
-hipError_t pe_launch_plan_stop(pe::NodeRec* rec, uint32_t* dev_free, const pe::PreemptAlloc* allocs,
-                               uint8_t* preempted, const uint32_t* slots, const uint32_t* rows, uint32_t n, int sign,
-                               uint64_t* core_used, const uint64_t* palloc_cores, hipStream_t st);
-hipError_t pe_launch_reset_plan(pe::NodeRec* rec, const pe::NodeRec* base_rec, uint32_t* dev_free,
-                                const uint32_t* dev_free_base, uint32_t n, uint8_t* preempted, uint32_t m,
-                                uint32_t* pcount, uint32_t keys, hipStream_t st);
-hipError_t pe_launch_commit(const pe::NodeSoA* s, const pe::TgTables* t, const pe::Ask* a, uint32_t row,
-                            uint32_t offers, hipStream_t st);
-hipError_t pe_launch_evict(const pe::PreemptArgs* a, const pe::EvictResolveArgs* r, hipStream_t st);
-hipError_t pe_launch_apply_commits(const pe::NodeSoA* s, const pe::TgTables* t, const pe::Ask* a, const uint32_t* rows,
-                                   const uint32_t* offers, uint32_t n, int sign, hipStream_t st);
-hipError_t pe_launch_evict_record(const pe::PreemptArgs* a, uint32_t row, pe_ranked_node* out, uint32_t* mask,
-                                  hipStream_t st);
-hipError_t pe_launch_commit_preempt(const pe::PreemptArgs* a, uint32_t row, const uint32_t* mask, uint8_t* preempted,
-                                    uint32_t* pcount, uint32_t* dev_free, hipStream_t st);
-hipError_t pe_launch_evict_only(const pe::PreemptArgs* a, hipStream_t st);
-hipError_t pe_launch_census(const pe::BatchArgs* a, uint32_t* counts, uint8_t* status, double* score,
-                            hipStream_t st, double* parts = nullptr, uint8_t* nparts = nullptr);
-hipError_t pe_launch_resolve(const pe::EvictResolveArgs* r, hipStream_t st);
-hipError_t pe_launch_ploop(const pe::PLoopArgs* a, hipStream_t st);
-hipError_t pe_launch_md_gate(pe::MdNet* md, const uint32_t* coll_tg, uint32_t n, hipStream_t st);
-hipError_t pe_launch_static_gate(const uint8_t* blocked, const uint32_t* coll_tg, uint32_t* gate, uint32_t n,
-                                 hipStream_t st);
-uint32_t pe_ploop_max_n(uint32_t words);
-hipError_t pe_launch_commit_evicted(const pe::PreemptArgs* a, uint8_t* preempted, uint32_t* pcount,
-                                    uint32_t* dev_free, uint32_t* placed, hipStream_t st);
-size_t pe_fold_feas_max_classes();
-hipError_t pe_launch_fold_feas_staged(const pe::NodeSoA* s, const unsigned char* class_src, uint8_t* class_dst,
-                                      uint32_t ncls, const uint8_t* node_ok, uint8_t* feas, hipStream_t st);
-hipError_t pe_launch_fold_feas(const pe::NodeSoA* s, const uint8_t* class_ok, const uint8_t* node_ok, uint8_t* feas,
-                               hipStream_t st);
-hipError_t pe_launch_sweep(const pe::SweepArgs* a, uint32_t blocks, pe::SweepRec* merged, hipStream_t st);
-hipError_t pe_launch_node_record(const pe::SweepArgs* a, uint32_t row, pe_ranked_node* out, hipStream_t st);
-hipError_t pe_launch_spread_table(const pe::TgTables* t, double* tab, hipStream_t st);
-uint32_t pe_rec_winner(const pe::SweepRec* r);
-void pe_rec_init(pe::SweepRec* r);
-void pe_rec_merge(pe::SweepRec* a, const pe::SweepRec* b);
-int pe_sweep_blocks_per_cu(bool aux);
-hipError_t pe_launch_fold_aux(const pe::NodeSoA* s, const pe::TgTables* t, const uint8_t* aff_idx_class,
-                              const uint8_t* aff_idx_node, uint32_t* aux, hipStream_t st);
-uint32_t pe_chain_max_n();
-uint32_t pe_chain_fused_max_n();
-int pe_chain_shape(uint32_t n_visit);
-uint32_t pe_chain_fused_max_count();
-uint32_t pe_chain_fused_max_classes();
-uint32_t pe_emit_grid(uint32_t count);
-uint32_t pe_chain_max_limit();
-size_t pe_chain_lds_bytes(int hash_bits, bool packed, uint32_t n);
-int pe_chain_blocks_per_cu(size_t lds);
-hipError_t pe_launch_chain(const pe::BatchArgs* a, uint32_t n_evals, uint32_t max_blocks, hipStream_t st,
-                           hipEvent_t* split = nullptr);
-hipError_t pe_launch_sweep_step(const pe::SweepArgs* a, uint32_t blocks, const uint32_t* visit, uint32_t n,
-                                uint32_t offset, pe_ranked_node* out, uint32_t* state, hipStream_t st);
-hipError_t pe_launch_sweep_loop(const pe::SweepArgs* a, uint32_t blocks, uint32_t count, const uint32_t* visit,
-                                uint32_t n, uint32_t offset, pe_ranked_node* out, uint32_t* state, hipStream_t st);
-hipError_t pe_launch_trace(const pe::NodeSoA* s, const pe::TgTables* t, const pe::Ask* a, const uint32_t* rows,
-                           uint32_t n, uint32_t* out, const uint32_t* penalty_bits, double log10,
-                           const double* spread_tab, double* scores, hipStream_t st, const uint16_t* dks = nullptr);
-hipError_t pe_launch_trace_batch(const pe::NodeSoA* s, const pe::TgTables* t, const pe::Ask* a,
-                                 const pe::TraceSrc* src, uint32_t n, uint32_t* out, double log10,
-                                 const double* spread_tab, double* scores, hipStream_t st);
-hipError_t pe_launch_spread_tables(const pe::TgTables* t, uint32_t n_rec, uint32_t* delta, double* tab,
-                                   hipStream_t st);
 
 namespace {
 
@@ -557,21 +469,74 @@ struct MemoDelta {
     int8_t v;
 };
 
+// Every environment switch of the engine (DESIGN.md lists them), read once
+// per handle by read_tunables() in pe_stack_create.
+struct Tunables {
+    // test hooks
+    uint32_t sweep_min = 1u << 15;     // PE_SWEEP_MIN: visit lists at least this long use the multi-CU sweep
+    uint32_t loop_sweep_min = 8192;    // PE_LOOP_SWEEP_MIN: full-pass count loops this long run device-resident sweeps
+    bool results_via_copy = false;     // PE_RESULTS_VIA_COPY=1: device buffer + one D2H copy
+    bool use_base = true;              // PE_WINDOW_LAZY=1: lazy per-position evaluation (k_window)
+    bool spec_on = true;               // PE_SPECULATE=0: every Select runs on its own
+    uint64_t test_fallback_every = 0;  // PE_TEST_FALLBACK_EVERY=n: every n-th Select takes the fallback path
+    int chain_items = 0;               // PE_CHAIN_ITEMS=4 / 16: a larger chain shape than the list needs
+    bool chain_fused = true;           // PE_CHAIN_FUSED set to anything: the unfused chain launches
+    bool full_lds = true;              // PE_FULL_LDS=0: no LDS-resident full-pass loop
+    bool ploop = true;                 // PE_PLOOP=0: no device preemption loop
+    bool ploop_check_dead = false;     // PE_PLOOP_CHECK_DEAD=1: k_ploop checks its dead-position bits
+    // behaviour knobs
+    bool spin_wait = true;             // PE_SPIN_WAIT=0: chain launches wait with a stream sync
+    bool counts_defer_ok = true;       // PE_COUNTS_DEFER=0: SetJob launches its counts at once
+    bool kernel_split = false;         // PE_KERNEL_SPLIT=1 (or pe_set_kernel_split): per-kernel chain events
+    // profiling, printed to stderr
+    bool api_prof = false;             // PE_API_PROF=1
+    bool place_prof = false;           // PE_PLACE_PROF set
+    bool chain_prof = false;           // PE_CHAIN_PROF set
+    bool full_prof = false;            // PE_FULL_PROF set: per-phase clocks of the LDS full-pass loop
+    bool metrics_prof = false;         // PE_METRICS_PROF set
+};
+
+static Tunables read_tunables() {
+    Tunables t;
+    auto flag = [](const char* name, bool* v) {   // NAME=0 / NAME=1
+        if (const char* e = std::getenv(name)) *v = std::atoi(e) != 0;
+    };
+    auto is_set = [](const char* name) { return std::getenv(name) != nullptr; };
+    if (const char* e = std::getenv("PE_SWEEP_MIN")) t.sweep_min = (uint32_t)std::strtoul(e, nullptr, 10);
+    if (const char* e = std::getenv("PE_LOOP_SWEEP_MIN")) t.loop_sweep_min = (uint32_t)std::strtoul(e, nullptr, 10);
+    flag("PE_RESULTS_VIA_COPY", &t.results_via_copy);
+    if (const char* e = std::getenv("PE_WINDOW_LAZY")) t.use_base = std::atoi(e) == 0;
+    flag("PE_SPECULATE", &t.spec_on);
+    if (const char* e = std::getenv("PE_TEST_FALLBACK_EVERY")) t.test_fallback_every = std::strtoull(e, nullptr, 10);
+    if (const char* e = std::getenv("PE_CHAIN_ITEMS")) t.chain_items = std::atoi(e);
+    t.chain_fused = !is_set("PE_CHAIN_FUSED");
+    flag("PE_FULL_LDS", &t.full_lds);
+    if (const char* e = std::getenv("PE_PLOOP")) t.ploop = e[0] != '0';
+    if (const char* e = std::getenv("PE_PLOOP_CHECK_DEAD")) t.ploop_check_dead = e[0] && e[0] != '0';
+    flag("PE_SPIN_WAIT", &t.spin_wait);
+    flag("PE_COUNTS_DEFER", &t.counts_defer_ok);
+    flag("PE_KERNEL_SPLIT", &t.kernel_split);
+    flag("PE_API_PROF", &t.api_prof);
+    t.place_prof = is_set("PE_PLACE_PROF");
+    t.chain_prof = is_set("PE_CHAIN_PROF");
+    t.full_prof = is_set("PE_FULL_PROF");
+    t.metrics_prof = is_set("PE_METRICS_PROF");
+    return t;
+}
+
 struct pe_stack {
     pe_config cfg{};
+    Tunables tun;                      // the environment switches, as read at create
     std::string err;
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    // per-kernel events of the windowed chain (PE_KERNEL_SPLIT / pe_set_kernel_split):
-    // before k_base, after k_base, k_chain, k_emit, k_emit_writeback of the last launch
-    bool kernel_split = false;
+    // per-kernel events of the windowed chain (tun.kernel_split): before k_base,
+    // after k_base, k_chain, k_emit, k_emit_writeback of the last launch
     bool split_valid = false;
     hipEvent_t ev_split[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double last_ms = 0;
     bool last_ms_pending = false;      // last_ms still to be read from ev0 / ev1
-    bool spin_wait = true;             // PE_SPIN_WAIT=0: chain launches wait with a stream sync
-    bool counts_defer_ok = true;       // PE_COUNTS_DEFER=0: SetJob launches its counts at once
     uint64_t nodes_gen = 1;            // bumped whenever the node table changes (apply_nodes)
     uint32_t place_seq = 0;            // completion word sequence (run_place)
     int n_cu = 256;
@@ -673,8 +638,6 @@ struct pe_stack {
     // full-scan sweep path
     DevMem d_count_ents;   // sparse per-node counts (build_collisions)
     DevMem d_rank_of, d_sweep_recs, d_sweep_merged, d_spread_tab, d_record;
-    uint32_t sweep_min = 1u << 15;     // visit lists at least this long use the multi-CU sweep
-    uint32_t loop_sweep_min = 8192;    // full-pass count loops this long run device-resident sweeps
     bool visit_unique = true;
     bool rank_of_valid = false;        // d_rank_of holds the current SetNodes list's positions
     std::vector<uint32_t> seen_stamp;  // SetNodes duplicate check
@@ -687,7 +650,6 @@ struct pe_stack {
     uint64_t gen = 1, batch_gen = 0;
     uint32_t batch_tgi = 0, batch_count = 0;
     bool batch_full = false, batch_direct = false;
-    bool results_via_copy = false;     // PE_RESULTS_VIA_COPY=1: device buffer + one D2H copy
     pe::BatchArgs batch_A{};
     PinnedMem h_batch_out, h_batch_status;
     PinnedMem h_sys_out;   // SystemStack results, staged for the caller's arrays
@@ -707,7 +669,6 @@ struct pe_stack {
     DevMem d_chain_vs;                 // k_chain per-workgroup scratch (window values by position)
     DevMem d_prof;                     // k_chain step profile (PE_CHAIN_PROF)
     bool orders_unique = true;         // every staged order lists each row at most once
-    bool use_base = true;              // PE_WINDOW_LAZY=1: lazy per-position evaluation (k_window)
     bool batch_chain = false;          // the prepared batch runs k_base + k_chain
     uint32_t chain_grid = 256;
     bool have_state = false;
@@ -844,7 +805,7 @@ struct pe_stack {
     DevMem d_identity;
     uint32_t identity_n = 0;
     DevMem d_sys_res;                     // k_system_rows outcomes by row
-    uint64_t test_fallback_every = 0, test_select_calls = 0;   // PE_TEST_FALLBACK_EVERY
+    uint64_t test_select_calls = 0;   // tun.test_fallback_every
     DevMem d_trace_rows, d_trace_out, d_trace_scores;
     PinnedMem h_trace_top;   // spec_metrics: the batched trace's ScoreMetaData and outcome codes
     DevMem d_cm_ends;        // compute_metrics: the one record's end and source (k_trace_top)
@@ -912,7 +873,6 @@ struct pe_stack {
     pe_system_view sysview{};          // the per-row cache for caller-served system Selects (pe_system_view_get)
     std::vector<uint32_t> sys_log;     // its log
     uint32_t sys_taken = 0;            // log entries taken over
-    bool spec_on = true;               // PE_SPECULATE=0: every Select runs on its own
     uint64_t spec_stats[4] = {0, 0, 0, 0};   // runs, Selects served, rollbacks, records computed
     DevMem ck_rec, ck_coll_job, ck_coll_tg, ck_dev_free, ck_pset[pe::kMaxPsets];
     DevMem d_commit_rows, d_commit_offers;
@@ -941,7 +901,6 @@ struct pe_stack {
     pe_exchange_fn xfn = nullptr;
     void* xctx = nullptr;
     void* h_xbuf = nullptr;   // pinned: this rank's record, then nranks records
-    DevMem d_sweep_done;      // k_sweep<..., MERGE> arrival counter
 
     // One handle over several devices (pe_config.device_count > 1): `kids`
     // hold replicas of the snapshot, job and plan on the other devices. The
@@ -967,7 +926,6 @@ struct pe_stack {
     std::vector<hipEvent_t> ev_xs;                   // pe_place_sharded: a pair per placement of a chunk
 
     // PE_API_PROF=1: wall time per named host step, printed at pe_stack_destroy
-    bool api_prof = false;
     std::map<std::string, std::pair<double, uint64_t>> api_acc;
 
     // ---- helpers --------------------------------------------------------
@@ -1051,9 +1009,9 @@ struct ApiScope {
     pe_stack* s;
     const char* name;
     double t0;
-    ApiScope(pe_stack* st, const char* n) : s(st), name(n), t0(st && st->api_prof ? now_us() : 0.0) {}
+    ApiScope(pe_stack* st, const char* n) : s(st), name(n), t0(st && st->tun.api_prof ? now_us() : 0.0) {}
     ~ApiScope() {
-        if (s && s->api_prof) {
+        if (s && s->tun.api_prof) {
             auto& a = s->api_acc[name];
             a.first += now_us() - t0;
             a.second++;
@@ -2250,8 +2208,7 @@ int refresh_node_rows(pe_stack* s, std::vector<uint32_t> rows, uint32_t n_old, b
                       bool cores_before) {
     const uint32_t n = (uint32_t)s->nodes.size();
     s->has_cores = s->has_cores || s->any_alloc_cores;
-    static const bool force_full = getenv("PE_UPDATE_FULL") != nullptr;   // A/B against the full build
-    if (force_full || !s->alloc_state_ok || s->h_node_alloc_off.size() != (size_t)n_old + 1 ||
+    if (!s->alloc_state_ok || s->h_node_alloc_off.size() != (size_t)n_old + 1 ||
         s->dev_packable != packable_before || s->has_cores != cores_before)
         return build_alloc_state(s);
     for (uint32_t r = n_old; r < n; r++) rows.push_back(r);
@@ -3379,7 +3336,7 @@ int build_collisions(pe_stack* s, bool own = false, bool defer = false) {
     const pe::ResetArgs R = s->reset_pending ? reset_args(s) : pe::ResetArgs{};
     // only where the next launch can be a fused k_chain (a short list): else
     // the counts launch now and run while the host prepares the first Select
-    if (defer && s->counts_defer_ok && n <= pe_chain_fused_max_n()) {
+    if (defer && s->tun.counts_defer_ok && n <= pe_chain_fused_max_n()) {
         // the entries stay in the mapped staging ring: the launch that carries
         // them reads them from there
         const uint2* staged = ents.empty() ? nullptr : reinterpret_cast<const uint2*>(stage_only(s, ents));
@@ -4171,8 +4128,7 @@ int sweep_setup(pe_stack* s, TgPlan& g, const pe_select_options* opts, uint32_t 
         int rc = build_aux(s, g, A.tg);
         if (rc) return rc;
     }
-    bool use_aux = g.aux_ok;
-    if (const char* e = std::getenv("PE_SWEEP_AUX")) use_aux = use_aux && std::atoi(e) != 0;
+    const bool use_aux = g.aux_ok;
     if (use_aux) {
         A.node_aux = g.node_aux.as<uint32_t>();
         A.aff_vals = g.aff_vals.as<double>();
@@ -4181,8 +4137,7 @@ int sweep_setup(pe_stack* s, TgPlan& g, const pe_select_options* opts, uint32_t 
     // exactly one round of resident workgroups: a grid-stride pass with no
     // tail, and few records for the merge
     uint32_t blocks = (A.row_end - A.row_begin + 256 * 8 - 1) / (256 * 8);
-    uint32_t per_cu = (uint32_t)(use_aux ? s->sweep_per_cu_aux : s->sweep_per_cu);
-    if (const char* e = std::getenv("PE_SWEEP_BPC")) per_cu = (uint32_t)std::max(1, std::atoi(e));
+    const uint32_t per_cu = (uint32_t)(use_aux ? s->sweep_per_cu_aux : s->sweep_per_cu);
     blocks = std::max<uint32_t>(1, std::min<uint32_t>(blocks, (uint32_t)s->n_cu * per_cu));
     HIP_TRY(s, s->d_sweep_recs.ensure(sizeof(pe::SweepRec) * blocks));
     HIP_TRY(s, s->d_sweep_merged.ensure(sizeof(pe::SweepRec)));
@@ -4552,7 +4507,7 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
     A.packed_overlay = packed_kbits(s, 1u << A.hash_bits, full);
     bool chain = false;
     // the phase-static chain is compiled without reserved cores (k_chain's registers)
-    if (!full && s->use_base && count > 1 && A.limit <= pe_chain_max_limit() && g.ask.cores == 0) {
+    if (!full && s->tun.use_base && count > 1 && A.limit <= pe_chain_max_limit() && g.ask.cores == 0) {
         // count loop over one rotation at a time (k_base + k_chain): needs a
         // visit list without repeated rows
         chain = true;
@@ -4567,17 +4522,14 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
         }
         if (chain) {
             // one evaluation: values in visit order (coalesced window reads)
-            // PE_BASE_BY_ROW=1: the values by row instead (k_base reads the
-            // records in row order, k_chain gathers the values through the list)
-            static const bool by_row = std::getenv("PE_BASE_BY_ROW") != nullptr;
             HIP_TRY(s, s->d_base.ensure(sizeof(double) * std::max<size_t>(std::max<size_t>(s->nodes.size(), n), 1)));
             A.base = s->d_base.as<double>();
-            A.base_by_pos = by_row ? 0 : 1;
-            HIP_TRY(s, s->d_base1.ensure(sizeof(double) * std::max<size_t>(by_row ? s->nodes.size() : n, 1)));
+            A.base_by_pos = 1;
+            HIP_TRY(s, s->d_base1.ensure(sizeof(double) * std::max<size_t>(n, 1)));
             A.base1 = s->d_base1.as<double>();
             HIP_TRY(s, s->d_chain_vs.ensure(sizeof(double) * (size_t)pe_chain_max_n()));
             A.chain_vs = s->d_chain_vs.as<double>();
-            if (std::getenv("PE_CHAIN_PROF")) {
+            if (s->tun.chain_prof) {
                 HIP_TRY(s, s->d_prof.ensure(32 * sizeof(unsigned long long)));
                 HIP_TRY(s, hipMemset(s->d_prof.p, 0, 32 * sizeof(unsigned long long)));
                 A.prof = s->d_prof.as<unsigned long long>();
@@ -4591,7 +4543,7 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
         ApiScope prof_up_(s, "run_place.upload_visit");
         const bool is_visit = &order == &s->visit;
         const unsigned char* src = nullptr;
-        if (chain && A.base_by_pos && !(is_visit && s->d_visit_is_visit)) {
+        if (chain && !(is_visit && s->d_visit_is_visit)) {
             HIP_TRY(s, s->d_visit.ensure(sizeof(uint32_t) * (size_t)n));
             src = stage_only(s, order);
         }
@@ -4627,9 +4579,9 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
     const pe::CountArgs counts_saved = s->pending_counts;
     if (chain) {
         const uint32_t base_blocks = (2u * (uint32_t)n + 63u) / 64u;
-        fused = A.base_by_pos && (uint32_t)n <= pe_chain_fused_max_n() && pe_chain_shape(n) <= 4 &&
+        fused = (uint32_t)n <= pe_chain_fused_max_n() && pe_chain_shape(n, s->tun.chain_items) <= 4 &&
                 count <= pe_chain_fused_max_count() && count <= chunk &&
-                s->nodes.size() <= 16384 && std::getenv("PE_CHAIN_FUSED") == nullptr;
+                s->nodes.size() <= 16384 && s->tun.chain_fused;
         if (fused && s->fold_pending && s->pending_fold.ncls > pe_chain_fused_max_classes()) fused = false;
         if (s->fold_pending && (fused || (size_t)s->pending_fold.ncls * base_blocks <= 256u * 1024u)) {
             A.fold = s->pending_fold;
@@ -4675,14 +4627,14 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
     }
     double total_ms = 0;
     uint32_t done = 0;
-    const bool hprof = std::getenv("PE_PLACE_PROF") != nullptr;
+    const bool hprof = s->tun.place_prof;
     double h_launch = 0, h_sync = 0, h_copy = 0;
     // The chain path ends with k_emit (or the fused k_chain), each of whose
     // workgroups raises its own completion word in the mapped h_emit_done
     // block (sequence place_seq): the host spins on them instead of waking
     // from a stream synchronisation; the launch's event timing is resolved
     // when it is asked for (pe_last_kernel_ms).
-    bool spin = chain && s->spin_wait;
+    bool spin = chain && s->tun.spin_wait;
     volatile uint32_t* flag = nullptr;
     if (spin) {
         const size_t fb = sizeof(uint32_t) * pe_emit_grid(chunk);
@@ -4708,13 +4660,13 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
             ApiScope prof_l_(s, "run_place.launch");
             if (chain) {
                 hipEvent_t* split = nullptr;
-                if (s->kernel_split) {
+                if (s->tun.kernel_split) {
                     for (auto& ev : s->ev_split)
                         if (!ev) HIP_TRY(s, hipEventCreate(&ev));
                     split = s->ev_split;
                 }
                 HIP_TRY_STATE(s, hipSuccess);   // whatever is still pending launches first
-                const hipError_t le = pe_launch_chain(&A, 1, 1, s->stream, split);
+                const hipError_t le = pe_launch_chain(&A, 1, 1, s->tun.chain_items, s->stream, split);
                 if (le != hipSuccess && done == 0) {
                     if (fold_taken) { s->pending_fold = fold_saved; s->fold_pending = true; }
                     if (counts_taken) { s->pending_counts = counts_saved; s->counts_pending = true; }
@@ -4903,16 +4855,7 @@ pe_stack* pe_stack_create(const pe_config* cfg) {
     s->sweep_per_cu = pe_sweep_blocks_per_cu(false);
     s->sweep_per_cu_aux = pe_sweep_blocks_per_cu(true);
     s->log10 = pe::gm::log_go(10.0);
-    if (const char* e = std::getenv("PE_SWEEP_MIN")) s->sweep_min = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char* e = std::getenv("PE_LOOP_SWEEP_MIN")) s->loop_sweep_min = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char* e = std::getenv("PE_RESULTS_VIA_COPY")) s->results_via_copy = std::atoi(e) != 0;
-    if (const char* e = std::getenv("PE_WINDOW_LAZY")) s->use_base = std::atoi(e) == 0;
-    if (const char* e = std::getenv("PE_SPECULATE")) s->spec_on = std::atoi(e) != 0;
-    if (const char* e = std::getenv("PE_SPIN_WAIT")) s->spin_wait = std::atoi(e) != 0;
-    if (const char* e = std::getenv("PE_COUNTS_DEFER")) s->counts_defer_ok = std::atoi(e) != 0;
-    if (const char* e = std::getenv("PE_API_PROF")) s->api_prof = std::atoi(e) != 0;
-    if (const char* e = std::getenv("PE_KERNEL_SPLIT")) s->kernel_split = std::atoi(e) != 0;
-    if (const char* e = std::getenv("PE_TEST_FALLBACK_EVERY")) s->test_fallback_every = std::strtoull(e, nullptr, 10);
+    s->tun = read_tunables();
     if (cfg->device_count > 1) {
         // replicas on the other devices, and the communicators of the group
         bool same = true;
@@ -4921,7 +4864,7 @@ pe_stack* pe_stack_create(const pe_config* cfg) {
             kc.device = cfg->device_ids[k];
             pe_stack* kid = pe_stack_create(&kc);
             if (!kid) { pe_stack_destroy(s); return nullptr; }
-            kid->test_fallback_every = 0;
+            kid->tun.test_fallback_every = 0;
             s->kids.push_back(kid);
             same = same && cfg->device_ids[k] == root_dev;
         }
@@ -4947,7 +4890,7 @@ void pe_stack_destroy(pe_stack* s) {
     for (pe_stack* k : s->kids) pe_stack_destroy(k);
     for (ncclComm_t c : s->group_comms)
         if (c) (void)rc_CommDestroy(c);
-    if (s->api_prof)
+    if (s->tun.api_prof)
         for (auto& kv : s->api_acc)
             std::fprintf(stderr, "api %-28s %10.1f us total %8llu calls %8.2f us/call\n", kv.first.c_str(),
                          kv.second.first, (unsigned long long)kv.second.second,
@@ -4986,7 +4929,7 @@ double pe_last_kernel_ms(const pe_stack* s) {
 
 int pe_set_kernel_split(pe_stack* s, int on) {
     if (!s) return PE_EINVAL;
-    s->kernel_split = on != 0;
+    s->tun.kernel_split = on != 0;
     s->split_valid = false;
     return PE_OK;
 }
@@ -6069,7 +6012,7 @@ static double g_cm_prof[4];
 static int compute_metrics(pe_stack* s, TgPlan& g, const std::vector<uint32_t>& order, uint32_t start,
                            uint32_t evaluated, const pe_select_options* opts, bool evict = false,
                            std::vector<MemoDelta>* log = nullptr, WalkCache* wc = nullptr) {
-    static const bool prof = std::getenv("PE_METRICS_PROF") != nullptr;
+    const bool prof = s->tun.metrics_prof;
     double tp = prof ? now_us() : 0.0;
     auto lap = [&](int k) {
         if (!prof) return;
@@ -6322,7 +6265,7 @@ static void spec_metrics_push(pe_stack::Spec& sp, MetricAcc& acc) {
 // the device (TraceSrc). Runs without evictions and distinct_property sets only
 // (their state differs by placements alone; spec_metrics_batched).
 static int spec_metrics(pe_stack* s, TgPlan& g, uint32_t off0) {
-    static const bool prof = std::getenv("PE_METRICS_PROF") != nullptr;
+    const bool prof = s->tun.metrics_prof;
     const double t0 = prof ? now_us() : 0.0;
     pe_stack::Spec& sp = s->spec;
     const auto& order = s->visit;
@@ -6559,7 +6502,7 @@ static int spec_copy(pe_stack* s, TgPlan& g, bool to_ckpt);
 // Whole-list windows (full passes, the nil Selects of a saturated cluster)
 // reuse one walk once the memo has settled (WalkCache).
 static int spec_metrics_replay(pe_stack* s, TgPlan& g, uint32_t off0) {
-    static const bool prof = std::getenv("PE_METRICS_PROF") != nullptr;
+    const bool prof = s->tun.metrics_prof;
     const double t0 = prof ? now_us() : 0.0;
     pe_stack::Spec& sp = s->spec;
     auto& rt = s->ref_tg_memo[g.name];
@@ -6883,9 +6826,9 @@ int pe_select(pe_stack* s, uint32_t tgi, const pe_select_options* opts, pe_ranke
     if (!s || !out) return PE_EINVAL;
     s->pre_overflow.clear();
     int rc = PE_OK;
-    if (s->cfg.stack_kind == PE_STACK_SYSTEM && !s->test_fallback_every && sys_serve(s, tgi, opts, out, &rc))
+    if (s->cfg.stack_kind == PE_STACK_SYSTEM && !s->tun.test_fallback_every && sys_serve(s, tgi, opts, out, &rc))
         return rc;
-    if (s->test_fallback_every && ++s->test_select_calls % s->test_fallback_every == 0) {
+    if (s->tun.test_fallback_every && ++s->test_select_calls % s->tun.test_fallback_every == 0) {
         // test hook: this Select is answered by the caller's Go chain (the
         // shim's PE_EUNSUPPORTED path); the engine state is the committed prefix
         rc = spec_flush(s);
@@ -6975,7 +6918,7 @@ static int select_impl(pe_stack* s, uint32_t tgi, const pe_select_options* opts,
         return rc;
     }
     const uint32_t start = s->offset;
-    if (s->limit >= s->visit.size() && s->visit.size() >= s->sweep_min && g.n_spread == (int)g.psets.size() &&
+    if (s->limit >= s->visit.size() && s->visit.size() >= s->tun.sweep_min && g.n_spread == (int)g.psets.size() &&
         s->visit_unique) {
         // a whole pass over a large list: multi-CU sweep instead of one workgroup
         rc = run_sweep_select(s, g, opts, out);
@@ -7143,7 +7086,7 @@ static int ploop_count_loop(pe_stack* s, TgPlan& g, uint32_t tgi, uint32_t count
     *handled = false;
     *placed = 0;
     const uint32_t n = (uint32_t)s->visit.size();
-    if (!count || (std::getenv("PE_PLOOP") && std::getenv("PE_PLOOP")[0] == '0')) return PE_OK;
+    if (!count || !s->tun.ploop) return PE_OK;
     if (!g.psets.empty() || g.psets_dynamic || !s->visit_unique || n == 0) return PE_OK;
     if (g.ask.cores > 0) return PE_OK;   // k_ploop is compiled without reserved cores
     if (has_static(g)) return PE_OK;  // the static port gate is rebuilt on the host after evictions
@@ -7223,10 +7166,7 @@ static int ploop_count_loop(pe_stack* s, TgPlan& g, uint32_t tgi, uint32_t count
     L.limit = s->limit;
     L.count = count;
     L.retry = retry ? 1 : 0;
-    {
-        const char* cd = std::getenv("PE_PLOOP_CHECK_DEAD");
-        L.check_dead = (cd && cd[0] && cd[0] != '0') ? 1 : 0;
-    }
+    L.check_dead = s->tun.ploop_check_dead ? 1 : 0;
     L.out = s->d_loop_out.as<pe_ranked_node>();
     L.out_mask = s->d_ploop_mask.as<uint32_t>();
     L.state = s->d_loop_state.as<uint32_t>();
@@ -7235,7 +7175,7 @@ static int ploop_count_loop(pe_stack* s, TgPlan& g, uint32_t tgi, uint32_t count
         HIP_TRY(s, hipMemsetAsync(s->d_ploop_nil.p, 0xFF, sizeof(uint32_t) * 4 * (size_t)count, s->stream));
         L.nil_out = s->d_ploop_nil.as<uint32_t>();
     }
-    const bool prof = std::getenv("PE_PLACE_PROF") != nullptr;
+    const bool prof = s->tun.place_prof;
     if (prof) {
         HIP_TRY(s, s->d_prof.ensure(24 * sizeof(unsigned long long)));
         HIP_TRY(s, hipMemsetAsync(s->d_prof.p, 0, 24 * sizeof(unsigned long long), s->stream));
@@ -7323,7 +7263,6 @@ static int sweep_count_loop(pe_stack* s, TgPlan& g, uint32_t tgi, uint32_t count
     // (256 rows each) than a single bandwidth-bound sweep would use
     blocks = std::max<uint32_t>(blocks, std::min<uint32_t>(((uint32_t)s->nodes.size() + 255) / 256,
                                                            (uint32_t)s->n_cu * (uint32_t)s->sweep_per_cu_aux));
-    if (const char* e = std::getenv("PE_LOOP_BLOCKS")) blocks = (uint32_t)std::max(1, std::atoi(e));
     HIP_TRY(s, s->d_sweep_recs.ensure(sizeof(pe::SweepRec) * blocks));
     A.recs = s->d_sweep_recs.as<pe::SweepRec>();
     HIP_TRY(s, upload_visit(s, s->visit));
@@ -7339,10 +7278,9 @@ static int sweep_count_loop(pe_stack* s, TgPlan& g, uint32_t tgi, uint32_t count
     // lists whose options fit one workgroup's LDS: the whole loop in one
     // launch (k_fullpass_lds: 16 B of LDS per option, only the committed
     // node refreshed); more options than entries -> state[5], the loops below
-    bool lds_loop = A.node_aux != nullptr && n <= kFullLdsMaxN && count > 0;
-    if (const char* e = std::getenv("PE_FULL_LDS")) lds_loop = lds_loop && std::atoi(e) != 0;
+    bool lds_loop = s->tun.full_lds && A.node_aux != nullptr && n <= kFullLdsMaxN && count > 0;
     if (lds_loop) {
-        const bool fprof = std::getenv("PE_FULL_PROF") != nullptr;   // per-phase clocks of the loop
+        const bool fprof = s->tun.full_prof;   // per-phase clocks of the loop
         DevMem d_prof;
         if (fprof) HIP_TRY(s, d_prof.ensure(12 * sizeof(unsigned long long)));
         HIP_TRY(s, hipMemsetAsync(s->d_loop_out.p, 0, sizeof(pe_ranked_node) * (size_t)count, s->stream));
@@ -7358,13 +7296,11 @@ static int sweep_count_loop(pe_stack* s, TgPlan& g, uint32_t tgi, uint32_t count
         bool svc = !fprof && count >= 8 && A.ask.n_dev == 0 && A.ask.cores == 0 && np == A.tg.n_psets &&
                    A.tg.n_psets == A.tg.n_spread;
         for (int p = 0; p < g.n_spread && svc; p++) svc = !g.psets[p]->even;
-        if (const char* e = std::getenv("PE_FULL_SVC")) svc = svc && std::atoi(e) != 0;
         if (svc) {
             ApiScope prof_k_(s, "sweep.svc_kernel+sync");
             // the lean service evaluation: asks whose dk-dependent checks are AllocsFit's alone
             bool lean = !A.ask.distinct_job && !A.ask.distinct_tg && A.ask.tg_dyn == 0 && !A.ask.has_task_net &&
                         !A.tg.static_gate && !A.tg.task_gate && !A.tg.md;
-            if (const char* e = std::getenv("PE_SVC_LEAN")) lean = lean && std::atoi(e) != 0;
             HIP_TRY_STATE(s, pe_launch_fullpass_svc(s->d_full_args.as<pe::SweepArgs>(), np, lean,
                                               s->d_visit.as<uint32_t>(), n, count,
                                               s->d_loop_out.as<pe_ranked_node>(), state, s->stream));
@@ -7393,26 +7329,7 @@ static int sweep_count_loop(pe_stack* s, TgPlan& g, uint32_t tgi, uint32_t count
         }
         if (h_state[5]) lds_loop = false;
     }
-    const char* pe_env = std::getenv("PE_LOOP_PERSISTENT");
-    // measured slower than back-to-back launches (10k nodes: 38.4 vs 34.6 us,
-    // 100k: 145 vs 91 us per placement: the agent-scope barrier fences cost
-    // more than the launch gaps they remove), so it is opt-in
-    const bool persistent = pe_env ? std::atoi(pe_env) != 0 : false;
-    if (persistent && count && !lds_loop) {
-        // one launch for the whole loop: grid barriers between the sweep and
-        // the step; at most one workgroup per CU so that all are resident
-        const uint32_t pb = std::max<uint32_t>(1, std::min<uint32_t>(blocks, (uint32_t)s->n_cu));
-        A.recs = s->d_sweep_recs.as<pe::SweepRec>();
-        HIP_TRY_STATE(s, pe_launch_sweep_loop(&A, pb, count, s->d_visit.as<uint32_t>(), n, s->offset,
-                                        s->d_loop_out.as<pe_ranked_node>(), state, s->stream));
-        HIP_TRY(s, hipMemcpyAsync(h_state, state, sizeof(h_state), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(s, hipStreamSynchronize(s->stream));
-        if (h_state[4]) {
-            s->have_state = false;   // partially committed: the caller must reload
-            return s->fail(PE_EHIP, "persistent count loop: grid barrier timed out");
-        }
-    }
-    for (uint32_t k = 0; !persistent && !lds_loop && k < count && !h_state[0]; k += chunk) {
+    for (uint32_t k = 0; !lds_loop && k < count && !h_state[0]; k += chunk) {
         const uint32_t m = std::min(chunk, count - k);
         for (uint32_t j = 0; j < m; j++)
             HIP_TRY_STATE(s, pe_launch_sweep_step(&A, blocks, s->d_visit.as<uint32_t>(), n, s->offset,
@@ -7449,7 +7366,7 @@ static inline void note_nil(pe_stack* s, uint32_t k, const pe_ranked_node& r) {
 
 static int place_impl(pe_stack* s, uint32_t tgi, uint32_t count, pe_ranked_node* out, uint32_t* placed,
                       bool retry_preempt) {
-    const bool prof = std::getenv("PE_PLACE_PROF") != nullptr;
+    const bool prof = s && s->tun.place_prof;
     const double t_enter = prof ? now_us() : 0.0;
     if (!s || (!out && count)) return PE_EINVAL;
     // compact chain records for the speculation (spec_start), honoured by the
@@ -7570,7 +7487,7 @@ static int place_impl(pe_stack* s, uint32_t tgi, uint32_t count, pe_ranked_node*
     }
     bool same_name = false;   // pe_commit would rebuild other task groups' collision counts
     for (size_t k = 0; k < s->tgs.size(); k++) same_name = same_name || (k != tgi && s->tgs[k]->name == g.name);
-    if (count && !parallel && !retry && s->limit >= nv && nv >= s->loop_sweep_min && s->visit_unique &&
+    if (count && !parallel && !retry && s->limit >= nv && nv >= s->tun.loop_sweep_min && s->visit_unique &&
         g.n_spread == (int)g.psets.size() && !same_name) {
         // A whole pass per placement over a long list: k_place would sweep it
         // with one workgroup. Here every placement is a multi-CU sweep +
@@ -7695,12 +7612,12 @@ static bool spec_serve(pe_stack* s, uint32_t tgi, const pe_select_options* opts,
 static bool spec_chain_path(pe_stack* s, TgPlan& g) {
     const uint32_t nv = (uint32_t)s->visit.size();
     (void)nv;
-    return !tg_full_scan(s, g) && !s->cfg.preempt && s->use_base && s->visit_unique &&
+    return !tg_full_scan(s, g) && !s->cfg.preempt && s->tun.use_base && s->visit_unique &&
            s->limit <= pe_chain_max_limit() && g.ask.cores == 0;
 }
 
 static bool spec_eligible(pe_stack* s, uint32_t tgi, const pe_select_options* opts) {
-    if (!s->spec_on || s->cfg.stack_kind != PE_STACK_GENERIC) return false;
+    if (!s->tun.spec_on || s->cfg.stack_kind != PE_STACK_GENERIC) return false;
     if (opts && (opts->penalty_count || opts->preferred_count || opts->preempt)) return false;
     if (!s->have_state || !s->have_job || tgi >= s->tgs.size()) return false;
     if (s->tgs[tgi]->ask.cores > 0) return false;   // the rollback kernel does not return reserved cores
@@ -8330,18 +8247,13 @@ static int place_sharded_impl(pe_stack* s, uint32_t tgi, uint32_t count, uint32_
     const size_t rec_bytes = sizeof(pe::SweepRec);
     HIP_TRY(s, s->d_sweep_recs.ensure(rec_bytes * blocks));
     HIP_TRY(s, s->d_gather.ensure(rec_bytes * (size_t)s->nranks));
-    HIP_TRY(s, s->d_sweep_done.ensure(sizeof(uint32_t)));
-    HIP_TRY(s, hipMemsetAsync(s->d_sweep_done.p, 0, sizeof(uint32_t), s->stream));
     A.recs = s->d_sweep_recs.as<pe::SweepRec>();
     A.merged = s->d_gather.as<pe::SweepRec>() + s->rank;
-    A.done = s->d_sweep_done.as<uint32_t>();
     pe::SweepArgs A2 = A;   // the step merges the gathered records
     A2.recs = s->d_gather.as<pe::SweepRec>();
     uint32_t nrecs = (uint32_t)s->nranks;
     // one rank exchanges nothing: its step merges the workgroup records itself
-    // (PE_SHARD_MERGE_ONE=1 runs the per-rank merge anyway, for measurement)
-    static const bool merge_one = std::getenv("PE_SHARD_MERGE_ONE") != nullptr;
-    const bool local_merge = s->nranks > 1 || merge_one;
+    const bool local_merge = s->nranks > 1;
     if (!local_merge) {
         A2.recs = A.recs;
         nrecs = blocks;
@@ -8532,7 +8444,7 @@ int prepare_batch(pe_stack* s, uint32_t tgi, uint32_t count) {
     A.commit = 1;
     A.writeback = 0;
     s->batch_chain = false;
-    if (!full && s->use_base && A.class_ok_stride == 0 && s->orders_unique && n <= pe_chain_max_n() && g.ask.cores == 0 &&
+    if (!full && s->tun.use_base && A.class_ok_stride == 0 && s->orders_unique && n <= pe_chain_max_n() && g.ask.cores == 0 &&
         A.limit <= pe_chain_max_limit()) {
         // one base pass shared by every evaluation, then k_chain (persistent grid)
         HIP_TRY(s, s->d_base.ensure(sizeof(double) * std::max<size_t>(s->nodes.size(), 1)));
@@ -8552,7 +8464,7 @@ int prepare_batch(pe_stack* s, uint32_t tgi, uint32_t count) {
     A.out = s->d_batch_out.as<pe_placement>();
     A.eval_status = s->d_batch_status.as<uint32_t>();
     s->batch_direct = false;
-    if (!full && !s->results_via_copy) {
+    if (!full && !s->tun.results_via_copy) {
         // the windowed kernel streams its records into the mapped host buffer
         pe_placement* o = s->h_batch_out.dev<pe_placement>();
         uint32_t* st = s->h_batch_status.dev<uint32_t>();
@@ -8610,7 +8522,7 @@ int pe_place_batch(pe_stack* s, uint32_t tgi, uint32_t count, pe_placement* out,
     const pe::BatchArgs& A = s->batch_A;
     const auto t1 = std::chrono::steady_clock::now();
     HIP_TRY(s, hipEventRecord(s->ev0, s->stream));
-    if (s->batch_chain) HIP_TRY_STATE(s, pe_launch_chain(&A, E, s->chain_grid, s->stream));
+    if (s->batch_chain) HIP_TRY_STATE(s, pe_launch_chain(&A, E, s->chain_grid, s->tun.chain_items, s->stream));
     else HIP_TRY_STATE(s, pe_launch_place(&A, E, s->batch_full, s->stream));
     HIP_TRY(s, hipEventRecord(s->ev1, s->stream));
     if (!s->batch_direct) {
@@ -9266,10 +9178,8 @@ static int multi_place(pe_stack* s, uint32_t tgi, uint32_t count, pe_ranked_node
         if (rc) return k ? s->fail(rc, "replica: " + x->err) : rc;
         HIP_TRY(s, x->d_sweep_recs.ensure(rec_bytes * blocks));
         HIP_TRY(s, x->d_gather.ensure(rec_bytes * N));
-        HIP_TRY(s, x->d_sweep_done.ensure(sizeof(uint32_t)));
         A[k].recs = x->d_sweep_recs.as<pe::SweepRec>();
         A[k].merged = x->d_gather.as<pe::SweepRec>() + k;
-        A[k].done = x->d_sweep_done.as<uint32_t>();
         A2[k] = A[k];
         A2[k].recs = x->d_gather.as<pe::SweepRec>();
         HIP_TRY(s, upload_visit(x, x->visit));
@@ -9277,7 +9187,6 @@ static int multi_place(pe_stack* s, uint32_t tgi, uint32_t count, pe_ranked_node
         HIP_TRY(s, x->d_loop_state.ensure(8 * sizeof(uint32_t)));
         HIP_TRY(s, hipStreamSynchronize(x->stream));   // uploads on the replica's own stream
         HIP_TRY(s, hipMemsetAsync(x->d_loop_state.p, 0, 8 * sizeof(uint32_t), strm(k)));
-        HIP_TRY(s, hipMemsetAsync(x->d_sweep_done.p, 0, sizeof(uint32_t), strm(k)));
         if (A[k].spread_tab) HIP_TRY(s, pe_launch_spread_table(&A[k].tg, x->d_spread_tab.as<double>(), strm(k)));
     }
     uint32_t h_state[5] = {0, 0, 0, 0, 0};

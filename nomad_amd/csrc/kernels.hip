@@ -22,11 +22,11 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <type_traits>
-#include <cstdlib>
 #include <cstring>
 #include "engine_types.h"
 #include "gomath_dev.h"
 #include "gosort.h"
+#include "launchers.h"
 
 namespace pe {
 
@@ -2659,16 +2659,10 @@ __global__ void __launch_bounds__(256) k_system_rows(SystemArgs A) {
     Overlay none;
     none.keys = nullptr;
     for (uint32_t row = blockIdx.x * blockDim.x + threadIdx.x; row < A.n_rows; row += stride) {
-        const uint32_t pos = A.rank_of[row];
-        if (pos == 0xFFFFFFFFu) continue;
+        if (A.rank_of[row] == 0xFFFFFFFFu) continue;
         NodeEval ev;
         eval_node<false>(A.soa, A.tg, A.tg.class_ok, A.ask, none, nullptr, A.log10, nullptr, row, &ev);
-        if (A.n_list) {   // the outcome at the row's list position (scattered stores, nothing waits on them)
-            A.out_score[pos] = ev.status == kOption ? ev.score : __builtin_nan("");
-            A.out_status[pos] = (uint8_t)ev.status;
-        } else {
-            A.res[row] = sys_box(ev.status, ev.score);
-        }
+        A.res[row] = sys_box(ev.status, ev.score);
         if (ev.status != kOption) continue;
         local++;
         if (!A.commit) continue;
@@ -2857,37 +2851,14 @@ __global__ void __launch_bounds__(256) k_apply_commits(NodeSoA s, TgTables t, As
 // runs the feasibility half and resolves the score-table lookups of an option.
 // Options go to a wave-private LDS ring (kQueue entries); whenever it holds 64
 // the wave runs the fp64 scoring half (two software Pow) on a full wave, so
-// the scoring is dense and no workgroup barrier sits in the loop. PF: the next
-// tile's loads are issued before the current tile is evaluated, so HBM
-// streaming overlaps the scoring. Per-lane SweepRec records, reduced per
-// workgroup at the end. Rows outside the visit list are dropped.
+// the scoring is dense and no workgroup barrier sits in the loop. Per-lane
+// SweepRec records, reduced per workgroup at the end. Rows outside the visit
+// list are dropped.
 //
 // AUX: the node's verdict, affinity index and spread values come folded in one
 // u32 per node (k_fold_aux) and resolve against LDS copies of the affinity
 // values and the spread boosts, so an option costs no dependent table load.
-// The grid's last workgroup to finish merges every workgroup's record into
-// *A.merged (a shard's one record: the all-gather then moves 80 bytes per
-// rank). Each workgroup's record store is released by its arrival count; the
-// last one acquires them all (the records cross XCDs: agent scope).
-template <int BLOCK>
-__device__ __forceinline__ void sweep_last_merge(const SweepArgs& A, SweepRec* red) {
-    __shared__ uint32_t last;
-    if (threadIdx.x == 0)
-        last = __hip_atomic_fetch_add(A.done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;   // workgroup-uniform
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    SweepRec r;
-    rec_init(r);
-    for (uint32_t i = threadIdx.x; i < gridDim.x; i += BLOCK) rec_merge(r, A.recs[i]);
-    rec_block_reduce<BLOCK>(r, red);
-    if (threadIdx.x == 0) {
-        *A.merged = r;
-        __hip_atomic_store(A.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-template <int BLOCK, bool PF, int PROBE = 0, bool AUX = false, bool MERGE = false>
+template <int BLOCK, bool AUX>
 __device__ __forceinline__ void sweep_block(const SweepArgs& A) {
     constexpr int W = BLOCK / 64;
     constexpr uint32_t kQueue = 128;
@@ -2914,8 +2885,7 @@ __device__ __forceinline__ void sweep_block(const SweepArgs& A) {
     auto score_from = [&](uint32_t at) {
         const uint32_t i = (at + (uint32_t)lane) & (kQueue - 1);
         NodeEval ev;
-        if (PROBE == 2) ev.score = wq[i].aff + wq[i].spread;
-        else score_option<false>(A.ask, A.log10, wq[i], &ev);
+        score_option<false>(A.ask, A.log10, wq[i], &ev);
         rec_add(r, wr[i], ev.score);
     };
     NodeIn nx;
@@ -2936,23 +2906,10 @@ __device__ __forceinline__ void sweep_block(const SweepArgs& A) {
             }
         }
     };
-    uint32_t tile = A.row_begin + blockIdx.x * BLOCK;
-    if (PF) fetch(tile);
-    for (; tile < A.row_end; tile += stride) {
-        NodeIn in;
-        uint32_t pos, aux;
-        if (PF) {
-            in = nx;
-            pos = npos;
-            aux = naux;
-            const uint32_t nt = tile + stride;
-            if (nt > tile && nt < A.row_end) fetch(nt);
-        } else {
-            fetch(tile);
-            in = nx;
-            pos = npos;
-            aux = naux;
-        }
+    for (uint32_t tile = A.row_begin + blockIdx.x * BLOCK; tile < A.row_end; tile += stride) {
+        fetch(tile);
+        const NodeIn in = nx;
+        const uint32_t pos = npos, aux = naux;
         const uint32_t row = tile + (uint32_t)tid;
         bool opt = false;
         uint32_t rank = 0;
@@ -2964,10 +2921,7 @@ __device__ __forceinline__ void sweep_block(const SweepArgs& A) {
             else {
                 opt = true;
                 rank = pos >= A.offset ? pos - A.offset : pos + n - A.offset;
-                if (PROBE == 1) {
-                    si.aff = si.spread = 0.0;
-                    si.penalty = 0;
-                } else if (AUX) {
+                if (AUX) {
                     si.penalty = A.penalty_bits ? (A.penalty_bits[row >> 5] >> (row & 31)) & 1u : 0u;
                     si.aff = aff_lds[aux & 255u];
                     double total = 0.0;
@@ -3001,56 +2955,11 @@ __device__ __forceinline__ void sweep_block(const SweepArgs& A) {
     if ((uint32_t)lane < qn) score_from(head);
     rec_block_reduce<BLOCK>(r, red);
     if (threadIdx.x == 0) A.recs[blockIdx.x] = r;
-    if (MERGE) sweep_last_merge<BLOCK>(A, red);
 }
 
-template <int BLOCK, bool PF, int PROBE = 0, bool AUX = false, bool MERGE = false>
+template <int BLOCK, bool AUX>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(AUX ? 4 : 5))) k_sweep(SweepArgs A) {
-    sweep_block<BLOCK, PF, PROBE, AUX, MERGE>(A);
-}
-
-// Bound probes for the sweep (PE_SWEEP_VARIANT 5 / 6): 5 streams exactly the
-// sweep's bytes with trivial arithmetic; 6 runs the scoring arithmetic on
-// register-synthesised inputs without touching memory.
-template <int BLOCK, int MODE>
-__global__ void __launch_bounds__(BLOCK) k_sweep_probe(SweepArgs A) {
-    __shared__ SweepRec red[BLOCK / 64];
-    SweepRec r;
-    rec_init(r);
-    const uint32_t stride = gridDim.x * BLOCK;
-    uint64_t acc = 0;
-    for (uint32_t row = A.row_begin + blockIdx.x * BLOCK + threadIdx.x; row < A.row_end; row += stride) {
-        if (MODE == 5) {
-            NodeIn in;
-            load_node(A.soa, A.tg, row, in);
-            acc += (uint64_t)in.r.cap_cpu + (uint64_t)in.r.used_mem + (uint64_t)in.r.cap_disk + in.r.cls + in.coll_tg +
-                   in.feas + A.rank_of[row] + (uint64_t)in.r.used_cpu + (uint64_t)in.r.cap_mem +
-                   (uint64_t)in.r.used_disk + (uint64_t)in.r.avail_mbits;
-        } else {
-            NodeIn in;
-            in.r.cap_cpu = 4000 + (row & 1023);
-            in.r.cap_mem = 8192 + (row & 2047);
-            in.r.cap_disk = 100000;
-            in.r.used_cpu = row & 511;
-            in.r.used_mem = row & 255;
-            in.r.used_disk = 0;
-            in.r.cls = row & 7;
-            in.r.avail_mbits = -1;
-            in.r.used_mbits = 0;
-            in.r.used_dyn = 0;
-            in.coll_tg = 0;
-            in.feas = (row & 3) == 0;
-            TgTables t = A.tg;
-            t.node_feas = &A.tg.class_ok[0];   // unused: in.feas drives the verdict
-            NodeEval ev;
-            ev.score = 0.0;
-            eval_loaded<false>(A.soa, t, A.tg.class_ok, A.ask, 0u, nullptr, A.log10, A.spread_tab, row, in, &ev);
-            if (ev.status == kOption) rec_add(r, row, ev.score);
-        }
-    }
-    r.filtered += (uint32_t)acc;
-    rec_block_reduce<BLOCK>(r, red);
-    if (threadIdx.x == 0) A.recs[blockIdx.x] = r;
+    sweep_block<BLOCK, AUX>(A);
 }
 
 // Merge the per-workgroup records (one 512-thread workgroup: a few records per
@@ -3913,64 +3822,6 @@ __global__ void __launch_bounds__(kFullThreads) k_fullpass_svc(const SweepArgs* 
             const_cast<double*>(A.spread_tab)[t.pset_tab_off[p] + v] = tab[t.pset_tab_off[p] + v];
 }
 
-// Grid-wide barrier of the persistent count loop (every workgroup resident;
-// the host launches at most one per CU). Stores of the whole workgroup are
-// released at agent scope before the arrival and acquired after it, so rows
-// committed by workgroup 0 on one XCD are seen by the sweeps on the others
-// (MI355X_MICROARCH.md, inter-workgroup visibility). The wait is bounded: on
-// timeout the workgroup sets state[4] and every workgroup leaves the loop.
-__device__ __forceinline__ bool grid_sync(uint32_t* state, uint32_t nblocks, uint32_t* gen) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
-    __shared__ uint32_t ok;
-    if (threadIdx.x == 0) {
-        ok = 1;
-        const uint32_t g = *gen;
-        const uint32_t arrived = __hip_atomic_fetch_add(&state[2], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1;
-        if (arrived == nblocks) {
-            __hip_atomic_store(&state[2], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&state[3], g + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            uint32_t spins = 0;
-            while (__hip_atomic_load(&state[3], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == g) {
-                if (++spins > (1u << 20) ||
-                    __hip_atomic_load(&state[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                    __hip_atomic_store(&state[4], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ok = 0;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
-        }
-        *gen = g + 1;
-    }
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    return ok != 0;
-}
-
-// Persistent full-pass count loop: every placement is sweep_block on all
-// workgroups, a grid barrier, step_block on workgroup 0 (merge, record,
-// commit, next spread table), a grid barrier. state: [0] stopped, [1] placed,
-// [2] barrier arrivals, [3] barrier generation, [4] barrier timeout.
-template <bool AUX>
-__global__ void __launch_bounds__(256) k_sweep_loop(SweepArgs A, uint32_t count, const uint32_t* visit, uint32_t n,
-                                                    uint32_t offset, pe_ranked_node* out, uint32_t* state) {
-    __shared__ uint32_t gen;
-    __shared__ uint32_t stop;
-    if (threadIdx.x == 0) gen = __hip_atomic_load(&state[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    for (uint32_t k = 0; k < count; k++) {
-        sweep_block<256, false, 0, AUX>(A);
-        if (!grid_sync(state, gridDim.x, &gen)) return;
-        if (blockIdx.x == 0) step_block(A, gridDim.x, visit, n, offset, out, state);
-        if (!grid_sync(state, gridDim.x, &gen)) return;
-        if (threadIdx.x == 0) stop = __hip_atomic_load(&state[0], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (stop) return;
-    }
-}
-
 // node_feas[row] = class_ok[cls] && node_ok[row]: one verdict byte per node so
 // the count loop issues a single dependent round trip per node.
 // Host -> device upload as a kernel: the source is page-locked mapped host
@@ -4131,18 +3982,13 @@ int pe_chain_blocks_per_cu(size_t lds) {
 }
 
 // Shape of a launch: the fewest positions per lane that hold one window of
-// the list. PE_CHAIN_ITEMS=4 / 16 asks for a larger shape (tests run every
-// shape on the same list); a smaller one than the list needs is never used.
-static int chain_items(uint32_t n_visit) {
+// the list. `forced` = 4 / 16 asks for a larger shape (tests run every shape
+// on the same list); a smaller one than the list needs is never used.
+int pe_chain_shape(uint32_t n_visit, int forced) {
     int items = n_visit > pe::kChainBlock * 4u ? 16 : (n_visit > pe::kChainBlock ? 4 : 1);
-    if (const char* e = std::getenv("PE_CHAIN_ITEMS")) {
-        const int forced = std::atoi(e);
-        if (forced > items) items = forced >= 16 ? 16 : 4;
-    }
+    if (forced > items) items = forced >= 16 ? 16 : 4;
     return items;
 }
-
-int pe_chain_shape(uint32_t n_visit) { return chain_items(n_visit); }
 
 // Largest list / count / class table a fused launch (BatchArgs::fused) takes.
 uint32_t pe_chain_fused_max_n() { return pe::kChainBlock * 4u; }
@@ -4151,8 +3997,8 @@ uint32_t pe_chain_fused_max_classes() { return pe::kFusedMaxClasses; }
 
 // split (or null): five events recorded before k_base and after k_base,
 // k_chain, k_emit and k_emit_writeback (per-kernel device time, PE_KERNEL_SPLIT)
-hipError_t pe_launch_chain(const pe::BatchArgs* a, uint32_t n_evals, uint32_t max_blocks, hipStream_t st,
-                           hipEvent_t* split) {
+hipError_t pe_launch_chain(const pe::BatchArgs* a, uint32_t n_evals, uint32_t max_blocks, int forced_items,
+                           hipStream_t st, hipEvent_t* split) {
     if (!a->base || !a->chain_vs || (a->n_visit > pe::kChainMaxN && n_evals != 1) || a->class_ok_stride ||
         a->limit > pe::kMaxChainLimit || a->count >= (1u << 18))   // redo entries pack count | position << 18
         return hipErrorInvalidValue;
@@ -4163,7 +4009,7 @@ hipError_t pe_launch_chain(const pe::BatchArgs* a, uint32_t n_evals, uint32_t ma
     const size_t lds = pe_chain_lds_bytes(a->hash_bits, a->packed_overlay != 0, a->n_visit);
     uint32_t grid = n_evals < max_blocks ? n_evals : max_blocks;
     if (grid == 0) grid = 1;
-    const int items = chain_items(a->n_visit);
+    const int items = pe_chain_shape(a->n_visit, forced_items);
     if (a->fused) {
         // one launch: fold, first-phase values, chain, records, writeback
         if (n_evals != 1 || !a->base_by_pos || a->base1 || !a->emit || !a->emit_out || items > 4 ||
@@ -4216,19 +4062,10 @@ hipError_t pe_launch_system(const pe::SystemArgs* a, hipStream_t st) {
         uint32_t b1 = (a->n_rows + 255) / 256;
         if (b1 > 8192) b1 = 8192;
         if (b1 == 0) b1 = 1;
-        static const bool scatter = [] {
-            const char* e = std::getenv("PE_SYS_SCATTER");
-            return e && e[0] == '1';
-        }();
-        if (scatter || !a->n_list) {   // outcomes stored at list positions directly (or kept by row)
-            hipLaunchKernelGGL(pe::k_system_rows, dim3(b1), dim3(256), 0, st, *a);
-            return hipGetLastError();
-        }
-        pe::SystemArgs r = *a;
-        r.n_list = 0;   // outcomes by row into res
-        hipLaunchKernelGGL(pe::k_system_rows, dim3(b1), dim3(256), 0, st, r);
-        hipLaunchKernelGGL(pe::k_system_gather, dim3((a->n_list + 255) / 256), dim3(256), 0, st, a->list, a->n_list,
-                           a->res, a->out_score, a->out_status);
+        hipLaunchKernelGGL(pe::k_system_rows, dim3(b1), dim3(256), 0, st, *a);   // outcomes by row into res
+        if (a->n_list)
+            hipLaunchKernelGGL(pe::k_system_gather, dim3((a->n_list + 255) / 256), dim3(256), 0, st, a->list,
+                               a->n_list, a->res, a->out_score, a->out_status);
         return hipGetLastError();
     }
     uint32_t blocks = (a->n_list + 255) / 256;
@@ -4468,27 +4305,14 @@ hipError_t pe_launch_fold_aux(const pe::NodeSoA* s, const pe::TgTables* t, const
     return hipGetLastError();
 }
 
-static int sweep_variant() {
-    const char* e = std::getenv("PE_SWEEP_VARIANT");
-    return e ? std::atoi(e) : 0;
+// k_sweep over `blocks` workgroups: the folded-aux form when the caller built node_aux.
+static void launch_k_sweep(const pe::SweepArgs* a, uint32_t blocks, hipStream_t st) {
+    if (a->node_aux) hipLaunchKernelGGL((pe::k_sweep<256, true>), dim3(blocks), dim3(256), 0, st, *a);
+    else hipLaunchKernelGGL((pe::k_sweep<256, false>), dim3(blocks), dim3(256), 0, st, *a);
 }
 
 hipError_t pe_launch_sweep(const pe::SweepArgs* a, uint32_t blocks, pe::SweepRec* merged, hipStream_t st) {
-    // PE_SWEEP_VARIANT selects measurement variants (tools/sweep_variants.py):
-    // 1 = next-tile prefetch, 5 = streaming-only bound probe, 6 = arithmetic-only probe.
-    if (a->node_aux) {
-        hipLaunchKernelGGL((pe::k_sweep<256, false, 0, true>), dim3(blocks), dim3(256), 0, st, *a);
-        hipLaunchKernelGGL(pe::k_sweep_merge, dim3(1), dim3(512), 0, st, (const pe::SweepRec*)a->recs, blocks, merged);
-        return hipGetLastError();
-    }
-    switch (sweep_variant()) {
-        case 1: hipLaunchKernelGGL((pe::k_sweep<256, true>), dim3(blocks), dim3(256), 0, st, *a); break;
-        case 7: hipLaunchKernelGGL((pe::k_sweep<256, false, 1>), dim3(blocks), dim3(256), 0, st, *a); break;
-        case 8: hipLaunchKernelGGL((pe::k_sweep<256, false, 2>), dim3(blocks), dim3(256), 0, st, *a); break;
-        case 5: hipLaunchKernelGGL((pe::k_sweep_probe<256, 5>), dim3(blocks), dim3(256), 0, st, *a); break;
-        case 6: hipLaunchKernelGGL((pe::k_sweep_probe<256, 6>), dim3(blocks), dim3(256), 0, st, *a); break;
-        default: hipLaunchKernelGGL((pe::k_sweep<256, false>), dim3(blocks), dim3(256), 0, st, *a); break;
-    }
+    launch_k_sweep(a, blocks, st);
     hipLaunchKernelGGL(pe::k_sweep_merge, dim3(1), dim3(512), 0, st, (const pe::SweepRec*)a->recs, blocks, merged);
     return hipGetLastError();
 }
@@ -4505,32 +4329,17 @@ hipError_t pe_launch_trace_top(const uint32_t* codes, const double* sc, const pe
     return hipGetLastError();
 }
 
-// A shard's sweep merged to one record in the same launch (a->merged,
-// a->done: the sharded count loop's exchange payload).
-// Default: k_sweep, then k_sweep_merge into *merged (a second launch queued
-// behind it); PE_SHARD_MERGE=fused: the sweep's last workgroup merges (one
-// launch, but every workgroup's release at agent scope writes back its L2).
+// A shard's sweep merged to one record (a->merged: the sharded count loop's
+// exchange payload): k_sweep, then k_sweep_merge queued behind it.
 hipError_t pe_launch_sweep_local(const pe::SweepArgs* a, uint32_t blocks, hipStream_t st) {
-    static const bool fused = [] {
-        const char* e = std::getenv("PE_SHARD_MERGE");
-        return e && std::strcmp(e, "fused") == 0;
-    }();
-    if (!a->merged || (fused && !a->done)) return hipErrorInvalidValue;
-    if (fused) {
-        if (a->node_aux) hipLaunchKernelGGL((pe::k_sweep<256, false, 0, true, true>), dim3(blocks), dim3(256), 0, st, *a);
-        else hipLaunchKernelGGL((pe::k_sweep<256, false, 0, false, true>), dim3(blocks), dim3(256), 0, st, *a);
-        return hipGetLastError();
-    }
-    if (a->node_aux) hipLaunchKernelGGL((pe::k_sweep<256, false, 0, true>), dim3(blocks), dim3(256), 0, st, *a);
-    else hipLaunchKernelGGL((pe::k_sweep<256, false>), dim3(blocks), dim3(256), 0, st, *a);
-    hipLaunchKernelGGL(pe::k_sweep_merge, dim3(1), dim3(512), 0, st, (const pe::SweepRec*)a->recs, blocks, a->merged);
-    return hipGetLastError();
+    if (!a->merged) return hipErrorInvalidValue;
+    return pe_launch_sweep(a, blocks, a->merged, st);
 }
 
 // Resident k_sweep<256> workgroups per CU (grid = one full wave of residency).
 int pe_sweep_blocks_per_cu(bool aux) {
     int nb = 0;
-    const hipError_t e = aux ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pe::k_sweep<256, false, 0, true>, 256, 0)
+    const hipError_t e = aux ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pe::k_sweep<256, true>, 256, 0)
                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pe::k_sweep<256, false>, 256, 0);
     if (e != hipSuccess || nb <= 0) nb = 4;
     return nb;
@@ -4587,8 +4396,7 @@ hipError_t pe_launch_spread_tables(const pe::TgTables* t, uint32_t n_rec, uint32
 // `blocks` workgroups, then k_sweep_step.
 hipError_t pe_launch_sweep_step(const pe::SweepArgs* a, uint32_t blocks, const uint32_t* visit, uint32_t n,
                                 uint32_t offset, pe_ranked_node* out, uint32_t* state, hipStream_t st) {
-    if (a->node_aux) hipLaunchKernelGGL((pe::k_sweep<256, false, 0, true>), dim3(blocks), dim3(256), 0, st, *a);
-    else hipLaunchKernelGGL((pe::k_sweep<256, false>), dim3(blocks), dim3(256), 0, st, *a);
+    launch_k_sweep(a, blocks, st);
     hipLaunchKernelGGL(pe::k_sweep_step, dim3(1), dim3(256), 0, st, *a, blocks, visit, n, offset, out, state);
     return hipGetLastError();
 }
@@ -4665,8 +4473,7 @@ hipError_t pe_launch_fullpass_svc(const pe::SweepArgs* a_dev, int np, bool lean,
 
 // The sweep alone (per-workgroup records into a->recs, no merge).
 hipError_t pe_launch_sweep_only(const pe::SweepArgs* a, uint32_t blocks, hipStream_t st) {
-    if (a->node_aux) hipLaunchKernelGGL((pe::k_sweep<256, false, 0, true>), dim3(blocks), dim3(256), 0, st, *a);
-    else hipLaunchKernelGGL((pe::k_sweep<256, false>), dim3(blocks), dim3(256), 0, st, *a);
+    launch_k_sweep(a, blocks, st);
     return hipGetLastError();
 }
 
@@ -4674,18 +4481,6 @@ hipError_t pe_launch_sweep_only(const pe::SweepArgs* a, uint32_t blocks, hipStre
 hipError_t pe_launch_step_only(const pe::SweepArgs* a, uint32_t nrecs, const uint32_t* visit, uint32_t n,
                                uint32_t offset, pe_ranked_node* out, uint32_t* state, hipStream_t st) {
     hipLaunchKernelGGL(pe::k_sweep_step, dim3(1), dim3(256), 0, st, *a, nrecs, visit, n, offset, out, state);
-    return hipGetLastError();
-}
-
-// The persistent loop; `blocks` must all be resident (the host keeps it at
-// most one workgroup per CU). state[0..4] zeroed by the caller.
-hipError_t pe_launch_sweep_loop(const pe::SweepArgs* a, uint32_t blocks, uint32_t count, const uint32_t* visit,
-                                uint32_t n, uint32_t offset, pe_ranked_node* out, uint32_t* state, hipStream_t st) {
-    if (a->node_aux)
-        hipLaunchKernelGGL(pe::k_sweep_loop<true>, dim3(blocks), dim3(256), 0, st, *a, count, visit, n, offset, out, state);
-    else
-        hipLaunchKernelGGL(pe::k_sweep_loop<false>, dim3(blocks), dim3(256), 0, st, *a, count, visit, n, offset, out,
-                           state);
     return hipGetLastError();
 }
 

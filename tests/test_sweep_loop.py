@@ -63,17 +63,15 @@ def test_sweep_count_loop_devices():
 
 
 @pytest.mark.gpu
-def test_persistent_count_loop_matches_oracle():
-    # the opt-in persistent variant (one launch, grid barriers) gives the same placements
-    os.environ["PE_LOOP_PERSISTENT"] = "1"
-    os.environ["PE_FULL_LDS"] = "0"   # the one-workgroup loop would take it first
+def test_multi_workgroup_count_loop_matches_oracle():
+    # the back-to-back sweep + step launches on a list the one-workgroup loop would take first
+    os.environ["PE_FULL_LDS"] = "0"
     try:
         nodes, allocs = synth.cluster_c3(2500, seed=11)
         job = synth.job_c3(100)
         perm = synth.shuffle(2500, 12)
         _, _, got = run_place(_engine_low_threshold, nodes, allocs, job, perm)
     finally:
-        del os.environ["PE_LOOP_PERSISTENT"]
         del os.environ["PE_FULL_LDS"]
     _, _, want = run_place(OracleGenericStack, nodes, allocs, job, perm)
     assert_same_placements(got, want)

@@ -33,10 +33,11 @@ cd "$ROOT"
 bash tools/headline_pmc.sh > "$OUT/headline_pmc.log" 2>&1
 cp gpurun_out/headline_pmc/headline_traffic.json "$OUT/headline_traffic.json"
 cd /tmp
-timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o fetch -- \
-  python3 "$ROOT/tools/sweep_variants.py" 16777216 0 0 > "$OUT/pmc_fetch.log" 2>&1
-timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o write -- \
-  python3 "$ROOT/tools/sweep_variants.py" 16777216 0 0 > "$OUT/pmc_write.log" 2>&1
+# the bench's own 2^24-node sweep section (six full-scan Selects after one headline step)
+timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o fetch -- \
+  python3 "$ROOT/bench.py" --full --no-cpu --steps 1 --warmup 0 --sections "" > "$OUT/pmc_fetch.log" 2>&1
+timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o write -- \
+  python3 "$ROOT/bench.py" --full --no-cpu --steps 1 --warmup 0 --sections "" > "$OUT/pmc_write.log" 2>&1
 cd "$ROOT"
 F=$(find "$OUT/pmc_fetch" -name "*counter_collection.csv" -print -quit)
 W=$(find "$OUT/pmc_write" -name "*counter_collection.csv" -print -quit)
