@@ -428,6 +428,29 @@ int pe_plan_stop(pe_stack* s, const uint32_t* allocs, uint32_t n);
  * the alloc's node when it is this alloc (generic_sched.go:644, util.go:756,
  * 1043); otherwise nothing happens. */
 int pe_plan_pop_update(pe_stack* s, uint32_t alloc);
+/* inplaceUpdate (util.go:692-806) for `n` snapshot allocs (alloc-table rows) against task group
+ * `tg_index`, in list order. For each: AppendStoppedAlloc, SetNodes([its node]), Select(tg),
+ * PopUpdate; when the Select returns an option, the updated alloc replaces the old one
+ * (the stop stays in NodeUpdate and the task group's ask is committed on the node).
+ * status[i] = 0 updated in place, 1 filtered, 2 exhausted (pe_system_place's codes);
+ * out[i] (may be NULL) is the record pe_select would have returned for that Select.
+ * *updated = number of status 0.
+ *
+ * One launch and one synchronisation whatever `n`: results and every later
+ * observable state (node records, collision and device free counts, dynamic
+ * ports and bandwidth, NodeUpdate, the plan, the EvalEligibility memo) equal
+ * those of the per-call sequence pe_plan_stop, pe_set_nodes (one row),
+ * pe_select, pe_plan_pop_update and, on an option, pe_plan_stop + pe_commit.
+ * The node list is unspecified afterwards: call pe_set_nodes before the next
+ * Select (computePlacements does, generic_sched.go:485). Updates of several
+ * task groups: one call per maximal run of one group, in order.
+ * PE_EINVAL (nothing changed): tg_index or an alloc row out of range, an alloc
+ * listed twice. PE_EUNSUPPORTED (nothing changed; the per-call sequence
+ * answers): spreads or distinct_property, reserved-cores asks, static ports,
+ * multi-device network nodes, a handle over several devices, pe_set_metrics on,
+ * a system stack with preemption enabled. */
+int pe_inplace_update(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n,
+                      pe_ranked_node* out, uint8_t* status, uint32_t* updated);
 /* Fused count loop of GenericScheduler.computePlacements (generic_sched.go:493-649)
  * for `count` fresh placements of one task group (no preferred / penalty nodes):
  * Select -> AppendAlloc repeated on the device; stops at the first nil option

@@ -891,6 +891,10 @@ struct pe_stack {
     std::map<uint32_t, std::vector<uint32_t>> node_update;
     std::vector<uint32_t> stop_count;
     DevMem d_stop_slots, d_stop_rows;
+    // pe_inplace_update: the grouped updates, the group offsets, and the
+    // results [records | outcomes] with their page-locked staging
+    DevMem d_inplace_upd, d_inplace_off, d_inplace_out;
+    PinnedMem h_inplace_out;
     bool stopped(uint32_t ai) const { return ai < stop_count.size() && stop_count[ai] > 0; }
 
     // multi-GPU handle (pe_comm_init): an RCCL communicator over the ranks'
@@ -8146,6 +8150,171 @@ static int plan_pop_update_one(pe_stack* s, uint32_t alloc) {
     return apply_stop_delta(s, gone, -1);
 }
 
+// inplaceUpdate's loop (util.go:692-806) in one launch: per
+// listed alloc the sequence pe_plan_stop, pe_set_nodes([its node]), pe_select,
+// pe_plan_pop_update and, on an option, pe_plan_stop + pe_commit, with the
+// same results and the same state afterwards. Everything that can refuse the
+// call is checked before anything changes.
+static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                              uint8_t* status, uint32_t* updated) {
+    if (!s) return PE_EINVAL;
+    if (updated) *updated = 0;
+    if (n && (!allocs || !status)) return s->fail(PE_EINVAL, "null alloc list or status array");
+    if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
+    if (!s->have_job) return s->fail(PE_ESTATE, "pe_set_job not called");
+    if (tgi >= s->tgs.size()) return s->fail(PE_EINVAL, "task group index out of range");
+    {
+        std::vector<uint32_t> sorted(allocs, allocs + n);
+        for (uint32_t ai : sorted)
+            if (ai >= s->allocs.size()) return s->fail(PE_EINVAL, "alloc index out of range");
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return s->fail(PE_EINVAL, "an alloc is listed twice");
+    }
+    if (n == 0) return PE_OK;
+    TgPlan& g = *s->tgs[tgi];
+    // what the batched path does not model: the caller's per-Select loop answers
+    const char* why = nullptr;
+    if (!s->kids.empty()) why = "a handle over several devices";
+    else if (s->metrics_on) why = "AllocMetric maps are on (pe_set_metrics)";
+    else if (s->cfg.stack_kind != PE_STACK_GENERIC && s->cfg.preempt) why = "a system stack with preemption (BinPack evicts)";
+    else if (g.ask.cores > 0) why = "a reserved-cores ask";
+    else if (has_static(g)) why = "static ports";
+    else if (!g.spreads.empty() || !s->job_spreads.empty()) why = "spreads";
+    else if (!g.distinct_props.empty()) why = "distinct_property";
+    else if (tg_md(s, g)) why = "a task network on multi-device nodes";
+    for (auto& c : s->job_constraints)
+        if (!why && c.op == "distinct_property") why = "distinct_property";
+    if (why) return s->fail(PE_EUNSUPPORTED, std::string("pe_inplace_update: ") + why);
+    if (!g.unsupported.empty()) return s->fail(PE_EUNSUPPORTED, g.unsupported);
+    if (!s->cores_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->cores_unsupported);
+    int rc = spec_flush(s);
+    if (rc) return rc;
+    s->gen++;
+    s->metrics_valid = false;
+    s->pre_overflow.clear();
+    HIP_TRY(s, hipSetDevice(s->device));
+    sys_deactivate(s);   // rows change on the device: the per-row cache is stale
+    s->sys.served_row = -1;
+    // The Selects' node lists, one after the other, as one list: the class
+    // memo is decided, and EvalEligibility replayed, in list order
+    elig_resolve(s);   // logged spans index the old list
+    s->visit.resize(n);
+    for (uint32_t i = 0; i < n; i++) s->visit[i] = s->allocs[allocs[i]].row;
+    s->d_visit_is_visit = false;
+    s->rank_of_valid = false;
+    s->visit_unique = false;
+    s->offset = 0;
+    s->limit = 2;
+    invalidate_tables(s);
+    rc = prepare_tg(s, tgi, s->visit, 0);
+    if (rc) return rc;
+    if (!g.psets.empty() || g.md_on) return s->fail(PE_EUNSUPPORTED, "pe_inplace_update: property sets or multi-device nodes");
+
+    // group by node row (stable: list order within a group), longest groups
+    // first so that the lanes of a wave walk groups of similar length
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return s->visit[x] < s->visit[y]; });
+    std::vector<std::pair<uint32_t, uint32_t>> groups;   // (begin in order, length)
+    for (uint32_t i = 0; i < n;) {
+        uint32_t j = i;
+        while (j < n && s->visit[order[j]] == s->visit[order[i]]) j++;
+        groups.emplace_back(i, j - i);
+        i = j;
+    }
+    std::stable_sort(groups.begin(), groups.end(),
+                     [](const std::pair<uint32_t, uint32_t>& x, const std::pair<uint32_t, uint32_t>& y) {
+                         return x.second > y.second;
+                     });
+    if (s->stop_count.size() != s->allocs.size()) s->stop_count.assign(s->allocs.size(), 0);
+    std::vector<pe::InplaceUpd> upd;
+    upd.reserve(n);
+    std::vector<uint32_t> group_off;
+    group_off.reserve(groups.size() + 1);
+    std::vector<uint8_t> in_state(n, 0);   // by list position: the old alloc is in the proposed state
+    for (auto& gr : groups) {
+        group_off.push_back((uint32_t)upd.size());
+        for (uint32_t k = gr.first; k < gr.first + gr.second; k++) {
+            const uint32_t i = order[k], ai = allocs[i];
+            const HostAlloc& a = s->allocs[ai];
+            const uint32_t slot = s->alloc_slot[ai];
+            pe::InplaceUpd u;
+            // pe_plan_stop's rule (apply_stop_delta): terminal allocs and those a
+            // stop or a plan preemption already took out hold nothing on the node
+            in_state[i] = !a.terminal && slot != PE_NONE && s->h_preempted[slot] == 0;
+            u.slot = in_state[i] ? slot : PE_NONE;
+            u.pos = i;
+            u.row = a.row;
+            // the collision counts hold the job's allocs that are not stopped (build_collisions)
+            u.flags = 0;
+            if (!a.terminal && a.job == s->job_id && !s->stopped(ai))
+                u.flags = pe::kInplaceOwnJob | (a.tg == g.name ? pe::kInplaceOwnTg : 0u);
+            upd.push_back(u);
+        }
+    }
+    group_off.push_back((uint32_t)upd.size());
+
+    HIP_TRY(s, upload_s(s, s->d_inplace_upd, upd));
+    HIP_TRY(s, upload_s(s, s->d_inplace_off, group_off));
+    const size_t st_off = out ? sizeof(pe::EmitRec) * (size_t)n : 0;
+    const size_t bytes = st_off + n;
+    HIP_TRY(s, s->d_inplace_out.ensure(bytes));
+    HIP_TRY(s, s->h_inplace_out.ensure(bytes));
+    unsigned char* dres = s->d_inplace_out.as<unsigned char>();
+    pe::InplaceArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.soa = soa_of(s);
+    A.tg = tables_of(g);
+    A.ask = ask_for(s, g);
+    A.group_off = s->d_inplace_off.as<uint32_t>();
+    A.upd = s->d_inplace_upd.as<pe::InplaceUpd>();
+    A.n_groups = (uint32_t)groups.size();
+    A.allocs = s->d_palloc.as<pe::PreemptAlloc>();
+    A.preempted = s->d_preempted.as<uint8_t>();
+    A.dev_free = s->dev_packable ? s->d_dev_free.as<uint32_t>() : nullptr;
+    A.palloc_cores = s->has_cores ? s->d_palloc_cores.as<uint64_t>() : nullptr;
+    A.log10 = s->log10;
+    A.out = out ? reinterpret_cast<pe::EmitRec*>(dres) : nullptr;
+    A.status = dres + st_off;
+    HIP_TRY(s, hipEventRecord(s->ev0, s->stream));
+    HIP_TRY_STATE(s, pe_launch_inplace(&A, s->stream));
+    HIP_TRY(s, hipEventRecord(s->ev1, s->stream));
+    HIP_TRY(s, hipMemcpyAsync(s->h_inplace_out.p, dres, bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));   // the call's one wait
+    float ms = 0;
+    HIP_TRY(s, hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    s->last_ms = ms;
+    s->last_ms_pending = false;
+
+    // the host mirrors, in list order, as the per-call sequence leaves them
+    const unsigned char* h = s->h_inplace_out.as<unsigned char>();
+    const pe::EmitRec* hrec = reinterpret_cast<const pe::EmitRec*>(h);
+    auto& plan = plan_of(s);
+    uint32_t up = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        status[i] = h[st_off + i];
+        if (out) widen_rec(hrec[i], &out[i]);
+        if (status[i] != 0) continue;   // stop, Select, PopUpdate: nothing remains
+        const uint32_t ai = allocs[i], row = s->allocs[ai].row;
+        up++;
+        s->node_update[row].push_back(ai);   // the in-place alloc's AppendStoppedAlloc
+        s->stop_count[ai]++;
+        if (in_state[i]) {
+            s->h_preempted[s->alloc_slot[ai]] = 2;
+            core_hold(s, ai, false);
+        }
+        plan.emplace_back(g.name, row);      // ... and its AppendAlloc
+    }
+    if (updated) *updated = up;
+    s->offer_row = -1;
+    invalidate_static(s);
+    for (auto& t : s->tgs) t->psets_built = false;   // the job's stopped allocs feed the property sets
+    elig_log_span(s, tgi, 0, n);   // every Select pulled its one node
+    // the job's own allocs per node and the other groups' collision counts
+    return build_job_counts(s);
+}
+
 // ---- multi-GPU ------------------------------------------------
 
 int pe_comm_unique_id(uint8_t* out, size_t cap) {
@@ -9471,6 +9640,12 @@ int pe_plan_pop_update(pe_stack* s, uint32_t alloc) {
     const int rc = plan_pop_update_one(s, alloc);
     if (rc == PE_OK && !s->kids.empty()) kid_log(s, 3, 0, 0, &alloc, 1);
     return rc;
+}
+
+int pe_inplace_update(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                      uint8_t* status, uint32_t* updated) {
+    PE_FLUSH_RESET(s);
+    return inplace_update_one(s, tgi, allocs, n, out, status, updated);
 }
 
 int pe_place(pe_stack* s, uint32_t tgi, uint32_t count, pe_ranked_node* out, uint32_t* placed) {

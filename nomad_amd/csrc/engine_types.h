@@ -476,4 +476,33 @@ struct SystemArgs {
     uint32_t n_rows;
 };
 
+// inplaceUpdate's loop (util.go:692-806) in one launch (k_inplace): the list's
+// updates grouped by node row, one lane per group walking its updates in list
+// order on the node's record held in registers.
+constexpr uint32_t kInplaceOwnJob = 1u;   // InplaceUpd::flags: the old alloc counts in coll_job
+constexpr uint32_t kInplaceOwnTg = 2u;    // ... and in this task group's coll_tg
+struct alignas(16) InplaceUpd {
+    uint32_t slot;    // CSR slot of the old alloc (PreemptAlloc), PE_NONE: not in the proposed state
+    uint32_t pos;     // the update's position in the caller's list
+    uint32_t row;     // its node
+    uint32_t flags;   // kInplace*
+};
+static_assert(sizeof(InplaceUpd) == 16, "InplaceUpd is one 16-byte load");
+
+struct InplaceArgs {
+    NodeSoA soa;
+    TgTables tg;
+    Ask ask;
+    const uint32_t* group_off;        // [n_groups + 1] into upd
+    const InplaceUpd* upd;            // [n] grouped by row, list order within a group
+    uint32_t n_groups;
+    const PreemptAlloc* allocs;       // [m] by CSR slot
+    uint8_t* preempted;               // [m] plan membership: 2 marks a stop
+    uint32_t* dev_free;               // [n rows] the stack's free-instance column, or null
+    const uint64_t* palloc_cores;     // [m x 4] or null (with soa.core_used)
+    double log10;
+    EmitRec* out;                     // [n] by list position, or null
+    uint8_t* status;                  // [n] by list position: 0 updated, 1 filtered, 2 exhausted
+};
+
 }  // namespace pe

@@ -3931,6 +3931,116 @@ __global__ void __launch_bounds__(256) k_md_gate(MdNet* md, const uint32_t* coll
 
 #include "evict.inc"
 
+// inplaceUpdate's loop (util.go:743-760) over a list of snapshot allocs: per
+// update AppendStoppedAlloc, a Select on the alloc's node alone, PopUpdate and,
+// on an option, the updated alloc in place of the old one. Only updates on one
+// node depend on each other: each lane owns one node group (distinct rows, no
+// atomics), keeps the node's record in registers and walks the group's updates
+// in list order. The old alloc leaves the proposed state (k_plan_stop's
+// deltas), the Select is the pipeline every other path runs (status_loaded,
+// score_into), an option adds the ask as k_system's commit does and keeps the
+// stop, anything else puts the registers back. One record store per group.
+// Two node images (current and trial) are live across the pipeline: without
+// the hint the allocator takes 130 VGPRs and a fourth wave per SIMD is lost.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_inplace(InplaceArgs A) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < A.n_groups; g += stride) {
+        const uint32_t b = A.group_off[g], e = A.group_off[g + 1];
+        if (b >= e) continue;
+        const uint32_t row = A.upd[b].row;
+        NodeIn in;
+        load_node(A.soa, A.tg, row, in);
+        if (A.dev_free) in.dev_free = A.dev_free[row];
+        uint32_t cj = A.soa.coll_job[row];
+        bool dirty = false;
+        for (uint32_t u = b; u < e; u++) {
+            const InplaceUpd x = A.upd[u];
+            NodeIn t = in;
+            uint32_t tj = cj;
+            if (x.slot != PE_NONE) {   // the old alloc leaves ProposedAllocs
+                const PreemptAlloc& p = A.allocs[x.slot];
+                t.r.used_cpu -= p.cpu;
+                t.r.used_mem -= p.mem;
+                t.r.used_disk -= p.disk;
+                t.r.used_mbits -= p.mbits;
+                t.r.used_dyn -= p.dyn;
+                for (int k = 0; k < 4 && k < (int)p.n_dev; k++) t.dev_free += byte_of(p.dev_c, k) << (8 * byte_of(p.dev_g, k));
+            }
+            if (x.flags & kInplaceOwnJob) tj -= 1u;
+            if (x.flags & kInplaceOwnTg) t.coll_tg -= 1u;
+            if (tj != cj) A.soa.coll_job[row] = tj;   // DistinctHostsIterator reads the column
+            ScoreIn si;
+            const int st = status_loaded<false>(A.soa, A.tg, A.tg.class_ok, A.ask, 0u, row, t, &si);
+            A.status[x.pos] = (uint8_t)st;
+            if (A.out) {
+                EmitRec& o = A.out[x.pos];
+                o.row = st == kOption ? (int32_t)row : -1;
+                o.n_scores = 0;
+                o.final_score = 0.0;
+                for (int k = 0; k < PE_MAX_SCORES; k++) o.scores[k] = 0.0;
+                o.nodes_evaluated = 1;
+                o.nodes_filtered = st == kFiltered;
+                o.nodes_exhausted = st == kExhausted;
+                o.new_offset = 0;   // a one-node list: the cursor wraps to its start
+                o.n_device_offers = 0;
+                for (int q = 0; q < kMaxDevReq; q++) o.device_offer_group[q] = 0;
+                o.flags = 0;
+            }
+            if (st != kOption) {
+                if (tj != cj) A.soa.coll_job[row] = cj;
+                continue;
+            }
+            if (A.out) {
+                EmitRec& o = A.out[x.pos];
+                lookup_scores(A.tg, nullptr, nullptr, row, t.r.cls, &si);
+                uint32_t ns;
+                o.final_score = score_into<true>(A.ask, A.log10, si, o.scores, &ns);
+                o.n_scores = ns;
+            }
+            if (A.ask.n_dev > 0) {   // the Select's offers, then consumed by the commit
+                const DevClass& dc = A.tg.dev_cls[t.r.cls];
+                uint32_t groups[kMaxDevReq];
+                double m;
+                uint32_t fr = t.dev_free;
+                if (dev_assign(A.ask, dc, fr, &m, groups)) {
+                    t.dev_free = fr;
+                    if (A.out) {
+                        EmitRec& o = A.out[x.pos];
+                        o.n_device_offers = (uint32_t)A.ask.n_dev;
+                        for (int q = 0; q < kMaxDevReq; q++)
+                            if (q < A.ask.n_dev) o.device_offer_group[q] = (uint16_t)groups[q];
+                    }
+                }
+            }
+            // Plan.AppendAlloc of the updated alloc; the stop stays
+            t.r.used_cpu += A.ask.cpu;
+            t.r.used_mem += A.ask.mem;
+            t.r.used_disk += A.ask.disk;
+            t.r.used_mbits += A.ask.commit_mbits;
+            t.r.used_dyn += A.ask.commit_dyn;
+            t.coll_tg += 1u;
+            cj = tj + 1u;
+            A.soa.coll_job[row] = cj;
+            in = t;
+            dirty = true;
+            if (x.slot != PE_NONE) {
+                A.preempted[x.slot] = 2;
+                if (A.soa.core_used && A.palloc_cores)   // its reserved cores leave the node's used set
+                    for (int w = 0; w < 4; w++) A.soa.core_used[4 * row + w] &= ~A.palloc_cores[4 * (size_t)x.slot + w];
+            }
+        }
+        if (!dirty) continue;
+        NodeRec& r = A.soa.rec[row];
+        r.used_cpu = in.r.used_cpu;
+        r.used_mem = in.r.used_mem;
+        r.used_disk = in.r.used_disk;
+        r.used_mbits = in.r.used_mbits;
+        r.used_dyn = in.r.used_dyn;
+        A.tg.coll_tg[row] = in.coll_tg;
+        if (A.dev_free) A.dev_free[row] = in.dev_free;
+    }
+}
+
 }  // namespace pe
 
 // ---- launch wrappers (host) ------------------------------------------------
@@ -4072,6 +4182,14 @@ hipError_t pe_launch_system(const pe::SystemArgs* a, hipStream_t st) {
     if (blocks > 2048) blocks = 2048;
     if (blocks == 0) blocks = 1;
     hipLaunchKernelGGL(pe::k_system, dim3(blocks), dim3(256), 0, st, *a);
+    return hipGetLastError();
+}
+
+hipError_t pe_launch_inplace(const pe::InplaceArgs* a, hipStream_t st) {
+    if (!a->n_groups) return hipSuccess;
+    uint32_t blocks = (a->n_groups + 255) / 256;
+    if (blocks > 2048) blocks = 2048;   // grid-stride beyond
+    hipLaunchKernelGGL(pe::k_inplace, dim3(blocks), dim3(256), 0, st, *a);
     return hipGetLastError();
 }
 

@@ -69,6 +69,9 @@ def load_engine():
         lib.pe_select_shard.restype = C.c_int
         lib.pe_select_shard.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                         C.POINTER(abi.pe_shard_rec)]
+        lib.pe_inplace_update.restype = C.c_int
+        lib.pe_inplace_update.argtypes = [C.c_void_p, C.c_uint32, abi.u32p, C.c_uint32,
+                                          C.POINTER(abi.pe_ranked_node), abi.u8p, abi.u32p]
         lib.pe_speculation_stats.restype = C.c_int
         lib.pe_speculation_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.pe_comm_unique_id.restype = C.c_int
@@ -495,6 +498,33 @@ class _Stack:
         """Plan.PopUpdate of a snapshot alloc (alloc-table row)."""
         self._check(self._fn("plan_pop_update")(self._h, int(alloc)))
 
+    def InplaceUpdate(self, tg, allocs: Sequence[int], fallback: bool = True):
+        """inplaceUpdate (util.go:692-806) of snapshot allocs (alloc-table rows)
+        against task group `tg`, in list order, in one call (pe_inplace_update).
+        Returns (records, status): records[i] the RankedNode of update i's
+        Select or None, status[i] 0 updated in place / 1 filtered / 2 exhausted.
+        The node list is unspecified afterwards: SetNodes before the next Select.
+        A job the batched path refuses (Unsupported) is answered by
+        inplace_update_by_select when `fallback`, else the refusal propagates."""
+        allocs = [int(a) for a in allocs]
+        try:
+            if not hasattr(self._lib, self._p + "inplace_update"):
+                raise Unsupported(abi.PE_EUNSUPPORTED, "no batched in-place update behind this ABI")
+            n = len(allocs)
+            a = np.ascontiguousarray(np.asarray(allocs or [0], dtype=np.uint32))
+            out = (abi.pe_ranked_node * max(1, n))()
+            status = np.zeros(max(1, n), dtype=np.uint8)
+            updated = C.c_uint32(0)
+            self._check(self._fn("inplace_update")(self._h, self._tg_index(tg), a.ctypes.data_as(abi.u32p), n, out,
+                                                   status.ctypes.data_as(abi.u8p), C.byref(updated)))
+        except Unsupported:
+            if not fallback:
+                raise
+            return inplace_update_by_select(self, tg, allocs)
+        records = [RankedNode.from_c(out[i], self.nodes) if status[i] == 0 else None for i in range(n)]
+        assert updated.value == sum(1 for r in records if r is not None)
+        return records, [int(x) for x in status[:n]]
+
     def Place(self, tg, count: int) -> List[RankedNode]:
         out = (abi.pe_ranked_node * max(1, count))()
         placed = C.c_uint32(0)
@@ -538,6 +568,35 @@ class _Stack:
         self._check(self._fn("system_place")(self._h, self._tg_index(tg), score.ctypes.data_as(abi.f64p),
                                              status.ctypes.data_as(abi.u8p), C.byref(placed)))
         return score[:n], status[:n], placed.value
+
+
+def inplace_update_by_select(stack, tg, allocs: Sequence[int]):
+    """inplaceUpdate's loop (util.go:743-760) as the per-call sequence, on any
+    stack with StopAllocs / SetNodes / SelectRaw / PopUpdate / Commit and the
+    encoded state (the engine's and the oracle's): per alloc
+    AppendStoppedAlloc, SetNodes([its node]), Select(tg), PopUpdate and, when
+    the Select returned an option, the updated alloc in place of the old one
+    (the stop again, then Commit). SelectRaw keeps a nil Select's counters,
+    which tell filtered from exhausted. Returns (records, status) in
+    InplaceUpdate's shape; the node list is left on the last alloc's node."""
+    node_row = stack.state.alloc_table.node_row
+    records, status = [], []
+    for ai in allocs:
+        ai = int(ai)
+        row = int(node_row[ai])
+        stack.StopAllocs([ai])
+        stack.SetNodes(np.asarray([row], dtype=np.uint32))
+        r = stack.SelectRaw(tg)
+        stack.PopUpdate(ai)
+        if r.row >= 0:
+            stack.StopAllocs([ai])        # the in-place alloc replaces the old one (same ID)
+            stack.Commit(tg, r.row)
+            records.append(r)
+            status.append(0)
+        else:
+            records.append(None)
+            status.append(1 if r.nodes_filtered else 2)
+    return records, status
 
 
 class GenericStack(_Stack):

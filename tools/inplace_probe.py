@@ -1,0 +1,155 @@
+"""In-place update probe: inplaceUpdate's loop (scheduler/util.go:692-806) on
+one handle and state, timed two ways through the C ABI:
+
+  (a) the per-call sequence: pe_plan_stop, pe_set_nodes (one row), pe_select,
+      pe_plan_pop_update and, on an option, pe_plan_stop + pe_commit per alloc
+  (b) pe_inplace_update, one call for the whole list
+
+at two shapes: 1000 updates of a job_c2 service on cluster_c2(10000), and an
+updated system job holding one alloc on each of 100k cluster_c4 nodes. Every
+repetition starts from the snapshot again (pe_reset_plan + pe_set_job, not
+timed); the two paths alternate; both must return the same statuses before a
+time is printed. Where every node is listed once (the system shape) the
+updates are independent, and (a) runs the first --per-call-cap of them per
+repetition (its cost per update does not depend on the list's length; a whole
+pass takes minutes); its statuses are compared with that prefix of (b)'s.
+Host clock around calls that end in a device synchronise; the kernel time of
+(b) is the engine's HIP events (pe_last_kernel_ms).
+
+    python tools/inplace_probe.py [--reps 5] [--small] [--out probe.json]
+"""
+import argparse
+import ctypes as C
+import json
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
+from nomad_amd import abi, synth  # noqa: E402
+from nomad_amd.stack import GenericStack, SystemStack  # noqa: E402
+from nomad_amd.structs import Allocation  # noqa: E402
+
+
+def service_shape(n_nodes, n_upd):
+    nodes, allocs = synth.cluster_c2(n_nodes, seed=42)
+    rng = np.random.Generator(np.random.PCG64(43))
+    base = len(allocs)
+    for k in rng.integers(0, n_nodes, size=n_upd):
+        allocs.append(Allocation(node_id=nodes[int(k)].id, job_id="svc-c2", task_group="web",
+                                 cpu_shares=500, memory_mb=256, disk_mb=150, priority=50))
+    job = synth.job_c2(n_upd)
+    job.version = 2
+    job.task_groups[0].tasks[0].cpu = 600
+    upd = base + rng.permutation(n_upd)
+    return GenericStack(), nodes, allocs, job, upd.astype(np.uint32)
+
+
+def system_shape(n_nodes):
+    nodes, allocs = synth.cluster_c4(n_nodes, seed=11)
+    base = len(allocs)
+    for nd in nodes:
+        allocs.append(Allocation(node_id=nd.id, job_id="mock-system-0", task_group="web", cpu_shares=500,
+                                 memory_mb=256, disk_mb=300, net_mbits=50, dyn_ports=1, priority=100))
+    job = synth.mock_system_job()
+    job.version = 2
+    job.task_groups[0].tasks[0].cpu = 600
+    upd = base + np.random.Generator(np.random.PCG64(12)).permutation(n_nodes)
+    return SystemStack(), nodes, allocs, job, upd.astype(np.uint32)
+
+
+def per_call(st, upd, node_row):
+    """(a): the statuses of the per-call sequence, straight through ctypes."""
+    lib, h = st._lib, st._h
+    out, opts = abi.pe_ranked_node(), abi.pe_select_options()
+    one, row = (C.c_uint32 * 1)(), (C.c_uint32 * 1)()
+    status = np.empty(len(upd), dtype=np.uint8)
+    for i, ai in enumerate(upd):
+        one[0], row[0] = int(ai), int(node_row[ai])
+        rc = lib.pe_plan_stop(h, one, 1) or lib.pe_set_nodes(h, row, 1, None) or \
+            lib.pe_select(h, 0, C.byref(opts), C.byref(out)) or lib.pe_plan_pop_update(h, one[0])
+        if rc == 0 and out.row >= 0:
+            rc = lib.pe_plan_stop(h, one, 1) or lib.pe_commit(h, 0, out.row)
+        st._check(rc)
+        status[i] = 0 if out.row >= 0 else (1 if out.nodes_filtered else 2)
+    return status
+
+
+def batched(st, upd, recs, status):
+    """(b): one pe_inplace_update."""
+    updated = C.c_uint32(0)
+    st._check(st._lib.pe_inplace_update(st._h, 0, upd.ctypes.data_as(abi.u32p), len(upd), recs,
+                                        status.ctypes.data_as(abi.u8p), C.byref(updated)))
+    return updated.value
+
+
+def measure(name, shape, reps, cap):
+    st, nodes, allocs, job, upd = shape
+    st.SetState(nodes, allocs)
+    st._lib.pe_flush.restype = C.c_int
+    st._lib.pe_flush.argtypes = [C.c_void_p]
+    node_row = np.ctypeslib.as_array(st.state.alloc_table.node_row, shape=(len(allocs),)).copy()
+    n = len(upd)
+    # (a) over the first `cap` updates only when no node is listed twice: the
+    # updates are independent then, so the prefix costs and answers the same
+    # inside the whole list, and a whole pass of (a) would take minutes
+    na = n
+    if cap and n > cap and len(np.unique(node_row[upd])) == n:
+        na = cap
+    recs = (abi.pe_ranked_node * n)()
+    sb = np.empty(n, dtype=np.uint8)
+    ta, tb, tk = [], [], []
+    for rep in range(reps + 1):   # the first repetition warms both paths up
+        for path in ("a", "b"):
+            st.ResetPlan()
+            st.SetJob(job)
+            st._check(st._lib.pe_flush(st._h))
+            t0 = time.perf_counter()
+            if path == "a":
+                sa = per_call(st, upd[:na], node_row)
+            else:
+                batched(st, upd, recs, sb)
+            dt = (time.perf_counter() - t0) * 1e6
+            if rep:
+                (ta if path == "a" else tb).append(dt)
+                if path == "b":
+                    tk.append(st.last_kernel_ms() * 1e3)
+        assert np.array_equal(sa, sb[:na]), "the two paths disagree"
+        print("# %s: repetition %d of %d done" % (name, rep, reps), file=sys.stderr, flush=True)
+    a, b, k = np.median(ta) * (n / na), np.median(tb), np.median(tk)
+    ta = [x * (n / na) for x in ta]   # per-update figures below divide by n
+    res = {"shape": name, "updates": n, "per_call_updates_timed": na, "nodes": len(nodes), "reps": reps,
+           "status_counts": [int((sb == v).sum()) for v in (0, 1, 2)],
+           "per_call_us_per_update": a / n, "per_call_us_min_max": [min(ta) / n, max(ta) / n],
+           "batched_us_per_update": b / n, "batched_us_min_max": [min(tb) / n, max(tb) / n],
+           "batched_call_us": b, "ratio_per_call_over_batched": a / b,
+           "k_inplace_us": k, "k_inplace_us_min_max": [min(tk), max(tk)]}
+    st.close()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--small", action="store_true", help="toy sizes (a rehearsal of the tool, not a measurement)")
+    ap.add_argument("--per-call-cap", type=int, default=2000,
+                    help="updates path (a) runs per repetition when every node is listed once (0: all)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    shapes = [("service: %d updates" % (50 if args.small else 1000),
+               lambda: service_shape(500 if args.small else 10000, 50 if args.small else 1000)),
+              ("system: one alloc per node", lambda: system_shape(2000 if args.small else 100000))]
+    results = []
+    for name, make in shapes:
+        r = measure(name, make(), args.reps, args.per_call_cap)
+        results.append(r)
+        print(json.dumps(r), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/inplace_probe.py", "small": args.small, "results": results}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
