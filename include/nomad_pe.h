@@ -491,6 +491,50 @@ int pe_system_place(pe_stack* s, uint32_t tg_index, double* out_score,
 /* The last pe_system_place's results in the engine's staging (score[n],
  * status[n], as above), valid until the next pe_system_place on the handle. */
 int pe_system_results(const pe_stack* s, const double** score, const uint8_t** status, uint32_t* n);
+/* SystemScheduler.computePlacements (scheduler_system.go:283-425) for a job
+ * with several task groups, in one pass. The call covers every position pos of
+ * the SetNodes list, in order, and within a position every listed group k, in
+ * list order: each (position, group) pair is one single-node Select of
+ * tg_indices[k] on list[pos], followed on an option by Plan.AppendAlloc.
+ * Nodes do not interact under the refusals below, so every result and every
+ * later observable state (node records, the job's and each group's collision
+ * counts and device free counts, dynamic ports and bandwidth, the plan, the
+ * EvalEligibility memo and its log) equals that of the sequence
+ * pe_system_place(tg_indices[0]), ..., pe_system_place(tg_indices[n_tg-1]) on
+ * the same handle. The reference visits the groups of one node in Go map order
+ * (diffSystemAllocsForNode ranges over a map), so any fixed group order is one
+ * of the reference's answers.
+ *
+ * Results, entry e = pos * n_tg + k:
+ *   out_status2: 2 bits per entry, four entries per byte: entry e in byte
+ *     e >> 2 at bits 2 * (e & 3); pe_system_place's codes (0 placed,
+ *     1 filtered, 2 exhausted); unused bits of the last byte are 0.
+ *     (n * n_tg + 3) / 4 bytes.
+ *   out_score: dense, the FinalScore of the placed entries only, in increasing
+ *     e; sized n * n_tg by the caller, the first *placed values are written.
+ *   counts[3 * k + code]: entries of group k per outcome (queuedAllocs and
+ *     CoalescedFailures of computePlacements).
+ * out_score, out_status2 and counts are all NULL or all set; NULL: the results
+ * stay in the engine's page-locked staging, read through
+ * pe_system_groups_results, valid until the next pe_system_place* call on the
+ * handle. An empty list returns PE_OK with *placed == 0.
+ *
+ * PE_EINVAL (nothing changed): n_tg == 0, an index out of range, a group
+ * listed twice, a mixed NULL / non-NULL set of output arrays. PE_ESTATE: not a
+ * system stack. PE_EUNSUPPORTED (checked before anything changes; the
+ * per-group or per-Select calls answer): duplicate rows in the list,
+ * preemption enabled on the stack, distinct_property at job or group level, a
+ * reserved-cores ask, static ports in a listed group, a task network on a
+ * snapshot with multi-NIC nodes, device asks in more than one listed group,
+ * pe_set_metrics on, a handle over several devices, a listed group whose own
+ * unsupported reason is set. */
+int pe_system_place_groups(pe_stack* s, const uint32_t* tg_indices, uint32_t n_tg,
+                           double* out_score, uint8_t* out_status2,
+                           uint32_t* counts, uint32_t* placed);
+/* The last pe_system_place_groups' results in the engine's staging (layout as
+ * above; score holds *placed values). */
+int pe_system_groups_results(const pe_stack* s, const double** score, const uint8_t** status2,
+                             const uint32_t** counts, uint32_t* n, uint32_t* n_tg, uint32_t* placed);
 /* Full-scan Select sharded over GPUs (one process per GPU, each holding the
  * same snapshot, job, SetNodes list and plan). Each rank sweeps
  * the snapshot rows [row_begin, row_end) it owns into a pe_shard_rec: the

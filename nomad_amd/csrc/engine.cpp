@@ -703,6 +703,10 @@ struct pe_stack {
         bool active = false;
         uint32_t name = 0, n = 0;
         const uint8_t* status = nullptr;
+        // pe_system_place_groups: the listed groups' names and the packed
+        // 2-bit outcomes (entry pos * names.size() + k); entries in tg-major order
+        std::vector<uint32_t> names;
+        const uint8_t* status2 = nullptr;
     } plan_defer;
 
     // SpreadIterator bookkeeping (spread.go:99-102, 254)
@@ -895,6 +899,16 @@ struct pe_stack {
     // results [records | outcomes] with their page-locked staging
     DevMem d_inplace_upd, d_inplace_off, d_inplace_out;
     PinnedMem h_inplace_out;
+    // pe_system_place_groups: the groups' tables, the outcomes by (node,
+    // group), the packed result [outcome bytes | dense scores], the tile
+    // counts and the counter slots; the staged result and the mapped header
+    // words (placed, then 3 counters per group)
+    DevMem d_sysg_groups, d_sysg_res, d_sysg_out, d_sysg_tiles, d_sysg_counts;
+    PinnedMem h_sysg_out, h_sysg_hdr;
+    std::vector<uint32_t> sysg_counts;
+    uint32_t sysg_n = 0, sysg_ntg = 0, sysg_placed = 0;
+    bool sysg_valid = false;
+    const void* sysg_counts_zeroed = nullptr;   // the counter block k_sysg_scan last left zero (null: unknown)
     bool stopped(uint32_t ai) const { return ai < stop_count.size() && stop_count[ai] > 0; }
 
     // multi-GPU handle (pe_comm_init): an RCCL communicator over the ranks'
@@ -973,6 +987,16 @@ static void plan_settle(pe_stack* s) {
     if (!d.active) return;
     d.active = false;
     const uint32_t n = std::min<uint32_t>(d.n, (uint32_t)s->visit.size());
+    if (!d.names.empty()) {   // as the per-group calls append them: group after group, list order within
+        const size_t G = d.names.size();
+        for (size_t k = 0; k < G; k++)
+            for (uint32_t i = 0; i < n; i++) {
+                const size_t e = (size_t)i * G + k;
+                if (((d.status2[e >> 2] >> (2 * (e & 3))) & 3u) == 0) s->plan.emplace_back(d.names[k], s->visit[i]);
+            }
+        d.names.clear();
+        return;
+    }
     size_t p = 0;
     for (uint32_t i = 0; i < n; i++) p += d.status[i] == 0;
     const size_t base = s->plan.size();
@@ -5215,6 +5239,7 @@ static int update_nodes_one(pe_stack* s, const pe_strtab* strs, const pe_node_ta
 static int reset_plan_one(pe_stack* s, bool may_defer) {
     if (!s) return PE_EINVAL;
     s->plan_defer.active = false;   // the plan is emptied below
+    s->plan_defer.names.clear();
     ApiScope prof_(s, "reset_plan");
     if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
     spec_drop(s);
@@ -8925,6 +8950,7 @@ static int system_place_impl(pe_stack* s, uint32_t tgi, double* out_score, uint8
         // read (plan_settle; ResetPlan drops it), from the staged outcomes when
         // the caller reads them there, else from its copy
         s->plan_defer.active = true;
+        s->plan_defer.names.clear();
         s->plan_defer.name = g.name;
         s->plan_defer.n = n;
         s->plan_defer.status = s->h_sys_out.as<uint8_t>() + st_off;
@@ -9700,6 +9726,199 @@ int pe_system_place(pe_stack* s, uint32_t tgi, double* out_score, uint8_t* out_s
     const int rc = system_place_one(s, tgi, out_score, out_status, placed);
     if (!s->kids.empty()) s->kids_valid = false;   // evictions / distinct_property: not replayable
     return rc;
+}
+
+// SystemScheduler.computePlacements' loop over (node, task group) in one pass
+// (DESIGN.md §32): results and state equal those of pe_system_place of each
+// listed group in turn. Everything that can refuse the call is checked before
+// anything changes; then system_place_impl's order of work with one upload,
+// the kernels and one wait, and the host mirrors group after group.
+static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n_tg, double* out_score,
+                                    uint8_t* out_status2, uint32_t* counts, uint32_t* placed) {
+    if (placed) *placed = 0;
+    if (n_tg == 0 || !tgs) return s->fail(PE_EINVAL, "pe_system_place_groups: no task group listed");
+    if ((!out_score) != (!out_status2) || (!out_score) != (!counts))
+        return s->fail(PE_EINVAL, "pe_system_place_groups: the output arrays are all null or all set");
+    if (s->cfg.stack_kind != PE_STACK_SYSTEM) return s->fail(PE_ESTATE, "pe_system_place_groups needs a system stack");
+    if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
+    if (!s->have_job) return s->fail(PE_ESTATE, "pe_set_job not called");
+    {
+        std::vector<uint32_t> sorted(tgs, tgs + n_tg);
+        for (uint32_t t : sorted)
+            if (t >= s->tgs.size()) return s->fail(PE_EINVAL, "task group index out of range");
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return s->fail(PE_EINVAL, "a task group is listed twice");
+    }
+    // what the pass does not model: the per-group or per-Select calls answer
+    const char* why = nullptr;
+    uint32_t n_dev_groups = 0;
+    if (!s->visit_unique) why = "duplicate rows in the system placement list";
+    else if (s->cfg.preempt) why = "preemption is enabled (BinPack evicts)";
+    else if (s->metrics_on) why = "AllocMetric maps are on (pe_set_metrics)";
+    else if (!s->kids.empty()) why = "a handle over several devices";
+    for (auto& c : s->job_constraints)
+        if (!why && c.op == "distinct_property") why = "distinct_property";
+    for (uint32_t k = 0; k < n_tg && !why; k++) {
+        const TgPlan& g = *s->tgs[tgs[k]];
+        if (!g.distinct_props.empty()) why = "distinct_property";
+        else if (g.ask.cores > 0) why = "a reserved-cores ask";
+        else if (has_static(g)) why = "static ports";
+        else if (tg_md(s, g)) why = "a task network on multi-device nodes";
+        else if (!g.dev_reqs.empty() && ++n_dev_groups > 1) why = "device asks in more than one listed group";
+    }
+    if (why) return s->fail(PE_EUNSUPPORTED, std::string("pe_system_place_groups: ") + why);
+    for (uint32_t k = 0; k < n_tg; k++)
+        if (!s->tgs[tgs[k]]->unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->tgs[tgs[k]]->unsupported);
+    if (!s->cores_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->cores_unsupported);
+
+    plan_settle(s);
+    {
+        const int frc = spec_flush(s);
+        if (frc) return frc;
+    }
+    HIP_TRY(s, hipSetDevice(s->device));
+    for (uint32_t k = 0; k < n_tg; k++) {   // the class memo as the calls in turn decide it
+        const int rc = prepare_tg(s, tgs[k], s->visit, 0);
+        if (rc) return rc;
+        const TgPlan& g = *s->tgs[tgs[k]];
+        if (g.psets.size() > (size_t)g.n_spread || g.md_on)
+            return s->fail(PE_EUNSUPPORTED, "pe_system_place_groups: property sets or multi-device nodes");
+    }
+    const uint32_t n = (uint32_t)s->visit.size();
+    const size_t E = (size_t)n * n_tg;
+    if (E >= (size_t(1) << 31)) return s->fail(PE_EUNSUPPORTED, "pe_system_place_groups: more than 2^31 entries");
+    s->sysg_valid = false;
+    s->sysg_counts.assign(3 * (size_t)n_tg, 0);
+    const size_t sb = ((E + 3) / 4 + 7) & ~(size_t)7;   // outcome bytes, the scores 8-byte aligned behind them
+    uint32_t p = 0;
+    bool any_dev = false;
+    if (n) {
+        std::vector<pe::SysGroup> groups(n_tg);
+        for (uint32_t k = 0; k < n_tg; k++) {
+            TgPlan& g = *s->tgs[tgs[k]];
+            groups[k].tg = tables_of(g);
+            groups[k].ask = ask_for(s, g);
+            any_dev = any_dev || groups[k].ask.n_dev > 0;
+        }
+        HIP_TRY(s, upload_visit(s, s->visit));
+        HIP_TRY(s, upload_s(s, s->d_sysg_groups, groups));
+        const uint32_t nn = (uint32_t)s->nodes.size();
+        const bool by_row = (uint64_t)n * 4 >= nn;   // system_place_impl's threshold
+        const uint32_t n_tiles = (uint32_t)((E + pe::kSysTile - 1) / pe::kSysTile);
+        const size_t cnt_bytes = sizeof(uint32_t) * pe::kPlacedSlots * 3 * (size_t)n_tg;
+        HIP_TRY(s, s->d_sysg_res.ensure(sizeof(uint64_t) * (by_row ? (size_t)nn * n_tg : E)));
+        HIP_TRY(s, s->d_sysg_out.ensure(sb + sizeof(double) * E));
+        HIP_TRY(s, s->h_sysg_out.ensure(sb + sizeof(double) * E));
+        HIP_TRY(s, s->d_sysg_tiles.ensure(sizeof(uint32_t) * n_tiles));
+        if (cnt_bytes > s->d_sysg_counts.bytes) s->sysg_counts_zeroed = nullptr;   // a new block follows
+        HIP_TRY(s, s->d_sysg_counts.ensure(cnt_bytes));
+        HIP_TRY(s, s->h_sysg_hdr.ensure(sizeof(uint32_t) * (1 + 3 * (size_t)n_tg)));
+        uint32_t* hdr = s->h_sysg_hdr.as<uint32_t>();
+        uint32_t* hdr_dev = s->h_sysg_hdr.dev<uint32_t>();
+        if (!hdr_dev) return s->fail(PE_EHIP, "pe_system_place_groups: no device view of the header words");
+        // k_sysg_scan leaves the slots zero: a memset only for a new block or after a failed call
+        if (s->sysg_counts_zeroed != s->d_sysg_counts.p)
+            HIP_TRY(s, hipMemsetAsync(s->d_sysg_counts.p, 0, s->d_sysg_counts.bytes, s->stream));
+        s->sysg_counts_zeroed = nullptr;
+        pe::SystemGroupsArgs A;
+        std::memset(&A, 0, sizeof(A));
+        A.soa = soa_of(s);
+        A.groups = s->d_sysg_groups.as<pe::SysGroup>();
+        A.n_tg = n_tg;
+        A.list = s->d_visit.as<uint32_t>();
+        A.n_list = n;
+        A.dev_free = any_dev ? s->d_dev_free.as<uint32_t>() : nullptr;
+        A.log10 = s->log10;
+        A.res = s->d_sysg_res.as<uint64_t>();
+        A.counts = s->d_sysg_counts.as<uint32_t>();
+        HIP_TRY(s, hipEventRecord(s->ev0, s->stream));   // the timed device work
+        if (by_row) {
+            HIP_TRY(s, s->d_rank_of.ensure(sizeof(uint32_t) * (size_t)std::max<uint32_t>(nn, 1)));
+            if (!s->rank_of_valid)
+                HIP_TRY(s, pe_launch_rank_of(s->d_visit.as<uint32_t>(), n, s->d_rank_of.as<uint32_t>(), nn, s->stream));
+            s->rank_of_valid = true;
+            A.rank_of = s->d_rank_of.as<uint32_t>();
+            A.n_rows = nn;
+        }
+        HIP_TRY_STATE(s, pe_launch_system_groups(&A, s->stream));
+        pe::SysCompactArgs Cx;
+        std::memset(&Cx, 0, sizeof(Cx));
+        Cx.res = A.res;
+        Cx.list = by_row ? A.list : nullptr;
+        Cx.n_tg = n_tg;
+        Cx.n_entries = (uint32_t)E;
+        Cx.n_tiles = n_tiles;
+        Cx.status2 = s->d_sysg_out.as<uint8_t>();
+        Cx.tile_off = s->d_sysg_tiles.as<uint32_t>();
+        Cx.score = reinterpret_cast<double*>(s->d_sysg_out.as<uint8_t>() + sb);
+        Cx.counts = A.counts;
+        Cx.hdr = hdr_dev;
+        HIP_TRY(s, pe_launch_system_compact(&Cx, s->stream));
+        HIP_TRY(s, hipEventRecord(s->ev1, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));   // the kernels' wait: the header words are in host memory
+        s->sysg_counts_zeroed = s->d_sysg_counts.p;
+        p = hdr[0];
+        if ((size_t)p > E) return s->fail(PE_EINTERNAL, "pe_system_place_groups: placed count beyond the entries");
+        std::memcpy(s->sysg_counts.data(), hdr + 1, sizeof(uint32_t) * 3 * (size_t)n_tg);
+        // one DMA: the outcome bytes and the placed entries' scores behind them
+        HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p, hipMemcpyDeviceToHost,
+                                  s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
+        float ms = 0;
+        HIP_TRY(s, hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        s->last_ms = ms;
+        s->last_ms_pending = false;
+    }
+    s->sysg_n = n;
+    s->sysg_ntg = n_tg;
+    s->sysg_placed = p;
+    s->sysg_valid = true;
+    if (out_score && n) {
+        const uint8_t* h = s->h_sysg_out.as<uint8_t>();
+        std::memcpy(out_status2, h, (E + 3) / 4);
+        std::memcpy(out_score, h + sb, sizeof(double) * (size_t)p);
+    }
+    if (counts) std::memcpy(counts, s->sysg_counts.data(), sizeof(uint32_t) * 3 * (size_t)n_tg);
+    if (placed) *placed = p;
+    // the host mirrors, group after group, as the calls in turn leave them
+    s->gen += n_tg;
+    if (n) {   // Plan.AppendAlloc of every placed entry: written when the plan is next read
+        s->plan_defer.active = true;
+        s->plan_defer.n = n;
+        s->plan_defer.names.resize(n_tg);
+        for (uint32_t k = 0; k < n_tg; k++) s->plan_defer.names[k] = s->tgs[tgs[k]]->name;
+        s->plan_defer.status2 = s->h_sysg_out.as<uint8_t>();
+    }
+    sys_deactivate(s);   // rows committed on the device: the per-row cache is stale
+    for (uint32_t k = 0; k < n_tg; k++) {
+        elig_log_span(s, tgs[k], 0, n);   // one single-node Select per row and group
+        invalidate_job_distinct(s, tgs[k]);
+    }
+    return PE_OK;
+}
+
+int pe_system_place_groups(pe_stack* s, const uint32_t* tg_indices, uint32_t n_tg, double* out_score,
+                           uint8_t* out_status2, uint32_t* counts, uint32_t* placed) {
+    PE_FLUSH_RESET(s);
+    if (!s) return PE_EINVAL;
+    s->pre_overflow.clear();
+    return system_place_groups_impl(s, tg_indices, n_tg, out_score, out_status2, counts, placed);
+}
+
+int pe_system_groups_results(const pe_stack* s, const double** score, const uint8_t** status2,
+                             const uint32_t** counts, uint32_t* n, uint32_t* n_tg, uint32_t* placed) {
+    if (!s || !score || !status2 || !counts || !n || !n_tg || !placed) return PE_EINVAL;
+    if (!s->sysg_valid) return PE_ESTATE;
+    const size_t E = (size_t)s->sysg_n * s->sysg_ntg;
+    const size_t sb = ((E + 3) / 4 + 7) & ~(size_t)7;
+    *status2 = s->h_sysg_out.as<uint8_t>();
+    *score = s->h_sysg_out.p ? reinterpret_cast<const double*>(s->h_sysg_out.as<uint8_t>() + sb) : nullptr;
+    *counts = s->sysg_counts.data();
+    *n = s->sysg_n;
+    *n_tg = s->sysg_ntg;
+    *placed = s->sysg_placed;
+    return PE_OK;
 }
 
 uint32_t pe_device_count(const pe_stack* s) { return s ? (uint32_t)s->kids.size() + 1u : 0u; }

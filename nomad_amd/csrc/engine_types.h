@@ -505,4 +505,46 @@ struct InplaceArgs {
     uint8_t* status;                  // [n] by list position: 0 updated, 1 filtered, 2 exhausted
 };
 
+// SystemScheduler.computePlacements' loop over (node, task group) in one pass
+// (k_system_groups): one lane per list position walks the listed groups in
+// order on the node's record held in registers. Entry e = pos * n_tg + k.
+constexpr uint32_t kSysGroupsChunk = 8;       // groups per k_system_groups launch
+constexpr uint32_t kSysTile = 1024;           // entries per compaction workgroup (256 lanes x 4)
+struct SysGroup {                             // one listed group, read wave-uniformly from HBM
+    TgTables tg;
+    Ask ask;
+};
+
+struct SystemGroupsArgs {
+    NodeSoA soa;
+    const SysGroup* groups;           // [n_tg] in list order
+    uint32_t n_tg;                    // every listed group (the stride of res)
+    uint32_t k0, nk;                  // this launch walks groups [k0, k0 + nk), nk <= kSysGroupsChunk
+    const uint32_t* list;             // SetNodes list
+    uint32_t n_list;
+    const uint32_t* rank_of;          // row-order form: [n_rows] list position or PE_NONE; null: list order
+    uint32_t n_rows;
+    uint32_t* dev_free;               // [n rows] the stack's free-instance column, or null (no device ask)
+    double log10;
+    // outcome of (node, group): the FinalScore or sys_box's NaN, at
+    // [row * n_tg + k] in the row-order form, else at [pos * n_tg + k]
+    uint64_t* res;
+    uint32_t* counts;                 // [kPlacedSlots][3 * n_tg] per-group outcome counters
+};
+
+// Ordered compaction of res into the packed result: 2-bit outcomes, the
+// per-tile placed counts, their exclusive scan, the dense scores.
+struct SysCompactArgs {
+    const uint64_t* res;
+    const uint32_t* list;             // row-order form: res is indexed through list[pos]; null: by position
+    uint32_t n_tg;
+    uint32_t n_entries;               // n_list * n_tg
+    uint32_t n_tiles;
+    uint8_t* status2;                 // [(n_entries + 3) / 4]
+    uint32_t* tile_off;               // [n_tiles] placed per tile, then their exclusive scan
+    double* score;                    // [placed] dense, increasing e
+    uint32_t* counts;                 // [kPlacedSlots][3 * n_tg], zero again after k_sysg_scan
+    uint32_t* hdr;                   // mapped host words: [0] placed, [1 + 3 * k + code] the summed counts
+};
+
 }  // namespace pe

@@ -4041,6 +4041,176 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
     }
 }
 
+// SystemScheduler.computePlacements' loop (scheduler_system.go:283-425) over
+// every (node, task group) pair of a job with several groups: the nodes are
+// independent, the groups of one node are not (an earlier group's ask shrinks
+// what a later one finds). One lane per list position (or per snapshot row in
+// the row-order form, as k_system_rows) loads the node once, keeps its record
+// in registers and walks the listed groups in order with the pipeline every
+// other path runs; an option adds the group's ask to the registers as
+// k_system's commit does. The groups' tables are one HBM array: every lane of
+// a wave reads the same element. coll_job is written through (status_loaded
+// reads the column); the record is stored once, only if something was placed.
+// Outcomes go to res (sys_box); the per-group outcome counts are one ballot
+// per code and wave, summed in LDS, one atomic per workgroup and counter.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_system_groups(SystemGroupsArgs A) {
+    __shared__ uint32_t cnt[3 * kSysGroupsChunk];
+    if (threadIdx.x < 3 * kSysGroupsChunk) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t span = A.rank_of ? A.n_rows : A.n_list;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < span; i += stride) {
+        uint32_t row = i;
+        if (A.rank_of) {
+            if (A.rank_of[i] == PE_NONE) continue;
+        } else {
+            row = A.list[i];
+        }
+        NodeIn in;
+        in.r = A.soa.rec[row];
+        uint32_t cj = A.soa.coll_job[row];
+        const uint32_t df0 = A.dev_free ? A.dev_free[row] : 0u;
+        uint32_t df = df0;
+        bool dirty = false;
+        uint64_t* out = A.res + (size_t)i * A.n_tg + A.k0;
+        for (uint32_t kk = 0; kk < A.nk; kk++) {
+            const SysGroup& G = A.groups[A.k0 + kk];
+            in.coll_tg = G.tg.coll_tg[row];
+            in.feas = G.tg.node_feas ? G.tg.node_feas[row] : 1u;
+            in.dev_free = df;
+            ScoreIn si;
+            const int st = status_loaded<false>(A.soa, G.tg, G.tg.class_ok, G.ask, 0u, row, in, &si);
+            double score = 0.0;
+            if (st == kOption) {
+                lookup_scores(G.tg, nullptr, nullptr, row, in.r.cls, &si);
+                uint32_t ns;
+                score = score_into<false>(G.ask, A.log10, si, nullptr, &ns);
+                // Plan.AppendAlloc: the later groups of this node see it
+                in.r.used_cpu += G.ask.cpu;
+                in.r.used_mem += G.ask.mem;
+                in.r.used_disk += G.ask.disk;
+                in.r.used_mbits += G.ask.commit_mbits;
+                in.r.used_dyn += G.ask.commit_dyn;
+                cj += 1u;
+                A.soa.coll_job[row] = cj;
+                G.tg.coll_tg[row] = in.coll_tg + 1u;
+                if (G.ask.n_dev > 0) df = dev_after(G.ask, G.tg.dev_cls[in.r.cls], df, 1);
+                dirty = true;
+            }
+            out[kk] = sys_box(st, score);
+            const uint64_t m0 = __ballot(st == kOption), m1 = __ballot(st == kFiltered), m2 = __ballot(st == kExhausted);
+            if (lane == (uint32_t)__ffsll((unsigned long long)(m0 | m1 | m2)) - 1u) {
+                if (m0) atomicAdd(&cnt[3 * kk + 0], (uint32_t)__popcll(m0));
+                if (m1) atomicAdd(&cnt[3 * kk + 1], (uint32_t)__popcll(m1));
+                if (m2) atomicAdd(&cnt[3 * kk + 2], (uint32_t)__popcll(m2));
+            }
+        }
+        if (!dirty) continue;
+        NodeRec& r = A.soa.rec[row];
+        r.used_cpu = in.r.used_cpu;
+        r.used_mem = in.r.used_mem;
+        r.used_disk = in.r.used_disk;
+        r.used_mbits = in.r.used_mbits;
+        r.used_dyn = in.r.used_dyn;
+        if (df != df0) A.dev_free[row] = df;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * A.nk && cnt[threadIdx.x])
+        atomicAdd(&A.counts[(size_t)(blockIdx.x % kPlacedSlots) * 3u * A.n_tg + 3u * A.k0 + threadIdx.x], cnt[threadIdx.x]);
+}
+
+// The outcome of entry e (position-major, group-minor) from res: 0 placed,
+// 1 filtered, 2 exhausted; *v its boxed word.
+__device__ __forceinline__ uint32_t sysg_entry(const SysCompactArgs& A, uint32_t e, uint64_t* v) {
+    size_t at = e;
+    if (A.list) {
+        const uint32_t pos = e / A.n_tg;
+        at = (size_t)A.list[pos] * A.n_tg + (e - pos * A.n_tg);
+    }
+    const uint64_t x = A.res[at];
+    *v = x;
+    return (x & 0xFFFFFFFFFFFFFFF0ull) == 0x7FF8000000000000ull ? (uint32_t)(x & 3u) : (uint32_t)kOption;
+}
+
+// Compaction, step one: each lane packs its four entries into one outcome byte
+// (coalesced byte stores); the tile's placed count goes to tile_off[tile].
+__global__ void __launch_bounds__(256) k_sysg_pack(SysCompactArgs A) {
+    __shared__ uint32_t red[4];
+    const uint32_t e0 = blockIdx.x * kSysTile + threadIdx.x * 4u;
+    uint32_t byte = 0, placed = 0;
+    for (uint32_t j = 0; j < 4; j++) {
+        if (e0 + j >= A.n_entries) break;
+        uint64_t v;
+        const uint32_t code = sysg_entry(A, e0 + j, &v);
+        byte |= code << (2u * j);
+        placed += code == (uint32_t)kOption;
+    }
+    if (e0 < A.n_entries) A.status2[e0 >> 2] = (uint8_t)byte;
+    for (int off = 32; off > 0; off >>= 1) placed += __shfl_xor(placed, off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = placed;
+    __syncthreads();
+    if (threadIdx.x == 0) A.tile_off[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+// Step two, one workgroup: the exclusive scan of the tile counts in place, the
+// total and the summed per-group counters into the mapped header words.
+__global__ void __launch_bounds__(256) k_sysg_scan(SysCompactArgs A) {
+    __shared__ uint32_t sh[256];
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < A.n_tiles; base += 256) {
+        const uint32_t t = base + threadIdx.x;
+        const uint32_t own = t < A.n_tiles ? A.tile_off[t] : 0u;
+        sh[threadIdx.x] = own;
+        __syncthreads();
+        for (uint32_t d = 1; d < 256; d <<= 1) {
+            const uint32_t add = threadIdx.x >= d ? sh[threadIdx.x - d] : 0u;
+            __syncthreads();
+            sh[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (t < A.n_tiles) A.tile_off[t] = carry + sh[threadIdx.x] - own;
+        carry += sh[255];
+        __syncthreads();
+    }
+    // one wave per counter, one lane per slot; the slots are left zero for the next call
+    static_assert(kPlacedSlots == 64, "one lane per counter slot");
+    for (uint32_t c = threadIdx.x >> 6; c < 3u * A.n_tg; c += 4) {
+        uint32_t* slot = &A.counts[(size_t)(threadIdx.x & 63u) * 3u * A.n_tg + c];
+        uint32_t sum = *slot;
+        *slot = 0;
+        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+        if ((threadIdx.x & 63u) == 0) A.hdr[1 + c] = sum;
+    }
+    if (threadIdx.x == 0) A.hdr[0] = carry;
+    __threadfence_system();
+}
+
+// Step three: the placed entries' scores to their dense positions, the tile's
+// offset plus a ballot / popcount prefix over the lanes below.
+__global__ void __launch_bounds__(256) k_sysg_scatter(SysCompactArgs A) {
+    __shared__ uint32_t wave_n[4];
+    const uint32_t e0 = blockIdx.x * kSysTile + threadIdx.x * 4u;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t v[4];
+    bool hit[4];
+    uint32_t below = 0, total = 0;
+    for (uint32_t j = 0; j < 4; j++) {
+        hit[j] = false;
+        v[j] = 0;
+        if (e0 + j < A.n_entries) hit[j] = sysg_entry(A, e0 + j, &v[j]) == (uint32_t)kOption;
+        const uint64_t m = __ballot(hit[j]);
+        below += (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        total += (uint32_t)__popcll(m);
+    }
+    if (lane == 0) wave_n[wave] = total;
+    __syncthreads();
+    uint32_t at = A.tile_off[blockIdx.x] + below;
+    for (uint32_t w = 0; w < wave; w++) at += wave_n[w];
+    for (uint32_t j = 0; j < 4; j++)
+        if (hit[j]) A.score[at++] = __longlong_as_double((long long)v[j]);
+}
+
 }  // namespace pe
 
 // ---- launch wrappers (host) ------------------------------------------------
@@ -4190,6 +4360,31 @@ hipError_t pe_launch_inplace(const pe::InplaceArgs* a, hipStream_t st) {
     uint32_t blocks = (a->n_groups + 255) / 256;
     if (blocks > 2048) blocks = 2048;   // grid-stride beyond
     hipLaunchKernelGGL(pe::k_inplace, dim3(blocks), dim3(256), 0, st, *a);
+    return hipGetLastError();
+}
+
+// One launch per chunk of kSysGroupsChunk listed groups, in list order on the
+// stream (a later chunk's lanes read what the earlier chunk's stored).
+hipError_t pe_launch_system_groups(const pe::SystemGroupsArgs* a, hipStream_t st) {
+    const uint32_t span = a->rank_of ? a->n_rows : a->n_list;
+    if (!span || !a->n_tg) return hipSuccess;
+    uint32_t blocks = (span + 255) / 256;
+    if (blocks > 8192) blocks = 8192;   // grid-stride beyond
+    pe::SystemGroupsArgs c = *a;
+    for (uint32_t k0 = 0; k0 < a->n_tg; k0 += pe::kSysGroupsChunk) {
+        c.k0 = k0;
+        c.nk = a->n_tg - k0 < pe::kSysGroupsChunk ? a->n_tg - k0 : pe::kSysGroupsChunk;
+        hipLaunchKernelGGL(pe::k_system_groups, dim3(blocks), dim3(256), 0, st, c);
+    }
+    return hipGetLastError();
+}
+
+// Pack, scan, scatter: ordered across workgroups by the kernel boundaries only.
+hipError_t pe_launch_system_compact(const pe::SysCompactArgs* a, hipStream_t st) {
+    if (!a->n_entries || a->n_tiles != (a->n_entries + pe::kSysTile - 1) / pe::kSysTile) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pe::k_sysg_pack, dim3(a->n_tiles), dim3(256), 0, st, *a);
+    hipLaunchKernelGGL(pe::k_sysg_scan, dim3(1), dim3(256), 0, st, *a);
+    hipLaunchKernelGGL(pe::k_sysg_scatter, dim3(a->n_tiles), dim3(256), 0, st, *a);
     return hipGetLastError();
 }
 

@@ -72,6 +72,13 @@ def load_engine():
         lib.pe_inplace_update.restype = C.c_int
         lib.pe_inplace_update.argtypes = [C.c_void_p, C.c_uint32, abi.u32p, C.c_uint32,
                                           C.POINTER(abi.pe_ranked_node), abi.u8p, abi.u32p]
+        if hasattr(lib, "pe_system_place_groups"):   # present or absent behind one ABI version
+            lib.pe_system_place_groups.restype = C.c_int
+            lib.pe_system_place_groups.argtypes = [C.c_void_p, abi.u32p, C.c_uint32, abi.f64p, abi.u8p, abi.u32p,
+                                                   abi.u32p]
+            lib.pe_system_groups_results.restype = C.c_int
+            lib.pe_system_groups_results.argtypes = [C.c_void_p, C.POINTER(abi.f64p), C.POINTER(abi.u8p),
+                                                     C.POINTER(abi.u32p), abi.u32p, abi.u32p, abi.u32p]
         lib.pe_speculation_stats.restype = C.c_int
         lib.pe_speculation_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.pe_comm_unique_id.restype = C.c_int
@@ -568,6 +575,103 @@ class _Stack:
         self._check(self._fn("system_place")(self._h, self._tg_index(tg), score.ctypes.data_as(abi.f64p),
                                              status.ctypes.data_as(abi.u8p), C.byref(placed)))
         return score[:n], status[:n], placed.value
+
+    def SystemPlaceGroups(self, tgs, fallback: bool = True, staged: bool = False):
+        """SystemScheduler.computePlacements for several task groups of a
+        system job in one pass (pe_system_place_groups): every position of the
+        SetNodes list in order and, within it, every group of `tgs` in list
+        order. Returns (score[n, G], status[n, G], counts[G, 3], placed):
+        FinalScore or NaN where nothing was placed, pe_system_place's codes,
+        the entries of each group per code. The arrays are copies (nothing
+        points into the engine's staging). `staged`: the call leaves the
+        results in the staging (null arrays) and they are copied from
+        pe_system_groups_results. A job the pass refuses (Unsupported), or a
+        library without the entry point, is answered by
+        system_place_groups_by_select when `fallback`."""
+        idx = [self._tg_index(t) for t in tgs]
+        n, G = len(self._visit), len(idx)
+        try:
+            if not hasattr(self._lib, self._p + "system_place_groups"):
+                raise Unsupported(abi.PE_EUNSUPPORTED, "no multi-group system placement behind this ABI")
+            fn = getattr(self._lib, self._p + "system_place_groups")
+            t = np.ascontiguousarray(np.asarray(idx or [0], dtype=np.uint32))
+            placed = C.c_uint32(0)
+            E = n * G
+            if staged:
+                self._check(fn(self._h, t.ctypes.data_as(abi.u32p), G, None, None, None, C.byref(placed)))
+                sc, st, cn = abi.f64p(), abi.u8p(), abi.u32p()
+                rn, rg, rp = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+                self._check(self._lib.pe_system_groups_results(self._h, C.byref(sc), C.byref(st), C.byref(cn),
+                                                               C.byref(rn), C.byref(rg), C.byref(rp)))
+                assert (rn.value, rg.value, rp.value) == (n, G, placed.value)
+                p = placed.value
+                dense = np.ctypeslib.as_array(sc, shape=(p,)).copy() if p else np.empty(0)
+                packed = np.ctypeslib.as_array(st, shape=((E + 3) // 4,)).copy() if E else np.empty(0, np.uint8)
+                counts = np.ctypeslib.as_array(cn, shape=(3 * G,)).copy()
+            else:
+                dense = np.empty(max(1, E), dtype=np.float64)
+                packed = np.zeros(max(1, (E + 3) // 4), dtype=np.uint8)
+                counts = np.zeros(3 * max(1, G), dtype=np.uint32)
+                self._check(fn(self._h, t.ctypes.data_as(abi.u32p), G, dense.ctypes.data_as(abi.f64p),
+                               packed.ctypes.data_as(abi.u8p), counts.ctypes.data_as(abi.u32p), C.byref(placed)))
+                counts = counts[:3 * G]
+        except Unsupported:
+            if not fallback:
+                raise
+            return system_place_groups_by_select(self, idx)
+        p = placed.value
+        status = unpack_status2(packed, E)
+        score = np.full(E, np.nan)
+        score[status == 0] = dense[:p]
+        return score.reshape(n, G), status.reshape(n, G), counts.reshape(G, 3).astype(np.uint32), p
+
+
+def pack_status2(status) -> np.ndarray:
+    """Outcome codes (0 placed, 1 filtered, 2 exhausted) packed as
+    pe_system_place_groups returns them: 2 bits per entry, entry e in byte
+    e >> 2 at bits 2 * (e & 3), unused bits of the last byte 0."""
+    st = np.asarray(status, dtype=np.uint8).ravel()
+    pad = np.zeros(4 * ((len(st) + 3) // 4), dtype=np.uint8)
+    pad[:len(st)] = st & 3
+    q = pad.reshape(-1, 4)
+    return (q[:, 0] | (q[:, 1] << 2) | (q[:, 2] << 4) | (q[:, 3] << 6)).astype(np.uint8)
+
+
+def unpack_status2(packed, n: int) -> np.ndarray:
+    """The first `n` outcome codes of a pack_status2 array."""
+    b = np.asarray(packed, dtype=np.uint8).ravel()[:(n + 3) // 4]
+    out = np.empty((len(b), 4), dtype=np.uint8)
+    for j in range(4):
+        out[:, j] = (b >> (2 * j)) & 3
+    return out.ravel()[:n].copy()
+
+
+def system_place_groups_by_select(stack, tgs):
+    """SystemScheduler.computePlacements' loop (scheduler_system.go:283-425)
+    for several task groups as the per-call sequence, on any stack with
+    SetNodes / SelectRaw / Commit (the engine's and the oracle's): for each
+    position of the SetNodes list, for each group of `tgs` in list order,
+    SetNodes([row]), Select(tg) and Commit on an option. SelectRaw keeps a nil
+    Select's counters, which tell filtered from exhausted. Returns
+    SystemPlaceGroups' shape; the node list is put back at the end."""
+    rows = np.array(stack._visit, dtype=np.uint32, copy=True)
+    n, G = len(rows), len(tgs)
+    score = np.full((n, G), np.nan)
+    status = np.zeros((n, G), dtype=np.uint8)
+    counts = np.zeros((G, 3), dtype=np.uint32)
+    for pos in range(n):
+        one = rows[pos:pos + 1]
+        for k, tg in enumerate(tgs):
+            stack.SetNodes(one)
+            r = stack.SelectRaw(tg)
+            if r.row >= 0:
+                stack.Commit(tg, r.row, r.preempted)   # with the evictions of a preempting stack
+                score[pos, k] = r.final_score
+            else:
+                status[pos, k] = 1 if r.nodes_filtered else 2
+            counts[k, status[pos, k]] += 1
+    stack.SetNodes(rows)
+    return score, status, counts, int(counts[:, 0].sum())
 
 
 def inplace_update_by_select(stack, tg, allocs: Sequence[int]):
