@@ -535,6 +535,46 @@ int pe_system_place_groups(pe_stack* s, const uint32_t* tg_indices, uint32_t n_t
  * above; score holds *placed values). */
 int pe_system_groups_results(const pe_stack* s, const double** score, const uint8_t** status2,
                              const uint32_t** counts, uint32_t* n, uint32_t* n_tg, uint32_t* placed);
+/* pe_system_place_groups on a stack with preemption enabled
+ * (PreemptionConfig.SystemSchedulerEnabled, the reference's default): the same
+ * walk, every position of the SetNodes list in order and every listed group
+ * in list order within it, each pair one single-node Select on the system
+ * stack. A plain BinPack that fails its fit goes into BinPack with evict
+ * (stack.go:267-278, rank.go:193-527, preemption.go); an option is followed
+ * by Plan.AppendAlloc and by Plan.AppendPreemptedAlloc of each preempted
+ * alloc. out_status2, out_score, counts and *placed have
+ * pe_system_place_groups' layout and carry the final outcome: a pair placed by
+ * eviction counts as placed and its score is the eviction Select's FinalScore.
+ * NULL arrays leave the results in staging (pe_system_groups_results serves
+ * both calls). Every result and every later observable state (node records,
+ * collision counts, device free counts, ports and bandwidth, the plan and its
+ * preemptions, the EvalEligibility memo and its log) equals that of the
+ * node-major per-Select loop and that of pe_system_place(tg_indices[0]), ...,
+ * pe_system_place(tg_indices[n_tg-1]) on the same handle. With preemption off
+ * on the stack the call is pe_system_place_groups and preempts nothing.
+ *
+ * PE_EINVAL / PE_ESTATE as pe_system_place_groups. PE_EUNSUPPORTED (checked
+ * before anything changes): everything pe_system_place_groups refuses except
+ * preemption itself, and: a non-terminal alloc in the snapshot with
+ * max_parallel > 0 whose job priority is at least 10 below the placing job's
+ * (its penalty reads the plan's preemption counts, which other nodes grow); a
+ * snapshot outside the on-device eviction limits; a device ask in a listed
+ * group while a non-terminal alloc holds two device entries of one device
+ * group; several task networks in a listed group; a listed node whose alloc
+ * count, or that count plus the plan's placements on it plus n_tg, is beyond
+ * the widest eviction width (1024 allocs, 2048 proposed allocs). */
+int pe_system_place_groups_preempt(pe_stack* s, const uint32_t* tg_indices, uint32_t n_tg,
+                                   double* out_score, uint8_t* out_status2,
+                                   uint32_t* counts, uint32_t* placed);
+/* The preempted allocs of the last pe_system_place_groups_preempt, a CSR in the
+ * engine's page-locked staging, valid until the next pe_system_place* call on
+ * the handle: entries[n_entries] holds the entry indices e = pos * n_tg + k
+ * that preempted something, increasing; allocs[off[i] .. off[i + 1]) their
+ * alloc-table rows in the order pe_select's record lists them (increasing slot
+ * of the node's alloc list). No PE_MAX_PREEMPT cap. PE_ESTATE: no such call
+ * yet, or a pe_system_place* call since. */
+int pe_system_groups_preempted(const pe_stack* s, const uint32_t** entries, const uint32_t** off,
+                               const uint32_t** allocs, uint32_t* n_entries);
 /* Full-scan Select sharded over GPUs (one process per GPU, each holding the
  * same snapshot, job, SetNodes list and plan). Each rank sweeps
  * the snapshot rows [row_begin, row_end) it owns into a pe_shard_rec: the
@@ -559,7 +599,12 @@ uint32_t pe_last_sweep_bytes(const pe_stack* s);
  * default, or PE_KERNEL_SPLIT=1 in the environment at pe_stack_create): with it
  * on, the chain path records HIP events between its kernels and
  * pe_last_kernel_split writes the last launch's ms4 = {k_base, k_chain, k_emit,
- * k_emit_writeback}; PE_ESTATE when the last pe_place / Select ran no chain. */
+ * k_emit_writeback}; PE_ESTATE when the last pe_place / Select ran no chain.
+ * pe_system_place_groups_preempt on a preempting stack records them too:
+ * ms4 = {stopping pass, eviction walk at the first width, compaction, the
+ * time on the stream from there to the end of the last relaunch at a wider
+ * width (host waits between the rounds included); exactly 0 when no node
+ * needed a wider width}. pe_last_kernel_ms covers the first round only. */
 int pe_set_kernel_split(pe_stack* s, int on);
 int pe_last_kernel_split(const pe_stack* s, double* ms4);
 /* AllocMetric maps (structs.go:9826-10026) of Selects: ClassFiltered,

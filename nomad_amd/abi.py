@@ -232,6 +232,7 @@ ENGINE_SYMBOLS = [
     "pe_last_kernel_split", "pe_preempted_of", "pe_spec_view_get", "pe_system_view_get", "pe_comm_library", "pe_last_exchange_stats",
     "pe_last_metrics_bin", "pe_metric_string", "pe_scorer_name", "pe_system_results", "pe_inplace_update",
     "pe_system_place_groups", "pe_system_groups_results",
+    "pe_system_place_groups_preempt", "pe_system_groups_preempted",
 ]
 
 

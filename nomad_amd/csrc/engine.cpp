@@ -534,6 +534,7 @@ struct pe_stack {
     // per-kernel events of the windowed chain (tun.kernel_split): before k_base,
     // after k_base, k_chain, k_emit, k_emit_writeback of the last launch
     bool split_valid = false;
+    uint32_t split_rounds = 0;   // pe_system_place_groups_preempt: walk launches of the timed call (0: the chain's events)
     hipEvent_t ev_split[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double last_ms = 0;
     bool last_ms_pending = false;      // last_ms still to be read from ev0 / ev1
@@ -604,6 +605,17 @@ struct pe_stack {
     // eviction width of the snapshot (PreemptArgs::mask_words, evict.inc): 1
     // while every node holds <= 32 non-terminal allocs, else 8 (<= 256)
     uint32_t evict_words = 1;
+    // the lowest job priority among the snapshot's non-terminal allocs with
+    // max_parallel > 0 (INT32_MAX: none): an eviction candidate whose penalty
+    // reads the plan's preemption counts exists only at or above it + 10
+    int32_t mp_min_priority = INT32_MAX;
+    // a non-terminal alloc holds two device entries of one device group (two
+    // tasks on one group): PreemptForDevice would list it twice, which the
+    // device path does not model (preempt_for_device flags it)
+    bool dup_dev_group = false;
+    // nodes whose alloc list is beyond the widths below the widest (32 and 256
+    // allocs): where the multi-group eviction walk starts
+    uint32_t n_beyond_w1 = 0, n_beyond_w8 = 0;
     // PreemptedAllocs past the PE_MAX_PREEMPT a record carries inline, of the
     // last record-producing call: (record index, the full list)
     std::vector<std::pair<uint32_t, std::vector<uint32_t>>> pre_overflow;
@@ -707,6 +719,8 @@ struct pe_stack {
         // 2-bit outcomes (entry pos * names.size() + k); entries in tg-major order
         std::vector<uint32_t> names;
         const uint8_t* status2 = nullptr;
+        // pe_system_place_groups_preempt: the entries placed by eviction, increasing
+        std::vector<uint32_t> evicting;
     } plan_defer;
 
     // SpreadIterator bookkeeping (spread.go:99-102, 254)
@@ -909,6 +923,15 @@ struct pe_stack {
     uint32_t sysg_n = 0, sysg_ntg = 0, sysg_placed = 0;
     bool sysg_valid = false;
     const void* sysg_counts_zeroed = nullptr;   // the counter block k_sysg_scan last left zero (null: unknown)
+    // pe_system_place_groups_preempt: the resume groups and the two lane
+    // lists of the eviction walk, its control words ([0] / [1] the lists'
+    // counts, [2] appended records, [3] flags), the append buffer; their
+    // staging, and the preempted lists as a CSR [entries | off | allocs]
+    DevMem d_sysg_resume, d_sysg_lanes, d_sysg_ctl, d_sysg_app;
+    PinnedMem h_sysg_ctl, h_sysg_app, h_sysg_csr;
+    uint32_t sysg_pre_entries = 0;
+    size_t sysg_pre_allocs = 0;
+    bool sysg_pre_valid = false;
     bool stopped(uint32_t ai) const { return ai < stop_count.size() && stop_count[ai] > 0; }
 
     // multi-GPU handle (pe_comm_init): an RCCL communicator over the ranks'
@@ -989,12 +1012,21 @@ static void plan_settle(pe_stack* s) {
     const uint32_t n = std::min<uint32_t>(d.n, (uint32_t)s->visit.size());
     if (!d.names.empty()) {   // as the per-group calls append them: group after group, list order within
         const size_t G = d.names.size();
-        for (size_t k = 0; k < G; k++)
+        // (pe_system_place appends a group's evicting placements behind its plain ones)
+        std::vector<std::vector<uint32_t>> late(G);   // per group: the evicting positions, increasing
+        for (uint32_t e : d.evicting) late[e % G].push_back((uint32_t)(e / G));
+        for (size_t k = 0; k < G; k++) {
+            size_t next = 0;
             for (uint32_t i = 0; i < n; i++) {
                 const size_t e = (size_t)i * G + k;
+                if (next < late[k].size() && late[k][next] == i) { next++; continue; }
                 if (((d.status2[e >> 2] >> (2 * (e & 3))) & 3u) == 0) s->plan.emplace_back(d.names[k], s->visit[i]);
             }
+            for (uint32_t i : late[k])
+                if (i < n) s->plan.emplace_back(d.names[k], s->visit[i]);
+        }
         d.names.clear();
+        d.evicting.clear();
         return;
     }
     size_t p = 0;
@@ -2137,12 +2169,23 @@ int build_alloc_state(pe_stack* s) {
     {
         std::vector<uint32_t> fill(s->h_node_alloc_off.begin(), s->h_node_alloc_off.end() - 1);
         uint32_t max_m = 0;
-        for (uint32_t i = 0; i < n; i++) max_m = std::max(max_m, cnt[i + 1]);
+        s->n_beyond_w1 = s->n_beyond_w8 = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            max_m = std::max(max_m, cnt[i + 1]);
+            s->n_beyond_w1 += cnt[i + 1] > 32u;
+            s->n_beyond_w8 += cnt[i + 1] > 256u;
+        }
         s->evict_words = max_m <= 32u ? 1u : max_m <= 256u ? 8u : 32u;
         s->evict_too_many = max_m > pe::kEvictMaxAllocs;
+        s->mp_min_priority = INT32_MAX;
+        s->dup_dev_group = false;
         for (uint32_t i = 0; i < s->allocs.size(); i++) {
             const HostAlloc& a = s->allocs[i];
             if (a.terminal) continue;
+            if (a.max_parallel > 0) s->mp_min_priority = std::min(s->mp_min_priority, a.priority);
+            for (uint32_t k = a.dev_begin; k < a.dev_end && !s->dup_dev_group; k++)
+                for (uint32_t j = a.dev_begin; j < k; j++)
+                    if (s->alloc_dev[j].first == s->alloc_dev[k].first) { s->dup_dev_group = true; break; }
             const uint32_t slot = fill[a.row]++;
             s->h_palloc_index[slot] = i;
             s->alloc_slot[i] = slot;
@@ -4701,6 +4744,7 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
                 }
                 HIP_TRY(s, le);
                 s->split_valid = split != nullptr;
+                s->split_rounds = 0;
             } else {
                 s->split_valid = false;
                 HIP_TRY_STATE(s, pe_launch_place(&A, 1, full, s->stream));
@@ -4973,6 +5017,7 @@ int pe_last_kernel_split(const pe_stack* s, double* ms4) {
             return m->fail(PE_EHIP, "kernel split events");
         ms4[k] = ms;
     }
+    if (s->split_rounds == 1) ms4[3] = 0;   // no wider round: the two events were recorded back to back
     return PE_OK;
 }
 
@@ -5240,6 +5285,7 @@ static int reset_plan_one(pe_stack* s, bool may_defer) {
     if (!s) return PE_EINVAL;
     s->plan_defer.active = false;   // the plan is emptied below
     s->plan_defer.names.clear();
+    s->plan_defer.evicting.clear();
     ApiScope prof_(s, "reset_plan");
     if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
     spec_drop(s);
@@ -8844,6 +8890,7 @@ static int system_place_impl(pe_stack* s, uint32_t tgi, double* out_score, uint8
         if (frc) return frc;
     }
     if (s->cfg.stack_kind != PE_STACK_SYSTEM) return s->fail(PE_ESTATE, "pe_system_place needs a system stack");
+    s->sysg_pre_valid = false;   // (pe_system_groups_preempted: until the next pe_system_place* call)
     s->gen++;
     HIP_TRY(s, hipSetDevice(s->device));
     // every node appears once (checked by SetNodes): the single-node Selects are independent
@@ -8951,6 +8998,7 @@ static int system_place_impl(pe_stack* s, uint32_t tgi, double* out_score, uint8
         // the caller reads them there, else from its copy
         s->plan_defer.active = true;
         s->plan_defer.names.clear();
+        s->plan_defer.evicting.clear();
         s->plan_defer.name = g.name;
         s->plan_defer.n = n;
         s->plan_defer.status = s->h_sys_out.as<uint8_t>() + st_off;
@@ -9733,13 +9781,22 @@ int pe_system_place(pe_stack* s, uint32_t tgi, double* out_score, uint8_t* out_s
 // listed group in turn. Everything that can refuse the call is checked before
 // anything changes; then system_place_impl's order of work with one upload,
 // the kernels and one wait, and the host mirrors group after group.
+//
+// `pre_call`: pe_system_place_groups_preempt. On a preempting
+// stack the pass stops a node at its first exhausted group
+// (k_system_groups_stop) and the eviction walk (k_system_groups_evict) takes
+// the stopped nodes from there, BinPack with evict where the plain fit is
+// exhausted; the preempted allocs of every evicting entry are kept as a CSR
+// (pe_system_groups_preempted). Results and state equal those of
+// pe_system_place of each listed group in turn on the preempting stack.
 static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n_tg, double* out_score,
-                                    uint8_t* out_status2, uint32_t* counts, uint32_t* placed) {
+                                    uint8_t* out_status2, uint32_t* counts, uint32_t* placed, bool pre_call) {
+    const std::string fn = pre_call ? "pe_system_place_groups_preempt" : "pe_system_place_groups";
     if (placed) *placed = 0;
-    if (n_tg == 0 || !tgs) return s->fail(PE_EINVAL, "pe_system_place_groups: no task group listed");
+    if (n_tg == 0 || !tgs) return s->fail(PE_EINVAL, fn + ": no task group listed");
     if ((!out_score) != (!out_status2) || (!out_score) != (!counts))
-        return s->fail(PE_EINVAL, "pe_system_place_groups: the output arrays are all null or all set");
-    if (s->cfg.stack_kind != PE_STACK_SYSTEM) return s->fail(PE_ESTATE, "pe_system_place_groups needs a system stack");
+        return s->fail(PE_EINVAL, fn + ": the output arrays are all null or all set");
+    if (s->cfg.stack_kind != PE_STACK_SYSTEM) return s->fail(PE_ESTATE, fn + " needs a system stack");
     if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
     if (!s->have_job) return s->fail(PE_ESTATE, "pe_set_job not called");
     {
@@ -9754,7 +9811,7 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
     const char* why = nullptr;
     uint32_t n_dev_groups = 0;
     if (!s->visit_unique) why = "duplicate rows in the system placement list";
-    else if (s->cfg.preempt) why = "preemption is enabled (BinPack evicts)";
+    else if (s->cfg.preempt && !pre_call) why = "preemption is enabled (BinPack evicts)";
     else if (s->metrics_on) why = "AllocMetric maps are on (pe_set_metrics)";
     else if (!s->kids.empty()) why = "a handle over several devices";
     for (auto& c : s->job_constraints)
@@ -9767,12 +9824,50 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
         else if (tg_md(s, g)) why = "a task network on multi-device nodes";
         else if (!g.dev_reqs.empty() && ++n_dev_groups > 1) why = "device asks in more than one listed group";
     }
-    if (why) return s->fail(PE_EUNSUPPORTED, std::string("pe_system_place_groups: ") + why);
+    if (why) return s->fail(PE_EUNSUPPORTED, fn + ": " + why);
     for (uint32_t k = 0; k < n_tg; k++)
         if (!s->tgs[tgs[k]]->unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->tgs[tgs[k]]->unsupported);
     if (!s->cores_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->cores_unsupported);
+    const bool evicting = pre_call && s->cfg.preempt;
+    plan_settle(s);   // (the deferred entries written out: nothing a caller can observe)
+    if (evicting) {
+        // a candidate whose max_parallel penalty reads the plan's preemption
+        // counts (preemption.go:220-240): other nodes grow them, the nodes are
+        // then ordered and node-major differs from group-major
+        if (s->mp_min_priority != INT32_MAX && (int64_t)s->job_priority - (int64_t)s->mp_min_priority >= 10)
+            return s->fail(PE_EUNSUPPORTED, fn + ": an eviction candidate with max_parallel > 0");
+        if (!s->preempt_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, "preemption: " + s->preempt_unsupported);
+        // what evict_eval would flag kEvictUnsup for in the middle of the walk:
+        // PreemptForDevice over an alloc with two entries of one device group,
+        // and a group with several task networks (AssignNetwork per task)
+        for (uint32_t k = 0; k < n_tg; k++) {
+            const TgPlan& g = *s->tgs[tgs[k]];
+            if (s->dup_dev_group && !g.dev_reqs.empty())
+                return s->fail(PE_EUNSUPPORTED, fn + ": a device ask with an alloc holding one device group twice");
+            if (g.ask.has_task_net > 1)
+                return s->fail(PE_EUNSUPPORTED, fn + ": several task networks in a listed group");
+        }
+        // every listed node within the widest eviction width: its allocs (a
+        // snapshot with a node beyond 1024 allocs sets preempt_unsupported and
+        // was refused above, listed or not), and its ProposedAllocs with the
+        // plan's placements and this call's. The snapshot's largest node
+        // bounds the first term; the plan per row is counted only when it
+        // could matter
+        const uint32_t max_m = 32u * s->evict_words;
+        bool beyond = false;
+        const uint64_t max_l = 64ull * pe::kEvictMaxWords;
+        if (!beyond && (uint64_t)max_m + s->plan.size() + n_tg > max_l) {
+            std::unordered_map<uint32_t, uint32_t> on_row;
+            for (auto& e : s->plan) on_row[e.second]++;
+            for (uint32_t r : s->visit) {
+                const auto it = on_row.find(r);
+                const uint64_t m = s->h_node_alloc_off[r + 1] - s->h_node_alloc_off[r];
+                beyond = beyond || m + (it == on_row.end() ? 0u : it->second) + n_tg > max_l;
+            }
+        }
+        if (beyond) return s->fail(PE_EUNSUPPORTED, fn + ": a node beyond the widest eviction width");
+    }
 
-    plan_settle(s);
     {
         const int frc = spec_flush(s);
         if (frc) return frc;
@@ -9783,26 +9878,40 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
         if (rc) return rc;
         const TgPlan& g = *s->tgs[tgs[k]];
         if (g.psets.size() > (size_t)g.n_spread || g.md_on)
-            return s->fail(PE_EUNSUPPORTED, "pe_system_place_groups: property sets or multi-device nodes");
+            return s->fail(PE_EUNSUPPORTED, fn + ": property sets or multi-device nodes");
     }
     const uint32_t n = (uint32_t)s->visit.size();
     const size_t E = (size_t)n * n_tg;
-    if (E >= (size_t(1) << 31)) return s->fail(PE_EUNSUPPORTED, "pe_system_place_groups: more than 2^31 entries");
+    if (E >= (size_t(1) << 31)) return s->fail(PE_EUNSUPPORTED, fn + ": more than 2^31 entries");
     s->sysg_valid = false;
+    s->sysg_pre_valid = false;
     s->sysg_counts.assign(3 * (size_t)n_tg, 0);
     const size_t sb = ((E + 3) / 4 + 7) & ~(size_t)7;   // outcome bytes, the scores 8-byte aligned behind them
     uint32_t p = 0;
     bool any_dev = false;
+    // the evicting entries with their preempted sets: (entry, width, mask words)
+    struct Evicted { uint32_t e, words; size_t at; };
+    std::vector<Evicted> evicted;
+    std::vector<uint32_t> ev_masks;
     if (n) {
-        std::vector<pe::SysGroup> groups(n_tg);
+        // one upload: the groups' tables and, on a preempting stack, evict_eval's view of each behind them
+        const size_t pre_off = (sizeof(pe::SysGroup) * n_tg + 15) & ~(size_t)15;
+        std::vector<uint8_t> blob(evicting ? pre_off + sizeof(pe::PreemptArgs) * n_tg : sizeof(pe::SysGroup) * n_tg);
         for (uint32_t k = 0; k < n_tg; k++) {
             TgPlan& g = *s->tgs[tgs[k]];
-            groups[k].tg = tables_of(g);
-            groups[k].ask = ask_for(s, g);
-            any_dev = any_dev || groups[k].ask.n_dev > 0;
+            pe::SysGroup sg;
+            std::memset(&sg, 0, sizeof(sg));
+            sg.tg = tables_of(g);
+            sg.ask = ask_for(s, g);
+            any_dev = any_dev || sg.ask.n_dev > 0;
+            std::memcpy(blob.data() + sizeof(pe::SysGroup) * k, &sg, sizeof(sg));
+            if (evicting) {
+                const pe::PreemptArgs P = preempt_args(s, g);
+                std::memcpy(blob.data() + pre_off + sizeof(pe::PreemptArgs) * k, &P, sizeof(P));
+            }
         }
         HIP_TRY(s, upload_visit(s, s->visit));
-        HIP_TRY(s, upload_s(s, s->d_sysg_groups, groups));
+        HIP_TRY(s, upload_s(s, s->d_sysg_groups, blob));
         const uint32_t nn = (uint32_t)s->nodes.size();
         const bool by_row = (uint64_t)n * 4 >= nn;   // system_place_impl's threshold
         const uint32_t n_tiles = (uint32_t)((E + pe::kSysTile - 1) / pe::kSysTile);
@@ -9816,7 +9925,7 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
         HIP_TRY(s, s->h_sysg_hdr.ensure(sizeof(uint32_t) * (1 + 3 * (size_t)n_tg)));
         uint32_t* hdr = s->h_sysg_hdr.as<uint32_t>();
         uint32_t* hdr_dev = s->h_sysg_hdr.dev<uint32_t>();
-        if (!hdr_dev) return s->fail(PE_EHIP, "pe_system_place_groups: no device view of the header words");
+        if (!hdr_dev) return s->fail(PE_EHIP, fn + ": no device view of the header words");
         // k_sysg_scan leaves the slots zero: a memset only for a new block or after a failed call
         if (s->sysg_counts_zeroed != s->d_sysg_counts.p)
             HIP_TRY(s, hipMemsetAsync(s->d_sysg_counts.p, 0, s->d_sysg_counts.bytes, s->stream));
@@ -9841,7 +9950,62 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
             A.rank_of = s->d_rank_of.as<uint32_t>();
             A.n_rows = nn;
         }
-        HIP_TRY_STATE(s, pe_launch_system_groups(&A, s->stream));
+        // a preempting stack: the stopping form, then the eviction walk over the stopped nodes
+        const uint32_t lanes = by_row ? nn : n;
+        pe::SysEvictArgs V;
+        std::memset(&V, 0, sizeof(V));
+        uint32_t* ctl = nullptr;
+        // the walk starts at the narrowest width that covers all but at most an
+        // eighth of the snapshot's nodes (s->evict_words covers them all): the
+        // few wider nodes take the relaunch, the others keep the small workspace
+        uint32_t words = s->evict_words;
+        if (s->n_beyond_w1 <= nn / 8) words = 1;
+        else if (s->n_beyond_w8 <= nn / 8) words = std::min(words, 8u);
+        size_t app_cap = 0;
+        if (evicting) {
+            // an evicting entry preempts at least one alloc and an alloc is preempted once
+            app_cap = std::min<size_t>(E, s->h_palloc_index.size());
+            HIP_TRY(s, s->d_sysg_resume.ensure(sizeof(uint32_t) * lanes));
+            HIP_TRY(s, s->d_sysg_lanes.ensure(sizeof(uint32_t) * 2 * (size_t)lanes));
+            HIP_TRY(s, s->d_sysg_ctl.ensure(sizeof(uint32_t) * 4));
+            HIP_TRY(s, s->h_sysg_ctl.ensure(sizeof(uint32_t) * 4));
+            HIP_TRY(s, s->d_sysg_app.ensure(sizeof(uint32_t) * (1 + words) * std::max<size_t>(app_cap, 1)));
+            HIP_TRY(s, hipMemsetAsync(s->d_sysg_ctl.p, 0, sizeof(uint32_t) * 4, s->stream));
+            ctl = s->d_sysg_ctl.as<uint32_t>();
+            pe::SysStopArgs S;
+            S.resume = s->d_sysg_resume.as<uint32_t>();
+            S.stopped = s->d_sysg_lanes.as<uint32_t>();
+            S.n_stopped = ctl;
+            // (measurement aid, pe_set_kernel_split: events around the stopping pass, the walk, the compaction)
+            hipEvent_t* split = nullptr;
+            s->split_valid = false;
+            if (s->tun.kernel_split) {
+                for (auto& ev : s->ev_split)
+                    if (!ev) HIP_TRY(s, hipEventCreate(&ev));
+                split = s->ev_split;
+                HIP_TRY(s, hipEventRecord(split[0], s->stream));
+            }
+            HIP_TRY_STATE(s, pe_launch_system_groups_stop(&A, &S, s->stream));
+            if (split) HIP_TRY(s, hipEventRecord(split[1], s->stream));
+            V.G = A;
+            V.pre = reinterpret_cast<const pe::PreemptArgs*>(s->d_sysg_groups.as<uint8_t>() + pre_off);
+            V.preempted = s->d_preempted.as<uint8_t>();
+            V.pcount = s->d_pcount.as<uint32_t>();
+            V.dev_free_all = s->d_dev_free.as<uint32_t>();
+            V.resume = S.resume;
+            V.stopped = S.stopped;
+            V.n_stopped = ctl;
+            V.wider = S.stopped + lanes;
+            V.n_wider = ctl + 1;
+            V.app = s->d_sysg_app.as<uint32_t>();
+            V.n_app = ctl + 2;
+            V.app_cap = (uint32_t)app_cap;
+            V.flags = ctl + 3;
+            HIP_TRY_STATE(s, pe_launch_system_groups_evict(&V, words, lanes, s->stream));
+            if (split) HIP_TRY(s, hipEventRecord(split[2], s->stream));
+        } else {
+            HIP_TRY_STATE(s, pe_launch_system_groups(&A, s->stream));
+        }
         pe::SysCompactArgs Cx;
         std::memset(&Cx, 0, sizeof(Cx));
         Cx.res = A.res;
@@ -9856,15 +10020,87 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
         Cx.hdr = hdr_dev;
         HIP_TRY(s, pe_launch_system_compact(&Cx, s->stream));
         HIP_TRY(s, hipEventRecord(s->ev1, s->stream));
+        if (evicting && s->tun.kernel_split) {
+            HIP_TRY(s, hipEventRecord(s->ev_split[3], s->stream));
+            HIP_TRY(s, hipEventRecord(s->ev_split[4], s->stream));   // (recorded again behind each wider round)
+            s->split_valid = true;
+            s->split_rounds = 1;
+        }
+        if (evicting)
+            HIP_TRY(s, hipMemcpyAsync(s->h_sysg_ctl.p, ctl, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(s, hipStreamSynchronize(s->stream));   // the kernels' wait: the header words are in host memory
         s->sysg_counts_zeroed = s->d_sysg_counts.p;
         p = hdr[0];
-        if ((size_t)p > E) return s->fail(PE_EINTERNAL, "pe_system_place_groups: placed count beyond the entries");
+        if ((size_t)p > E) return s->fail(PE_EINTERNAL, fn + ": placed count beyond the entries");
         std::memcpy(s->sysg_counts.data(), hdr + 1, sizeof(uint32_t) * 3 * (size_t)n_tg);
-        // one DMA: the outcome bytes and the placed entries' scores behind them
-        HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p, hipMemcpyDeviceToHost,
-                                  s->stream));
-        HIP_TRY(s, hipStreamSynchronize(s->stream));
+        // one more round per wider eviction width some node needs (none in the
+        // common case): the walk over the lanes the last launch left, the
+        // compaction again over the completed outcomes; k_sysg_scan hands out
+        // and clears the counters each time, so the rounds' counts add up
+        for (uint32_t round = 0; evicting; round++) {
+            const uint32_t* hc = s->h_sysg_ctl.as<uint32_t>();
+            const uint32_t n_app = hc[2], flags = hc[3];
+            if (flags & (pe::kEvictUnsup | pe::kSysgOverflow))
+                return s->fail(PE_EINTERNAL, fn + ": the eviction walk met a node outside the device path");
+            if ((size_t)n_app > app_cap) return s->fail(PE_EINTERNAL, fn + ": appended records beyond the buffer");
+            if (n_app) {   // this round's records: [entry | mask words]
+                const size_t rec = 1 + (size_t)words, bytes = sizeof(uint32_t) * rec * n_app;
+                HIP_TRY(s, s->h_sysg_app.ensure(bytes));
+                HIP_TRY(s, hipMemcpyAsync(s->h_sysg_app.p, s->d_sysg_app.p, bytes, hipMemcpyDeviceToHost, s->stream));
+                if (!(flags & pe::kEvictWider))   // with the results' DMA below: one wait for both
+                    HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p,
+                                              hipMemcpyDeviceToHost, s->stream));
+                HIP_TRY(s, hipStreamSynchronize(s->stream));
+                const uint32_t* r = s->h_sysg_app.as<uint32_t>();
+                const size_t base = ev_masks.size();
+                ev_masks.insert(ev_masks.end(), r, r + rec * n_app);   // (the staging is reused by a wider round)
+                evicted.reserve(evicted.size() + n_app);
+                for (uint32_t a = 0; a < n_app; a++, r += rec) {
+                    if ((size_t)r[0] >= E) return s->fail(PE_EINTERNAL, fn + ": an appended entry out of range");
+                    evicted.push_back(Evicted{r[0], words, base + rec * a + 1});
+                }
+            } else if (!(flags & pe::kEvictWider)) {
+                HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p,
+                                          hipMemcpyDeviceToHost, s->stream));
+                HIP_TRY(s, hipStreamSynchronize(s->stream));
+            }
+            if (!(flags & pe::kEvictWider)) break;
+            words = wider_words(words);
+            if (!words || round >= 2) return s->fail(PE_EINTERNAL, fn + ": a node beyond the widest eviction width");
+            // the lanes left over become this round's list; its own leftovers go to the other half
+            uint32_t* lists = s->d_sysg_lanes.as<uint32_t>();
+            const bool from_second = (round & 1u) == 0;   // the first walk wrote the second half
+            V.stopped = from_second ? lists + lanes : lists;
+            V.n_stopped = from_second ? ctl + 1 : ctl;
+            V.wider = from_second ? lists : lists + lanes;
+            V.n_wider = from_second ? ctl : ctl + 1;
+            HIP_TRY(s, s->d_sysg_app.ensure(sizeof(uint32_t) * (1 + words) * std::max<size_t>(app_cap, 1)));
+            V.app = s->d_sysg_app.as<uint32_t>();
+            HIP_TRY(s, hipMemsetAsync(V.n_wider, 0, sizeof(uint32_t), s->stream));
+            HIP_TRY(s, hipMemsetAsync(ctl + 2, 0, sizeof(uint32_t) * 2, s->stream));
+            HIP_TRY_STATE(s, pe_launch_system_groups_evict(&V, words, lanes, s->stream));
+            // the compaction again, now over the completed outcomes. (The one
+            // before read res words that the left-over nodes had not written
+            // yet, stale from an earlier call or never initialised: its packed
+            // outcomes, scores and total are all rewritten here and were not
+            // used, only its counters, which come from the kernels' counts.)
+            HIP_TRY(s, pe_launch_system_compact(&Cx, s->stream));
+            if (s->tun.kernel_split) {
+                HIP_TRY(s, hipEventRecord(s->ev_split[4], s->stream));
+                s->split_rounds++;
+            }
+            HIP_TRY(s, hipMemcpyAsync(s->h_sysg_ctl.p, ctl, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(s, hipStreamSynchronize(s->stream));
+            p = hdr[0];
+            if ((size_t)p > E) return s->fail(PE_EINTERNAL, fn + ": placed count beyond the entries");
+            for (size_t c = 0; c < 3 * (size_t)n_tg; c++) s->sysg_counts[c] += hdr[1 + c];
+        }
+        if (!evicting) {
+            // one DMA: the outcome bytes and the placed entries' scores behind them
+            HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p,
+                                      hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(s, hipStreamSynchronize(s->stream));
+        }
         float ms = 0;
         HIP_TRY(s, hipEventElapsedTime(&ms, s->ev0, s->ev1));
         s->last_ms = ms;
@@ -9889,6 +10125,57 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
         s->plan_defer.names.resize(n_tg);
         for (uint32_t k = 0; k < n_tg; k++) s->plan_defer.names[k] = s->tgs[tgs[k]]->name;
         s->plan_defer.status2 = s->h_sysg_out.as<uint8_t>();
+        s->plan_defer.evicting.clear();
+    }
+    if (pre_call) {
+        // Plan.AppendPreemptedAlloc of every evicting entry, as set_preempted
+        // mirrors it: the masks become alloc-table rows in increasing CSR slot,
+        // kept as a CSR by increasing entry
+        const auto by_entry = [](const Evicted& a, const Evicted& b) { return a.e < b.e; };
+        if (evicted.size() * 16 < (size_t)n) {
+            std::sort(evicted.begin(), evicted.end(), by_entry);
+        } else {   // many: a counting sort over the list positions, then the few entries of one position
+            std::vector<uint32_t> at(n + 1, 0);
+            for (const Evicted& v : evicted) at[v.e / n_tg + 1]++;
+            for (uint32_t i = 0; i < n; i++) at[i + 1] += at[i];
+            std::vector<Evicted> sorted(evicted.size());
+            for (const Evicted& v : evicted) sorted[at[v.e / n_tg]++] = v;   // at[pos] ends as the end of pos
+            for (uint32_t i = 0, b = 0; i < n; b = at[i++])
+                if (at[i] - b > 1) std::sort(sorted.begin() + b, sorted.begin() + at[i], by_entry);
+            evicted.swap(sorted);
+        }
+        std::vector<uint32_t> off(1, 0), rows_of;
+        off.reserve(evicted.size() + 1);
+        rows_of.reserve(evicted.size() + evicted.size() / 4);
+        s->plan_defer.evicting.reserve(evicted.size());
+        bool any = false;
+        for (const Evicted& v : evicted) {
+            const uint32_t row = s->visit[v.e / n_tg];
+            const uint32_t b = s->h_node_alloc_off[row], m = s->h_node_alloc_off[row + 1] - b;
+            const uint32_t* mask = ev_masks.data() + v.at;
+            for (uint32_t w = 0; w < v.words && 32u * w < m; w++)
+                for (uint32_t bits = mask[w]; bits; bits &= bits - 1) {   // increasing slot
+                    const uint32_t i = 32u * w + (uint32_t)__builtin_ctz(bits);
+                    if (i >= m) break;
+                    const uint32_t a = s->h_palloc_index[b + i];
+                    rows_of.push_back(a);
+                    s->h_preempted[b + i] = 1;
+                    core_hold(s, a, false);
+                    any = true;
+                }
+            off.push_back((uint32_t)rows_of.size());
+            s->plan_defer.evicting.push_back(v.e);
+        }
+        if (any) invalidate_static(s);
+        const size_t ne = evicted.size();
+        HIP_TRY(s, s->h_sysg_csr.ensure(sizeof(uint32_t) * (2 * ne + 1 + rows_of.size())));
+        uint32_t* w = s->h_sysg_csr.as<uint32_t>();
+        for (size_t i = 0; i < ne; i++) w[i] = evicted[i].e;
+        std::memcpy(w + ne, off.data(), sizeof(uint32_t) * (ne + 1));
+        if (!rows_of.empty()) std::memcpy(w + 2 * ne + 1, rows_of.data(), sizeof(uint32_t) * rows_of.size());
+        s->sysg_pre_entries = (uint32_t)ne;
+        s->sysg_pre_allocs = rows_of.size();
+        s->sysg_pre_valid = true;
     }
     sys_deactivate(s);   // rows committed on the device: the per-row cache is stale
     for (uint32_t k = 0; k < n_tg; k++) {
@@ -9903,7 +10190,27 @@ int pe_system_place_groups(pe_stack* s, const uint32_t* tg_indices, uint32_t n_t
     PE_FLUSH_RESET(s);
     if (!s) return PE_EINVAL;
     s->pre_overflow.clear();
-    return system_place_groups_impl(s, tg_indices, n_tg, out_score, out_status2, counts, placed);
+    return system_place_groups_impl(s, tg_indices, n_tg, out_score, out_status2, counts, placed, false);
+}
+
+int pe_system_place_groups_preempt(pe_stack* s, const uint32_t* tg_indices, uint32_t n_tg, double* out_score,
+                                   uint8_t* out_status2, uint32_t* counts, uint32_t* placed) {
+    PE_FLUSH_RESET(s);
+    if (!s) return PE_EINVAL;
+    s->pre_overflow.clear();
+    return system_place_groups_impl(s, tg_indices, n_tg, out_score, out_status2, counts, placed, true);
+}
+
+int pe_system_groups_preempted(const pe_stack* s, const uint32_t** entries, const uint32_t** off,
+                               const uint32_t** allocs, uint32_t* n_entries) {
+    if (!s || !entries || !off || !allocs || !n_entries) return PE_EINVAL;
+    if (!s->sysg_pre_valid || !s->h_sysg_csr.p) return PE_ESTATE;
+    const uint32_t* w = s->h_sysg_csr.as<uint32_t>();
+    *entries = w;
+    *off = w + s->sysg_pre_entries;
+    *allocs = w + 2 * (size_t)s->sysg_pre_entries + 1;
+    *n_entries = s->sysg_pre_entries;
+    return PE_OK;
 }
 
 int pe_system_groups_results(const pe_stack* s, const double** score, const uint8_t** status2,

@@ -547,4 +547,35 @@ struct SysCompactArgs {
     uint32_t* hdr;                   // mapped host words: [0] placed, [1 + 3 * k + code] the summed counts
 };
 
+// pe_system_place_groups_preempt: the stopping form of the
+// pass (k_system_groups_stop) and the eviction walk over the nodes it stopped
+// (k_system_groups_evict). A lane index is a snapshot row in the row-order
+// form and a list position otherwise, as in k_system_groups.
+struct SysStopArgs {
+    uint32_t* resume;                 // [lanes] the group a node stopped at; n_tg: walked to the end
+    uint32_t* stopped;                // [lanes] the lane indices that stopped, in any order
+    uint32_t* n_stopped;              // [1]
+};
+
+constexpr uint32_t kSysgOverflow = 4u;   // SysEvictArgs::flags beside kEvictUnsup / kEvictWider: the append buffer is full
+
+struct SysEvictArgs {
+    SystemGroupsArgs G;               // (k0 / nk unused: the walk covers every group from a lane's resume group on)
+    const PreemptArgs* pre;           // [n_tg] evict_eval's view of each listed group
+    uint8_t* preempted;               // Plan.NodePreemptions flags, pcount and the free-instance column as
+    uint32_t* pcount;                 // apply_preempt takes them
+    uint32_t* dev_free_all;
+    uint32_t* resume;                 // [lanes] read; rewritten for a lane the launch's width does not cover
+    const uint32_t* stopped;          // the lanes of this launch
+    const uint32_t* n_stopped;
+    uint32_t* wider;                  // the lanes left to the next width
+    uint32_t* n_wider;
+    // one record per evicting entry: the entry index, then the launch's mask
+    // words over the node's CSR slots; at most app_cap records
+    uint32_t* app;
+    uint32_t* n_app;
+    uint32_t app_cap;
+    uint32_t* flags;                  // [1] kEvictUnsup | kEvictWider | kSysgOverflow
+};
+
 }  // namespace pe

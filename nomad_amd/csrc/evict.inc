@@ -1064,6 +1064,34 @@ __global__ void k_commit_preempt(PreemptArgs A, uint32_t row, const uint32_t* ma
     apply_preempt(A, row, AMask<W>::load(mask), preempted, pcount, dev_free);
 }
 
+// One evicting placement on `row`: Plan.AppendPreemptedAlloc of the masked
+// allocs, then Plan.AppendAlloc of the ask with its device offers (*offers:
+// one byte per request, read only for a device ask).
+template <int W>
+__device__ __forceinline__ void commit_evicted_row(const PreemptArgs& A, uint32_t row, const AMask<W>& mask,
+                                                   const uint32_t* offers, uint8_t* preempted, uint32_t* pcount,
+                                                   uint32_t* dev_free) {
+    apply_preempt(A, row, mask, preempted, pcount, dev_free);
+    NodeRec& r = A.soa.rec[row];
+    r.used_cpu += ask_cpu(A.soa, A.ask, row);
+    core_take(A.soa, A.ask, row, 1);
+    r.used_mem += A.ask.mem;
+    r.used_disk += A.ask.disk;
+    r.used_mbits += A.ask.commit_mbits;
+    r.used_dyn += A.ask.commit_dyn;
+    A.soa.coll_job[row] += 1;
+    A.tg.coll_tg[row] += 1;
+    if (A.ask.n_dev > 0) {
+        uint32_t fr = A.tg.dev_free[row];
+        for (int q = 0; q < kMaxDevReq && q < A.ask.n_dev; q++) {
+            const uint32_t g = byte_of(*offers, q), f = byte_of(fr, (int)g);
+            const uint32_t cnt = (uint32_t)A.ask.dev_cnt[q];
+            fr -= (cnt < f ? cnt : f) << (8 * g);
+        }
+        A.tg.dev_free[row] = fr;
+    }
+}
+
 // SystemScheduler placements that evict (scheduler_system.go:283-425): every
 // listed node is distinct, so the preemptions and Plan.AppendAlloc of all
 // chosen nodes apply in parallel (one lane per node).
@@ -1074,26 +1102,8 @@ __global__ void __launch_bounds__(256) k_commit_evicted(PreemptArgs A, uint8_t* 
     uint32_t local = 0;
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < A.n_visit; j += stride) {
         if (A.status[j] != kOption) continue;
-        const uint32_t row = A.visit[j];
-        apply_preempt(A, row, AMask<W>::load(A.mask_out + (size_t)j * W), preempted, pcount, dev_free);
-        NodeRec& r = A.soa.rec[row];
-        r.used_cpu += ask_cpu(A.soa, A.ask, row);
-        core_take(A.soa, A.ask, row, 1);
-        r.used_mem += A.ask.mem;
-        r.used_disk += A.ask.disk;
-        r.used_mbits += A.ask.commit_mbits;
-        r.used_dyn += A.ask.commit_dyn;
-        A.soa.coll_job[row] += 1;
-        A.tg.coll_tg[row] += 1;
-        if (A.ask.n_dev > 0) {
-            uint32_t fr = A.tg.dev_free[row];
-            for (int q = 0; q < kMaxDevReq && q < A.ask.n_dev; q++) {
-                const uint32_t g = byte_of(A.offers_out[j], q), f = byte_of(fr, (int)g);
-                const uint32_t cnt = (uint32_t)A.ask.dev_cnt[q];
-                fr -= (cnt < f ? cnt : f) << (8 * g);
-            }
-            A.tg.dev_free[row] = fr;
-        }
+        commit_evicted_row(A, A.visit[j], AMask<W>::load(A.mask_out + (size_t)j * W), A.offers_out + j, preempted,
+                           pcount, dev_free);
         local++;
     }
     for (int off = 32; off > 0; off >>= 1) local += __shfl_xor(local, off);

@@ -4120,6 +4120,202 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
         atomicAdd(&A.counts[(size_t)(blockIdx.x % kPlacedSlots) * 3u * A.n_tg + 3u * A.k0 + threadIdx.x], cnt[threadIdx.x]);
 }
 
+// ---- the same pass on a preempting stack -------------------
+
+// A distinct slot of `counter` for every active lane: one atomic per wave.
+__device__ __forceinline__ uint32_t wave_slot(uint32_t* counter) {
+    const uint64_t m = __ballot(1);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t leader = (uint32_t)__ffsll((unsigned long long)m) - 1u;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
+    base = __shfl(base, (int)leader);
+    return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+// One plain (node, group) step on a lane's register image: k_system_groups'
+// loop body (the same status_loaded / score_into, so the same bits).
+__device__ __forceinline__ int sysg_plain(const NodeSoA& soa, const SysGroup& G, double log10, uint32_t row, NodeIn& in,
+                                          uint32_t& cj, uint32_t& df, double* score) {
+    in.coll_tg = G.tg.coll_tg[row];
+    in.feas = G.tg.node_feas ? G.tg.node_feas[row] : 1u;
+    in.dev_free = df;
+    ScoreIn si;
+    const int st = status_loaded<false>(soa, G.tg, G.tg.class_ok, G.ask, 0u, row, in, &si);
+    *score = 0.0;
+    if (st == kOption) {
+        lookup_scores(G.tg, nullptr, nullptr, row, in.r.cls, &si);
+        uint32_t ns;
+        *score = score_into<false>(G.ask, log10, si, nullptr, &ns);
+        in.r.used_cpu += G.ask.cpu;
+        in.r.used_mem += G.ask.mem;
+        in.r.used_disk += G.ask.disk;
+        in.r.used_mbits += G.ask.commit_mbits;
+        in.r.used_dyn += G.ask.commit_dyn;
+        cj += 1u;
+        soa.coll_job[row] = cj;
+        G.tg.coll_tg[row] = in.coll_tg + 1u;
+        if (G.ask.n_dev > 0) df = dev_after(G.ask, G.tg.dev_cls[in.r.cls], df, 1);
+    }
+    return st;
+}
+
+// A lane's register image of its node back to HBM.
+__device__ __forceinline__ void sysg_store(const SystemGroupsArgs& A, uint32_t row, const NodeIn& in, uint32_t df,
+                                           uint32_t df0) {
+    NodeRec& r = A.soa.rec[row];
+    r.used_cpu = in.r.used_cpu;
+    r.used_mem = in.r.used_mem;
+    r.used_disk = in.r.used_disk;
+    r.used_mbits = in.r.used_mbits;
+    r.used_dyn = in.r.used_dyn;
+    if (df != df0) A.dev_free[row] = df;
+}
+
+// k_system_groups' stopping form: at the first group whose plain fit is
+// exhausted the lane stops. That entry and the later ones stay unwritten and
+// uncounted, the node's image goes back to HBM as at the end of the walk, the
+// group is kept in resume[lane] and the lane joins the stopped list (one
+// atomic per wave; the list's order is free, the nodes are independent). A
+// later chunk skips the lanes an earlier chunk stopped.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_system_groups_stop(SystemGroupsArgs A,
+                                                                                                   SysStopArgs S) {
+    __shared__ uint32_t cnt[3 * kSysGroupsChunk];
+    if (threadIdx.x < 3 * kSysGroupsChunk) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t span = A.rank_of ? A.n_rows : A.n_list;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < span; i += stride) {
+        uint32_t row = i;
+        if (A.rank_of) {
+            if (A.rank_of[i] == PE_NONE) continue;
+        } else {
+            row = A.list[i];
+        }
+        if (A.k0 > 0 && S.resume[i] < A.k0) continue;   // stopped in an earlier chunk
+        NodeIn in;
+        in.r = A.soa.rec[row];
+        uint32_t cj = A.soa.coll_job[row];
+        const uint32_t df0 = A.dev_free ? A.dev_free[row] : 0u;
+        uint32_t df = df0;
+        bool dirty = false;
+        uint32_t stop_at = A.n_tg;
+        uint64_t* out = A.res + (size_t)i * A.n_tg + A.k0;
+        for (uint32_t kk = 0; kk < A.nk; kk++) {
+            double score;
+            const int st = sysg_plain(A.soa, A.groups[A.k0 + kk], A.log10, row, in, cj, df, &score);
+            if (st == kExhausted) {
+                stop_at = A.k0 + kk;
+                break;
+            }
+            dirty = dirty || st == kOption;
+            out[kk] = sys_box(st, score);
+            const uint64_t m0 = __ballot(st == kOption), m1 = __ballot(st == kFiltered);
+            if (lane == (uint32_t)__ffsll((unsigned long long)(m0 | m1)) - 1u) {
+                if (m0) atomicAdd(&cnt[3 * kk + 0], (uint32_t)__popcll(m0));
+                if (m1) atomicAdd(&cnt[3 * kk + 1], (uint32_t)__popcll(m1));
+            }
+        }
+        if (A.k0 == 0 || stop_at < A.n_tg) S.resume[i] = stop_at;
+        if (stop_at < A.n_tg) S.stopped[wave_slot(S.n_stopped)] = i;
+        if (dirty) sysg_store(A, row, in, df, df0);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * A.nk && cnt[threadIdx.x])
+        atomicAdd(&A.counts[(size_t)(blockIdx.x % kPlacedSlots) * 3u * A.n_tg + 3u * A.k0 + threadIdx.x], cnt[threadIdx.x]);
+}
+
+// The eviction walk over the stopped nodes, one lane per node, at eviction
+// width W. The group loop is wave-uniform (group k's tables and PreemptArgs are
+// read by every lane at once); a lane acts at its resume group and after it:
+// BinPack with evict (evict_eval) where the plain fit is exhausted, on an
+// option k_commit_evicted's commit of one row and a record [entry, W mask
+// words] in the append buffer, then the plain walk as k_system_groups_stop to
+// the next exhausted group. evict_eval and the commit work on HBM, so the image
+// is stored before the call and loaded again after a commit: a lane reads back
+// its own stores only. A node beyond the width commits nothing from that group
+// on: it keeps its resume group, joins the wider list and raises kEvictWider.
+template <int W>
+__global__ void __launch_bounds__(256) k_system_groups_evict(SysEvictArgs A) {
+    const SystemGroupsArgs& Gx = A.G;
+    const uint32_t n = *A.n_stopped;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t* counts = Gx.counts + (size_t)(blockIdx.x % kPlacedSlots) * 3u * Gx.n_tg;
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
+        const uint32_t i = A.stopped[j];
+        uint32_t row = i, pos = i;
+        if (Gx.rank_of) pos = Gx.rank_of[i];
+        else row = Gx.list[i];
+        uint32_t next = A.resume[i];
+        bool evict = true;   // the plain fit at the resume group is known: exhausted
+        NodeIn in;
+        in.r = Gx.soa.rec[row];
+        uint32_t cj = Gx.soa.coll_job[row];
+        uint32_t df0 = Gx.dev_free ? Gx.dev_free[row] : 0u;
+        uint32_t df = df0;
+        bool dirty = false;
+        uint64_t* out = Gx.res + (size_t)i * Gx.n_tg;
+        EvictWs<W> ws;
+        for (uint32_t k = 0; k < Gx.n_tg; k++) {
+            if (k != next) continue;
+            int st = kExhausted;
+            double score = 0.0;
+            if (!evict) {
+                st = sysg_plain(Gx.soa, Gx.groups[k], Gx.log10, row, in, cj, df, &score);
+                dirty = dirty || st == kOption;
+                evict = st == kExhausted;
+            }
+            if (evict) {
+                if (dirty) sysg_store(Gx, row, in, df, df0);
+                dirty = false;
+                const PreemptArgs& P = A.pre[k];
+                NodeEval ev;
+                AMask<W> mask = AMask<W>::zero();
+                uint32_t offers = 0, unsup = 0;
+                const int es = evict_eval<false, false, W>(P, row, &ev, &mask, &offers, &unsup, &ws);
+                if (unsup) {
+                    atomicOr(A.flags, unsup);
+                    if (unsup == kEvictWider) {
+                        A.resume[i] = k;
+                        A.wider[wave_slot(A.n_wider)] = i;
+                    }
+                    next = PE_NONE;   // nothing more for this node in this launch
+                    continue;
+                }
+                if (es == kOption) {
+                    commit_evicted_row(P, row, mask, &offers, A.preempted, A.pcount, A.dev_free_all);
+                    in.r = Gx.soa.rec[row];
+                    cj = Gx.soa.coll_job[row];
+                    df0 = Gx.dev_free ? Gx.dev_free[row] : 0u;
+                    df = df0;
+                    st = kOption;
+                    score = ev.score;
+                    const uint32_t at = wave_slot(A.n_app);
+                    if (at < A.app_cap) {
+                        uint32_t* rec = A.app + (size_t)at * (1u + W);
+                        rec[0] = pos * Gx.n_tg + k;
+                        mask.store(rec + 1);
+                    } else {
+                        atomicOr(A.flags, kSysgOverflow);
+                    }
+                }
+            }
+            out[k] = sys_box(st, score);
+            const uint64_t m0 = __ballot(st == kOption), m1 = __ballot(st == kFiltered), m2 = __ballot(st == kExhausted);
+            if (lane == (uint32_t)__ffsll((unsigned long long)(m0 | m1 | m2)) - 1u) {
+                if (m0) atomicAdd(&counts[3 * k + 0], (uint32_t)__popcll(m0));
+                if (m1) atomicAdd(&counts[3 * k + 1], (uint32_t)__popcll(m1));
+                if (m2) atomicAdd(&counts[3 * k + 2], (uint32_t)__popcll(m2));
+            }
+            evict = false;
+            next = k + 1u;
+        }
+        if (dirty) sysg_store(Gx, row, in, df, df0);
+    }
+}
+
 // The outcome of entry e (position-major, group-minor) from res: 0 placed,
 // 1 filtered, 2 exhausted; *v its boxed word.
 __device__ __forceinline__ uint32_t sysg_entry(const SysCompactArgs& A, uint32_t e, uint64_t* v) {
@@ -4376,6 +4572,38 @@ hipError_t pe_launch_system_groups(const pe::SystemGroupsArgs* a, hipStream_t st
         c.nk = a->n_tg - k0 < pe::kSysGroupsChunk ? a->n_tg - k0 : pe::kSysGroupsChunk;
         hipLaunchKernelGGL(pe::k_system_groups, dim3(blocks), dim3(256), 0, st, c);
     }
+    return hipGetLastError();
+}
+
+// The stopping form, chunked as above (a later chunk skips the stopped lanes).
+hipError_t pe_launch_system_groups_stop(const pe::SystemGroupsArgs* a, const pe::SysStopArgs* s, hipStream_t st) {
+    const uint32_t span = a->rank_of ? a->n_rows : a->n_list;
+    if (!span || !a->n_tg) return hipSuccess;
+    if (!s->resume || !s->stopped || !s->n_stopped) return hipErrorInvalidValue;
+    uint32_t blocks = (span + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    pe::SystemGroupsArgs c = *a;
+    for (uint32_t k0 = 0; k0 < a->n_tg; k0 += pe::kSysGroupsChunk) {
+        c.k0 = k0;
+        c.nk = a->n_tg - k0 < pe::kSysGroupsChunk ? a->n_tg - k0 : pe::kSysGroupsChunk;
+        hipLaunchKernelGGL(pe::k_system_groups_stop, dim3(blocks), dim3(256), 0, st, c, *s);
+    }
+    return hipGetLastError();
+}
+
+// The eviction walk at width `words` over the lanes listed in a->stopped
+// (their count is read on the device; at most `max_lanes`).
+hipError_t pe_launch_system_groups_evict(const pe::SysEvictArgs* a, uint32_t words, uint32_t max_lanes, hipStream_t st) {
+    if (!max_lanes || !a->G.n_tg) return hipSuccess;
+    if (!a->pre || !a->resume || !a->stopped || !a->n_stopped || !a->wider || !a->n_wider || !a->app || !a->n_app ||
+        !a->flags || !a->preempted || !a->pcount || !a->dev_free_all)
+        return hipErrorInvalidValue;
+    uint32_t blocks = (max_lanes + 255) / 256;
+    if (blocks > 1024) blocks = 1024;   // grid-stride beyond
+    if (words == 1u) hipLaunchKernelGGL(pe::k_system_groups_evict<1>, dim3(blocks), dim3(256), 0, st, *a);
+    else if (words == 8u) hipLaunchKernelGGL(pe::k_system_groups_evict<8>, dim3(blocks), dim3(256), 0, st, *a);
+    else if (words == 32u) hipLaunchKernelGGL(pe::k_system_groups_evict<32>, dim3(blocks), dim3(256), 0, st, *a);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

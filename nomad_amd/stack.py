@@ -79,6 +79,13 @@ def load_engine():
             lib.pe_system_groups_results.restype = C.c_int
             lib.pe_system_groups_results.argtypes = [C.c_void_p, C.POINTER(abi.f64p), C.POINTER(abi.u8p),
                                                      C.POINTER(abi.u32p), abi.u32p, abi.u32p, abi.u32p]
+        if hasattr(lib, "pe_system_place_groups_preempt"):
+            lib.pe_system_place_groups_preempt.restype = C.c_int
+            lib.pe_system_place_groups_preempt.argtypes = [C.c_void_p, abi.u32p, C.c_uint32, abi.f64p, abi.u8p,
+                                                           abi.u32p, abi.u32p]
+            lib.pe_system_groups_preempted.restype = C.c_int
+            lib.pe_system_groups_preempted.argtypes = [C.c_void_p, C.POINTER(abi.u32p), C.POINTER(abi.u32p),
+                                                       C.POINTER(abi.u32p), abi.u32p]
         lib.pe_speculation_stats.restype = C.c_int
         lib.pe_speculation_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.pe_comm_unique_id.restype = C.c_int
@@ -588,12 +595,30 @@ class _Stack:
         pe_system_groups_results. A job the pass refuses (Unsupported), or a
         library without the entry point, is answered by
         system_place_groups_by_select when `fallback`."""
+        return self._system_place_groups(tgs, fallback, staged, "system_place_groups")[:4]
+
+    def SystemPlaceGroupsPreempt(self, tgs, fallback: bool = True, staged: bool = False):
+        """SystemPlaceGroups on a stack with preemption enabled
+        (pe_system_place_groups_preempt): a pair whose plain fit is exhausted
+        goes through BinPack with evict, and a pair placed by eviction counts
+        as placed with the eviction Select's FinalScore. Returns
+        (score[n, G], status[n, G], counts[G, 3], placed, preempted), where
+        `preempted` is {(pos, k): [alloc-table rows]} for every entry that
+        preempted something (pe_system_groups_preempted; no PE_MAX_PREEMPT
+        cap). The fallback is system_place_groups_preempt_by_select; it is the
+        stack's own Select in a loop, so it raises Unsupported itself for a job
+        or snapshot that Select refuses where it would evict (reserved cores,
+        allocs outside the on-device eviction limits, an alloc holding one
+        device group twice, several task networks)."""
+        return self._system_place_groups(tgs, fallback, staged, "system_place_groups_preempt")
+
+    def _system_place_groups(self, tgs, fallback, staged, name):
         idx = [self._tg_index(t) for t in tgs]
         n, G = len(self._visit), len(idx)
         try:
-            if not hasattr(self._lib, self._p + "system_place_groups"):
-                raise Unsupported(abi.PE_EUNSUPPORTED, "no multi-group system placement behind this ABI")
-            fn = getattr(self._lib, self._p + "system_place_groups")
+            if not hasattr(self._lib, self._p + name):
+                raise Unsupported(abi.PE_EUNSUPPORTED, "no %s behind this ABI" % name)
+            fn = getattr(self._lib, self._p + name)
             t = np.ascontiguousarray(np.asarray(idx or [0], dtype=np.uint32))
             placed = C.c_uint32(0)
             E = n * G
@@ -618,12 +643,22 @@ class _Stack:
         except Unsupported:
             if not fallback:
                 raise
-            return system_place_groups_by_select(self, idx)
+            return system_place_groups_preempt_by_select(self, idx)
         p = placed.value
         status = unpack_status2(packed, E)
         score = np.full(E, np.nan)
         score[status == 0] = dense[:p]
-        return score.reshape(n, G), status.reshape(n, G), counts.reshape(G, 3).astype(np.uint32), p
+        preempted = {}
+        if name == "system_place_groups_preempt":
+            en, of, al = abi.u32p(), abi.u32p(), abi.u32p()
+            ne = C.c_uint32(0)
+            self._check(self._lib.pe_system_groups_preempted(self._h, C.byref(en), C.byref(of), C.byref(al),
+                                                             C.byref(ne)))
+            if ne.value:
+                offs = np.ctypeslib.as_array(of, shape=(ne.value + 1,)).copy()
+                preempted = preempted_from_csr(np.ctypeslib.as_array(en, shape=(ne.value,)).copy(), offs,
+                                               np.ctypeslib.as_array(al, shape=(int(offs[-1]),)).copy(), G)
+        return score.reshape(n, G), status.reshape(n, G), counts.reshape(G, 3).astype(np.uint32), p, preempted
 
 
 def pack_status2(status) -> np.ndarray:
@@ -654,11 +689,30 @@ def system_place_groups_by_select(stack, tgs):
     SetNodes([row]), Select(tg) and Commit on an option. SelectRaw keeps a nil
     Select's counters, which tell filtered from exhausted. Returns
     SystemPlaceGroups' shape; the node list is put back at the end."""
+    return system_place_groups_preempt_by_select(stack, tgs)[:4]
+
+
+def preempted_from_csr(entries, off, allocs, n_tg: int) -> Dict:
+    """pe_system_groups_preempted's CSR as {(pos, k): [alloc-table rows]}:
+    entry e = pos * n_tg + k, its allocs in allocs[off[i]:off[i + 1]]."""
+    out = {}
+    for i, e in enumerate(entries):
+        out[(int(e) // n_tg, int(e) % n_tg)] = [int(a) for a in allocs[int(off[i]):int(off[i + 1])]]
+    return out
+
+
+def system_place_groups_preempt_by_select(stack, tgs):
+    """system_place_groups_by_select's loop, which on a stack with preemption
+    enabled evicts where the plain fit is exhausted (the Select's record
+    carries the PreemptedAllocs, Commit appends them to the plan). Returns
+    SystemPlaceGroupsPreempt's shape: the four results and
+    {(pos, k): [alloc-table rows]} for every entry that preempted something."""
     rows = np.array(stack._visit, dtype=np.uint32, copy=True)
     n, G = len(rows), len(tgs)
     score = np.full((n, G), np.nan)
     status = np.zeros((n, G), dtype=np.uint8)
     counts = np.zeros((G, 3), dtype=np.uint32)
+    preempted = {}
     for pos in range(n):
         one = rows[pos:pos + 1]
         for k, tg in enumerate(tgs):
@@ -667,11 +721,15 @@ def system_place_groups_by_select(stack, tgs):
             if r.row >= 0:
                 stack.Commit(tg, r.row, r.preempted)   # with the evictions of a preempting stack
                 score[pos, k] = r.final_score
+                if len(r.preempted):
+                    # increasing alloc-table row, as pe_system_groups_preempted lists them (the
+                    # slots of a node are in table order; the reference's order is Go map order)
+                    preempted[(pos, k)] = sorted(int(a) for a in r.preempted)
             else:
                 status[pos, k] = 1 if r.nodes_filtered else 2
             counts[k, status[pos, k]] += 1
     stack.SetNodes(rows)
-    return score, status, counts, int(counts[:, 0].sum())
+    return score, status, counts, int(counts[:, 0].sum()), preempted
 
 
 def inplace_update_by_select(stack, tg, allocs: Sequence[int]):
