@@ -3825,7 +3825,7 @@ int build_tables(pe_stack* s, TgPlan& g, const std::vector<uint32_t>& order, uin
             if (rc) return rc;
         }
         if (staged) {
-            pe::FoldArgs F;
+            pe::FoldArgs F{};
             F.class_src = staged;
             F.class_dst = g.class_ok.as<uint8_t>();
             F.ncls = (uint32_t)class_ok.size();
@@ -4658,6 +4658,9 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
             A.fold = s->pending_fold;
             s->fold_pending = false;
             fold_taken = true;
+            // unique rows (the chain's precondition) over the whole table: a
+            // permutation, so k_base's pass over the list stores node_feas
+            A.fold.list_covers = !fused && A.base_by_pos && n == A.soa.n ? 1u : 0u;
         }
     }
     {

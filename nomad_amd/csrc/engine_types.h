@@ -239,6 +239,10 @@ struct FoldArgs {
     uint32_t ncls;
     const uint8_t* node_ok;      // [n] or null
     uint8_t* feas;               // [n] node_feas; null: no fold carried
+    // k_base only: the launch's visit list is a permutation of the whole table
+    // (unique rows, n_visit == n), so the pass over the list stores every
+    // row's node_feas and the separate pass over the table is skipped
+    uint32_t list_covers;
 };
 
 // One launch = n_evals independent evaluations (one workgroup each) of the same

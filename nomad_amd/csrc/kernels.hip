@@ -1555,7 +1555,9 @@ __device__ __forceinline__ double encode_eval(const NodeEval& ev) {
 // each workgroup pulls the class verdict table from the staging ring into LDS,
 // the grid stores node_feas for every row (the later kernels read it), and the
 // evaluation reads the verdict from the table (no dependency on another
-// workgroup's stores).
+// workgroup's stores). FoldArgs::list_covers: the visit list is a permutation
+// of the table, so the main loop's dk == 0 lane stores its row's node_feas and
+// no separate pass over the table runs.
 constexpr int kBaseBlock = 64;
 template <bool FOLD>
 __global__ void __launch_bounds__(kBaseBlock) k_base(BatchArgs A) {
@@ -1571,42 +1573,67 @@ __global__ void __launch_bounds__(kBaseBlock) k_base(BatchArgs A) {
         if (A.fold.node_ok) ok = ok && A.fold.node_ok[row] != 0;
         return ok;
     };
+    const uint32_t m = A.base_by_pos ? A.n_visit : A.soa.n;
+    const uint32_t sh = A.base1 ? 1u : 0u;
+    const uint32_t total = m << sh;
+    const uint32_t first = blockIdx.x * kBaseBlock + threadIdx.x;
+    // the row of position t >> sh (a staged list is read over the bus)
+    auto row_of = [&](uint32_t t) {
+        const uint32_t j = t >> sh;
+        if (!A.base_by_pos) return j;
+        return A.perm_src ? A.perm_src[j] : A.perms[j];
+    };
+    // the row's reads but the verdict (FOLD takes it from the LDS table)
+    auto load_row = [&](uint32_t row, NodeIn& in) {
+        in.r = A.soa.rec[row];
+        in.coll_tg = tg.coll_tg[row];
+        in.dev_free = tg.dev_free ? tg.dev_free[row] : 0u;
+    };
+    uint32_t row = 0;
+    NodeIn in;
     if (FOLD) {
+        // The lane's first position is in flight while the class table comes
+        // over the bus: its list entry is requested before the table, its row's
+        // reads as soon as the entry is there, and nothing waits for them
+        // before the evaluation.
         const FoldArgs& F = A.fold;
-        for (uint32_t c = threadIdx.x; c < F.ncls; c += kBaseBlock) {
+        if (first < total) row = row_of(first);
+        uint8_t v0 = 0;
+        if (threadIdx.x < F.ncls) v0 = F.class_src[threadIdx.x];
+        if (first < total) load_row(row, in);
+        if (threadIdx.x < F.ncls) {
+            cls_ok[threadIdx.x] = v0;
+            if (blockIdx.x == 0) F.class_dst[threadIdx.x] = v0;
+        }
+        for (uint32_t c = threadIdx.x + kBaseBlock; c < F.ncls; c += kBaseBlock) {
             const uint8_t v = F.class_src[c];
             cls_ok[c] = v;
             if (blockIdx.x == 0) F.class_dst[c] = v;
         }
         __syncthreads();
-        for (uint32_t row = blockIdx.x * kBaseBlock + threadIdx.x; row < A.soa.n; row += stride)
-            F.feas[row] = fold_ok(row, A.soa.rec[row].cls) ? 1 : 0;
+        // node_feas of every row: by the main loop below when the list is a
+        // permutation of the table (it holds each row's record and verdict
+        // once), else by a pass over the table
+        if (!F.list_covers)
+            for (uint32_t r = first; r < A.soa.n; r += stride)
+                F.feas[r] = fold_ok(r, A.soa.rec[r].cls) ? 1 : 0;
         class_ok = cls_ok;
     }
-    const uint32_t m = A.base_by_pos ? A.n_visit : A.soa.n;
-    const uint32_t sh = A.base1 ? 1u : 0u;
-    const uint32_t total = m << sh;
-    for (uint32_t t = blockIdx.x * kBaseBlock + threadIdx.x; t < total; t += stride) {
+    for (uint32_t t = first; t < total; t += stride) {
         const uint32_t dk = t & sh;
         const uint32_t j = t >> sh;
-        uint32_t row = j;
-        if (A.base_by_pos) {
-            if (A.perm_src) {
-                row = A.perm_src[j];
-                if (!dk) A.perm_dst[j] = row;
-            } else {
-                row = A.perms[j];
-            }
-        }
-        NodeIn in;
         if (FOLD) {   // the verdict from the LDS table: other workgroups are still storing node_feas
-            in.r = A.soa.rec[row];
-            in.coll_tg = tg.coll_tg[row];
-            in.dev_free = tg.dev_free ? tg.dev_free[row] : 0u;
+            if (t != first) {
+                row = row_of(t);
+                load_row(row, in);
+            }
             in.feas = fold_ok(row, in.r.cls) ? 1u : 0u;
+            if (A.fold.list_covers && !dk) A.fold.feas[row] = (uint8_t)in.feas;
         } else {
+            row = row_of(t);
             load_node(A.soa, tg, row, in);
         }
+        if (A.base_by_pos && A.perm_src && !dk) A.perm_dst[j] = row;
         NodeEval ev;
         ev.score = 0.0;
         eval_loaded<false, false>(A.soa, tg, class_ok, A.ask, dk, A.penalty_bits, A.log10, nullptr, row, in, &ev);
@@ -1691,6 +1718,10 @@ __device__ __forceinline__ void build_emit_rec(const BatchArgs& A, const ChainEm
 constexpr int kChainBlock = 1024;
 constexpr int kChainItems = 16;                               // positions per lane of the largest shape
 constexpr uint32_t kChainMaxN = kChainBlock * kChainItems;   // positions per phase held in registers (largest shape)
+#ifndef PE_CHAIN_LOAD_BATCH
+#define PE_CHAIN_LOAD_BATCH 4
+#endif
+constexpr int kChainLoadBatch = PE_CHAIN_LOAD_BATCH;          // window values a lane loads per memory round trip
 constexpr int kChainMaxSel = 1024;                            // Selects resolved per phase
 constexpr uint32_t kChainMaxRedo = 2048;                      // rows re-evaluated per phase (<= placements per launch)
 
@@ -2047,6 +2078,8 @@ __global__ void __launch_bounds__(kChainBlock) k_chain(BatchArgs A, uint32_t n_e
                 const bool rows_all = !A.base_by_pos || (placed && !use_bm);
                 uint32_t row[ITEMS];
 #pragma unroll
+                for (int q = 0; q < ITEMS; q++) row[q] = 0u;   // a valid index where the position is not read
+#pragma unroll
                 for (int q = 0; q < ITEMS; q++) {
                     if (q >= qn) break;
                     const uint32_t j = (uint32_t)(q * kChainBlock + tid);
@@ -2074,13 +2107,12 @@ __global__ void __launch_bounds__(kChainBlock) k_chain(BatchArgs A, uint32_t n_e
                         }
                     }
                 }
+                if (FUSED && !placed) {
 #pragma unroll
-                for (int q = 0; q < ITEMS; q++) {
-                    if (q >= qn) break;
-                    const uint32_t j = (uint32_t)(q * kChainBlock + tid);
-                    if (j < W && !((redo_mask >> q) & 1u)) {
-                        double v;
-                        if (FUSED && !placed) {
+                    for (int q = 0; q < ITEMS; q++) {
+                        if (q >= qn) break;
+                        const uint32_t j = (uint32_t)(q * kChainBlock + tid);
+                        if (j < W && !((redo_mask >> q) & 1u)) {
                             // the first phase evaluates its positions (and
                             // stores the visit order when it came staged)
                             const uint32_t p = wrap_pos(cur + j, n);
@@ -2091,16 +2123,59 @@ __global__ void __launch_bounds__(kChainBlock) k_chain(BatchArgs A, uint32_t n_e
                             } else {
                                 r = perm[p];
                             }
-                            v = A.fused_parts ? chain_eval_parts(Ak, r, p) : chain_reeval(Ak, r, 0u);
+                            const double v = A.fused_parts ? chain_eval_parts(Ak, r, p) : chain_reeval(Ak, r, 0u);
                             A.base[p] = v;
-                        } else {
-                            const double* src = ((one_mask >> q) & 1u) ? A.base1 : A.base;
-                            v = src[A.base_by_pos ? wrap_pos(cur + j, n) : row[q]];
+                            vs[j] = v;   // read back by the Select walks of step 5 (after the barriers)
+                            const bool is_o = v > -__builtin_inf() && v < __builtin_inf();
+                            optmask |= (uint32_t)is_o << q;
+                            nmask |= (uint32_t)(is_o && v <= 0.0) << q;
                         }
-                        vs[j] = v;   // read back by the Select walks of step 5 (after the barriers)
-                        const bool is_o = v > -__builtin_inf() && v < __builtin_inf();
-                        optmask |= (uint32_t)is_o << q;
-                        nmask |= (uint32_t)(is_o && v <= 0.0) << q;
+                    }
+                } else {
+                    // table reads in groups of kBatch: a group's loads are all
+                    // issued before the first is consumed (one memory round
+                    // trip per group, not per item). The index is clamped to
+                    // the window's last position, so the loads need no guard;
+                    // a position past the window or queued for re-evaluation
+                    // drops its value.
+                    constexpr int kBatch = kChainLoadBatch < ITEMS ? kChainLoadBatch : ITEMS;
+                    // the lane's index as the compiler cannot see through it:
+                    // the addresses vs + j of all ITEMS stores are otherwise
+                    // loop-invariant, hoisted out of the phase loop and spilled
+                    uint32_t ltid = (uint32_t)tid;
+                    asm volatile("" : "+v"(ltid));
+#pragma unroll
+                    for (int g = 0; g < ITEMS; g += kBatch) {
+                        if (g >= qn) break;
+                        double v[kBatch];
+#pragma unroll
+                        for (int k = 0; k < kBatch; k++) {
+                            const int q = g + k;
+                            if (q >= ITEMS) break;
+                            const uint32_t j = min((uint32_t)(q * kChainBlock) + ltid, W - 1u);
+                            const double* src = ((one_mask >> q) & 1u) ? A.base1 : A.base;
+                            uint32_t p = cur + j;   // cur < n and j < W <= n: one subtraction wraps it
+                            if (p >= n) p -= n;
+                            v[k] = src[A.base_by_pos ? p : row[q]];
+                        }
+                        // the whole group has landed here: a load still pending
+                        // across the conditional stores below makes the next
+                        // group wait for those stores' completion as well
+#pragma unroll
+                        for (int k = 0; k < kBatch; k++)
+                            if (g + k < ITEMS) asm volatile("" : "+v"(v[k]));
+#pragma unroll
+                        for (int k = 0; k < kBatch; k++) {
+                            const int q = g + k;
+                            if (q >= ITEMS) break;
+                            const uint32_t j = (uint32_t)(q * kChainBlock) + ltid;
+                            if (j < W && !((redo_mask >> q) & 1u)) {
+                                vs[j] = v[k];   // read back by the Select walks of step 5 (after the barriers)
+                                const bool is_o = v[k] > -__builtin_inf() && v[k] < __builtin_inf();
+                                optmask |= (uint32_t)is_o << q;
+                                nmask |= (uint32_t)(is_o && v[k] <= 0.0) << q;
+                            }
+                        }
                     }
                 }
             }
@@ -2126,14 +2201,32 @@ __global__ void __launch_bounds__(kChainBlock) k_chain(BatchArgs A, uint32_t n_e
                 }
                 __syncthreads();
                 if (sh.err) break;
+                // the re-evaluated values back, in the same groups (every index
+                // lies inside this workgroup's kChainMaxN doubles of vs)
+                constexpr int kBatch = kChainLoadBatch < ITEMS ? kChainLoadBatch : ITEMS;
+                uint32_t ltid = (uint32_t)tid;   // opaque, as in step 1: no hoisted address per item
+                asm volatile("" : "+v"(ltid));
 #pragma unroll
-                for (int q = 0; q < ITEMS; q++) {
-                    if (q >= qn) break;
-                    if ((redo_mask >> q) & 1u) {
-                        const double v = vs[q * kChainBlock + tid];
-                        const bool is_o = v > -__builtin_inf() && v < __builtin_inf();
-                        optmask |= (uint32_t)is_o << q;
-                        nmask |= (uint32_t)(is_o && v <= 0.0) << q;
+                for (int g = 0; g < ITEMS; g += kBatch) {
+                    if (g >= qn) break;
+                    double v[kBatch];
+#pragma unroll
+                    for (int k = 0; k < kBatch; k++) {
+                        if (g + k >= ITEMS) break;
+                        v[k] = vs[(uint32_t)((g + k) * kChainBlock) + ltid];
+                    }
+#pragma unroll
+                    for (int k = 0; k < kBatch; k++)
+                        if (g + k < ITEMS) asm volatile("" : "+v"(v[k]));
+#pragma unroll
+                    for (int k = 0; k < kBatch; k++) {
+                        const int q = g + k;
+                        if (q >= ITEMS) break;
+                        if ((redo_mask >> q) & 1u) {
+                            const bool is_o = v[k] > -__builtin_inf() && v[k] < __builtin_inf();
+                            optmask |= (uint32_t)is_o << q;
+                            nmask |= (uint32_t)(is_o && v[k] <= 0.0) << q;
+                        }
                     }
                 }
             }
@@ -4481,6 +4574,9 @@ hipError_t pe_launch_chain(const pe::BatchArgs* a, uint32_t n_evals, uint32_t ma
     if (a->base_by_pos && n_evals != 1) return hipErrorInvalidValue;
     if (a->perm_src && (!a->base_by_pos || !a->perm_dst)) return hipErrorInvalidValue;
     if (a->fold.feas && (!a->fold.class_src || !a->fold.class_dst || a->fold.ncls > pe::kFoldMaxClasses))
+        return hipErrorInvalidValue;
+    // list_covers: k_base's pass over the list is the only writer of node_feas
+    if (a->fold.list_covers && (!a->fold.feas || a->fused || !a->base_by_pos || a->n_visit != a->soa.n))
         return hipErrorInvalidValue;
     const size_t lds = pe_chain_lds_bytes(a->hash_bits, a->packed_overlay != 0, a->n_visit);
     uint32_t grid = n_evals < max_blocks ? n_evals : max_blocks;
