@@ -575,6 +575,57 @@ int pe_system_place_groups_preempt(pe_stack* s, const uint32_t* tg_indices, uint
  * yet, or a pe_system_place* call since. */
 int pe_system_groups_preempted(const pe_stack* s, const uint32_t** entries, const uint32_t** off,
                                const uint32_t** allocs, uint32_t* n_entries);
+/* pe_system_place_groups_preempt for a caller that keeps AllocMetric
+ * (pe_set_metrics on), as SystemScheduler.computePlacements does
+ * (scheduler_system.go:283-425: every placed alloc carries ctx.Metrics(), the
+ * first failed placement of a task group is kept whole in failedTGAllocs, later
+ * ones only count). The walk, the result layout, the staging rules, the
+ * argument errors and the refusals are pe_system_place_groups_preempt's, minus
+ * the refusal of pe_set_metrics; it runs on a preempting and on a
+ * non-preempting system stack; pe_system_groups_results and
+ * pe_system_groups_preempted serve it too. With metrics off it is
+ * pe_system_place_groups_preempt. With metrics on every result and every later
+ * observable state equals that of the node-major per-Select loop with metrics
+ * on, the reference memo behind the "computed class ineligible" reasons of
+ * later Selects included; the filtered reasons of this call's own Selects are
+ * not returned (computePlacements drops a filtered nil Select, :311-324), and
+ * there is no "last Select": pe_last_metrics answers PE_ESTATE after it.
+ *
+ * What the caller needs of each Select's maps comes from pe_system_groups_metrics:
+ *   failures[k], k < n_tg: the first exhausted Select of listed group k in walk
+ *     order (the smallest list position whose entry of group k is exhausted in
+ *     the final outcome). That Select's maps are NodesEvaluated 1,
+ *     NodesExhausted 1, ClassExhausted{node_class: 1} and
+ *     DimensionExhausted{dimension: 1}: the dimension that Select saw, after
+ *     the earlier groups' placements and evictions on the node. dimension is a
+ *     key as pe_metric_count.key (pe_metric_string gives its text); it and
+ *     node_class are PE_NONE where that Select recorded none (an empty
+ *     NodeClass; an eviction Select that gave the node up without
+ *     ExhaustedNode, rank.go:283-300). Later exhausted entries are
+ *     counts[3 * k + 2] - 1 coalesced failures.
+ *   *dev_group: the listed index of the group whose ask scores devices (a
+ *     device request with affinities), or -1. When >= 0, dev_binpack[pos] and
+ *     dev_devices[pos] (*n values each, by list position) are that group's
+ *     "binpack" and "devices" ScoreNode values where its entry is placed,
+ *     plainly or by eviction, NaN elsewhere; its NormScore is the entry's
+ *     FinalScore. When -1 both pointers are NULL: every placed entry's
+ *     ScoreMetaData is one item, its node with "binpack" = NormScore =
+ *     FinalScore (the SystemStack ranks with BinPack alone, stack.go:277-281).
+ * The arrays are page-locked staging, valid until the next pe_system_place*
+ * call on the handle. PE_ESTATE: no pe_system_place_groups_metrics call with
+ * metrics on yet, or a pe_system_place* call since. */
+typedef struct pe_sysg_failure {
+    uint32_t pos;          /* list position; PE_NONE: group k has no exhausted entry (dimension and node_class PE_NONE too) */
+    uint32_t dimension;    /* DimensionExhausted key, or PE_NONE */
+    uint32_t node_class;   /* ClassExhausted key (the node's NodeClass string id), or PE_NONE */
+    uint32_t reserved;     /* 0 */
+} pe_sysg_failure;
+int pe_system_place_groups_metrics(pe_stack* s, const uint32_t* tg_indices, uint32_t n_tg,
+                                   double* out_score, uint8_t* out_status2,
+                                   uint32_t* counts, uint32_t* placed);
+int pe_system_groups_metrics(const pe_stack* s, const pe_sysg_failure** failures,
+                             int32_t* dev_group, const double** dev_binpack, const double** dev_devices,
+                             uint32_t* n);
 /* Full-scan Select sharded over GPUs (one process per GPU, each holding the
  * same snapshot, job, SetNodes list and plan). Each rank sweeps
  * the snapshot rows [row_begin, row_end) it owns into a pe_shard_rec: the
@@ -600,7 +651,8 @@ uint32_t pe_last_sweep_bytes(const pe_stack* s);
  * on, the chain path records HIP events between its kernels and
  * pe_last_kernel_split writes the last launch's ms4 = {k_base, k_chain, k_emit,
  * k_emit_writeback}; PE_ESTATE when the last pe_place / Select ran no chain.
- * pe_system_place_groups_preempt on a preempting stack records them too:
+ * pe_system_place_groups_preempt and pe_system_place_groups_metrics on a
+ * preempting stack record them too:
  * ms4 = {stopping pass, eviction walk at the first width, compaction, the
  * time on the stream from there to the end of the last relaunch at a wider
  * width (host waits between the rounds included); exactly 0 when no node

@@ -233,6 +233,7 @@ ENGINE_SYMBOLS = [
     "pe_last_metrics_bin", "pe_metric_string", "pe_scorer_name", "pe_system_results", "pe_inplace_update",
     "pe_system_place_groups", "pe_system_groups_results",
     "pe_system_place_groups_preempt", "pe_system_groups_preempted",
+    "pe_system_place_groups_metrics", "pe_system_groups_metrics",
 ]
 
 
@@ -251,6 +252,10 @@ PE_METRIC_CLASS_FILTERED, PE_METRIC_CONSTRAINT_FILTERED, PE_METRIC_CLASS_EXHAUST
 PE_METRIC_ENGINE_KEY = 0x80000000
 SCORER_NAMES = ("binpack", "devices", "job-anti-affinity", "node-reschedule-penalty", "node-affinity",
                 "allocation-spread", "preemption")
+
+
+class pe_sysg_failure(C.Structure):   # nomad_pe.h: a listed group's first exhausted Select (pe_system_groups_metrics)
+    _fields_ = [("pos", C.c_uint32), ("dimension", C.c_uint32), ("node_class", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class pe_metric_count(C.Structure):   # nomad_pe.h: one AllocMetric map entry

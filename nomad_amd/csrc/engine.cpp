@@ -932,6 +932,13 @@ struct pe_stack {
     uint32_t sysg_pre_entries = 0;
     size_t sysg_pre_allocs = 0;
     bool sysg_pre_valid = false;
+    // pe_system_place_groups_metrics: the first-failure words and the device
+    // group's named scores on the device; in staging the failures as the
+    // caller reads them and the two named arrays ([n] binpack, [n] devices)
+    DevMem d_sysg_first, d_sysg_named;
+    PinnedMem h_sysg_first, h_sysg_fail, h_sysg_named;
+    int32_t sysg_dev_group = -1;
+    bool sysg_met_valid = false;
     bool stopped(uint32_t ai) const { return ai < stop_count.size() && stop_count[ai] > 0; }
 
     // multi-GPU handle (pe_comm_init): an RCCL communicator over the ranks'
@@ -8894,6 +8901,7 @@ static int system_place_impl(pe_stack* s, uint32_t tgi, double* out_score, uint8
     }
     if (s->cfg.stack_kind != PE_STACK_SYSTEM) return s->fail(PE_ESTATE, "pe_system_place needs a system stack");
     s->sysg_pre_valid = false;   // (pe_system_groups_preempted: until the next pe_system_place* call)
+    s->sysg_met_valid = false;   // (pe_system_groups_metrics likewise)
     s->gen++;
     HIP_TRY(s, hipSetDevice(s->device));
     // every node appears once (checked by SetNodes): the single-node Selects are independent
@@ -9792,9 +9800,17 @@ int pe_system_place(pe_stack* s, uint32_t tgi, double* out_score, uint8_t* out_s
 // exhausted; the preempted allocs of every evicting entry are kept as a CSR
 // (pe_system_groups_preempted). Results and state equal those of
 // pe_system_place of each listed group in turn on the preempting stack.
+//
+// `met_call`: pe_system_place_groups_metrics, the `pre_call`
+// form that runs with AllocMetric on. The walks' metrics forms return each
+// group's first exhausted entry with its dimension and the device group's
+// named scores (pe_system_groups_metrics); the reference memo advances group
+// after group.
 static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n_tg, double* out_score,
-                                    uint8_t* out_status2, uint32_t* counts, uint32_t* placed, bool pre_call) {
-    const std::string fn = pre_call ? "pe_system_place_groups_preempt" : "pe_system_place_groups";
+                                    uint8_t* out_status2, uint32_t* counts, uint32_t* placed, bool pre_call,
+                                    bool met_call = false) {
+    const std::string fn = met_call ? "pe_system_place_groups_metrics"
+                                    : (pre_call ? "pe_system_place_groups_preempt" : "pe_system_place_groups");
     if (placed) *placed = 0;
     if (n_tg == 0 || !tgs) return s->fail(PE_EINVAL, fn + ": no task group listed");
     if ((!out_score) != (!out_status2) || (!out_score) != (!counts))
@@ -9815,10 +9831,11 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
     uint32_t n_dev_groups = 0;
     if (!s->visit_unique) why = "duplicate rows in the system placement list";
     else if (s->cfg.preempt && !pre_call) why = "preemption is enabled (BinPack evicts)";
-    else if (s->metrics_on) why = "AllocMetric maps are on (pe_set_metrics)";
+    else if (s->metrics_on && !met_call) why = "AllocMetric maps are on (pe_set_metrics)";
     else if (!s->kids.empty()) why = "a handle over several devices";
     for (auto& c : s->job_constraints)
         if (!why && c.op == "distinct_property") why = "distinct_property";
+    const bool metrics = met_call && s->metrics_on;
     for (uint32_t k = 0; k < n_tg && !why; k++) {
         const TgPlan& g = *s->tgs[tgs[k]];
         if (!g.distinct_props.empty()) why = "distinct_property";
@@ -9888,10 +9905,14 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
     if (E >= (size_t(1) << 31)) return s->fail(PE_EUNSUPPORTED, fn + ": more than 2^31 entries");
     s->sysg_valid = false;
     s->sysg_pre_valid = false;
+    s->sysg_met_valid = false;
     s->sysg_counts.assign(3 * (size_t)n_tg, 0);
     const size_t sb = ((E + 3) / 4 + 7) & ~(size_t)7;   // outcome bytes, the scores 8-byte aligned behind them
     uint32_t p = 0;
     bool any_dev = false;
+    int32_t dev_group = -1;   // (metrics) the listed group whose ask scores devices
+    for (uint32_t k = 0; k < n_tg && metrics; k++)
+        if (ask_for(s, *s->tgs[tgs[k]]).dev_tw != 0.0) dev_group = (int32_t)k;
     // the evicting entries with their preempted sets: (entry, width, mask words)
     struct Evicted { uint32_t e, words; size_t at; };
     std::vector<Evicted> evicted;
@@ -9933,6 +9954,36 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
         if (s->sysg_counts_zeroed != s->d_sysg_counts.p)
             HIP_TRY(s, hipMemsetAsync(s->d_sysg_counts.p, 0, s->d_sysg_counts.bytes, s->stream));
         s->sysg_counts_zeroed = nullptr;
+        // AllocMetric on: the first-failure words (all ones: none) and the
+        // device group's named scores (NaN: not placed), filled by the walks
+        pe::SysMetricsArgs M;
+        std::memset(&M, 0, sizeof(M));
+        M.dev_group = -1;
+        if (metrics) {
+            const size_t fb = sizeof(uint64_t) * n_tg, nb = sizeof(double) * 2 * (size_t)n;
+            HIP_TRY(s, s->d_sysg_first.ensure(fb));
+            HIP_TRY(s, s->h_sysg_first.ensure(fb));
+            HIP_TRY(s, hipMemsetAsync(s->d_sysg_first.p, 0xFF, fb, s->stream));
+            M.first = s->d_sysg_first.as<unsigned long long>();
+            M.n_list = n;
+            if (dev_group >= 0) {
+                HIP_TRY(s, s->d_sysg_named.ensure(nb));
+                HIP_TRY(s, s->h_sysg_named.ensure(nb));
+                HIP_TRY(s, hipMemsetAsync(s->d_sysg_named.p, 0xFF, nb, s->stream));
+                M.dev_group = dev_group;
+                M.dev_named = s->d_sysg_named.as<double>();
+            }
+        }
+        // the maps' copies, queued with the results' DMA: one wait for all
+        auto queue_maps = [&]() -> hipError_t {
+            if (!metrics) return hipSuccess;
+            hipError_t e = hipMemcpyAsync(s->h_sysg_first.p, s->d_sysg_first.p, sizeof(uint64_t) * n_tg,
+                                          hipMemcpyDeviceToHost, s->stream);
+            if (e == hipSuccess && dev_group >= 0)
+                e = hipMemcpyAsync(s->h_sysg_named.p, s->d_sysg_named.p, sizeof(double) * 2 * (size_t)n,
+                                   hipMemcpyDeviceToHost, s->stream);
+            return e;
+        };
         pe::SystemGroupsArgs A;
         std::memset(&A, 0, sizeof(A));
         A.soa = soa_of(s);
@@ -9988,7 +10039,9 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
                 split = s->ev_split;
                 HIP_TRY(s, hipEventRecord(split[0], s->stream));
             }
-            HIP_TRY_STATE(s, pe_launch_system_groups_stop(&A, &S, s->stream));
+            // (the stopping pass records no failure; its metrics form only for the device group's named scores)
+            if (metrics && dev_group >= 0) HIP_TRY_STATE(s, pe_launch_system_groups_metrics(&A, &S, &M, s->stream));
+            else HIP_TRY_STATE(s, pe_launch_system_groups_stop(&A, &S, s->stream));
             if (split) HIP_TRY(s, hipEventRecord(split[1], s->stream));
             V.G = A;
             V.pre = reinterpret_cast<const pe::PreemptArgs*>(s->d_sysg_groups.as<uint8_t>() + pre_off);
@@ -10004,10 +10057,13 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
             V.n_app = ctl + 2;
             V.app_cap = (uint32_t)app_cap;
             V.flags = ctl + 3;
-            HIP_TRY_STATE(s, pe_launch_system_groups_evict(&V, words, lanes, s->stream));
+            V.M = M;
+            if (metrics) HIP_TRY_STATE(s, pe_launch_system_groups_evict_metrics(&V, words, lanes, s->stream));
+            else HIP_TRY_STATE(s, pe_launch_system_groups_evict(&V, words, lanes, s->stream));
             if (split) HIP_TRY(s, hipEventRecord(split[2], s->stream));
         } else {
-            HIP_TRY_STATE(s, pe_launch_system_groups(&A, s->stream));
+            if (metrics) HIP_TRY_STATE(s, pe_launch_system_groups_metrics(&A, nullptr, &M, s->stream));
+            else HIP_TRY_STATE(s, pe_launch_system_groups(&A, s->stream));
         }
         pe::SysCompactArgs Cx;
         std::memset(&Cx, 0, sizeof(Cx));
@@ -10050,6 +10106,7 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
                 const size_t rec = 1 + (size_t)words, bytes = sizeof(uint32_t) * rec * n_app;
                 HIP_TRY(s, s->h_sysg_app.ensure(bytes));
                 HIP_TRY(s, hipMemcpyAsync(s->h_sysg_app.p, s->d_sysg_app.p, bytes, hipMemcpyDeviceToHost, s->stream));
+                if (!(flags & pe::kEvictWider)) HIP_TRY(s, queue_maps());
                 if (!(flags & pe::kEvictWider))   // with the results' DMA below: one wait for both
                     HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p,
                                               hipMemcpyDeviceToHost, s->stream));
@@ -10063,6 +10120,7 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
                     evicted.push_back(Evicted{r[0], words, base + rec * a + 1});
                 }
             } else if (!(flags & pe::kEvictWider)) {
+                HIP_TRY(s, queue_maps());
                 HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p,
                                           hipMemcpyDeviceToHost, s->stream));
                 HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -10081,7 +10139,8 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
             V.app = s->d_sysg_app.as<uint32_t>();
             HIP_TRY(s, hipMemsetAsync(V.n_wider, 0, sizeof(uint32_t), s->stream));
             HIP_TRY(s, hipMemsetAsync(ctl + 2, 0, sizeof(uint32_t) * 2, s->stream));
-            HIP_TRY_STATE(s, pe_launch_system_groups_evict(&V, words, lanes, s->stream));
+            if (metrics) HIP_TRY_STATE(s, pe_launch_system_groups_evict_metrics(&V, words, lanes, s->stream));
+            else HIP_TRY_STATE(s, pe_launch_system_groups_evict(&V, words, lanes, s->stream));
             // the compaction again, now over the completed outcomes. (The one
             // before read res words that the left-over nodes had not written
             // yet, stale from an earlier call or never initialised: its packed
@@ -10100,6 +10159,7 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
         }
         if (!evicting) {
             // one DMA: the outcome bytes and the placed entries' scores behind them
+            HIP_TRY(s, queue_maps());
             HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p,
                                       hipMemcpyDeviceToHost, s->stream));
             HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -10113,6 +10173,61 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
     s->sysg_ntg = n_tg;
     s->sysg_placed = p;
     s->sysg_valid = true;
+    if (metrics) {
+        // each group's first failure as the caller reads it: the walk's code
+        // to the dimension key compute_metrics records, the node's class key
+        HIP_TRY(s, s->h_sysg_fail.ensure(sizeof(pe_sysg_failure) * n_tg));
+        pe_sysg_failure* f = s->h_sysg_fail.as<pe_sysg_failure>();
+        const uint64_t* w = n ? s->h_sysg_first.as<uint64_t>() : nullptr;
+        for (uint32_t k = 0; k < n_tg; k++) {
+            f[k] = pe_sysg_failure{PE_NONE, PE_NONE, PE_NONE, 0u};
+            if (!w || w[k] == ~(uint64_t)0) continue;
+            const uint32_t pos = (uint32_t)(w[k] >> 32), code = (uint32_t)w[k];
+            if (pos >= n) return s->fail(PE_EINTERNAL, fn + ": a first failure out of range");
+            f[k].pos = pos;
+            if (code == pe::kTrOption) {
+                // an eviction Select that gave the node up records nothing
+                // (compute_metrics' kSkipped); the plain walk always has a reason
+                if (!evicting) return s->fail(PE_EINTERNAL, fn + ": an exhausted entry without a dimension");
+                continue;
+            }
+            uint32_t kind = 0, key = PE_NONE;
+            if (!trace_key(s, code, &kind, &key) || kind != PE_METRIC_DIMENSION_EXHAUSTED)
+                return s->fail(PE_EINTERNAL, fn + ": unknown dimension code");
+            f[k].dimension = key;
+            f[k].node_class = MetricAcc::mclass(s, s->visit[pos]);
+        }
+        // the reference memo shadow as the Selects leave it: every node of a
+        // computed class shares a verdict, so the final memo does not depend on
+        // the visiting order and each group walks the list once. Only a
+        // class's first listed node can change an entry (unless the job's
+        // constraints escape the classes, where the job verdict is per node),
+        // so the walk is over those nodes and evaluates no constraint for the
+        // others
+        MetricAcc acc;
+        std::vector<uint32_t> passed, firsts;
+        const std::vector<uint32_t>* order = &s->visit;
+        if (n && !s->job_escaped) {
+            jf_ready(s);
+            std::vector<uint8_t> seen(s->ncls, 0);
+            for (uint32_t r : s->visit) {
+                const uint32_t c = s->jf_cls[r];
+                if (c < seen.size() && !seen[c]) {
+                    seen[c] = 1;
+                    firsts.push_back(r);
+                }
+            }
+            order = &firsts;
+        }
+        for (uint32_t k = 0; k < n_tg && n; k++) {
+            acc.reset();
+            passed.clear();
+            metrics_walk(s, *s->tgs[tgs[k]], *order, 0, (uint32_t)order->size(), acc, passed);
+        }
+        s->sysg_dev_group = dev_group;
+        s->sysg_met_valid = true;
+        s->metrics_valid = false;   // no "last Select"
+    }
     if (out_score && n) {
         const uint8_t* h = s->h_sysg_out.as<uint8_t>();
         std::memcpy(out_status2, h, (E + 3) / 4);
@@ -10202,6 +10317,27 @@ int pe_system_place_groups_preempt(pe_stack* s, const uint32_t* tg_indices, uint
     if (!s) return PE_EINVAL;
     s->pre_overflow.clear();
     return system_place_groups_impl(s, tg_indices, n_tg, out_score, out_status2, counts, placed, true);
+}
+
+int pe_system_place_groups_metrics(pe_stack* s, const uint32_t* tg_indices, uint32_t n_tg, double* out_score,
+                                   uint8_t* out_status2, uint32_t* counts, uint32_t* placed) {
+    PE_FLUSH_RESET(s);
+    if (!s) return PE_EINVAL;
+    s->pre_overflow.clear();
+    return system_place_groups_impl(s, tg_indices, n_tg, out_score, out_status2, counts, placed, true, true);
+}
+
+int pe_system_groups_metrics(const pe_stack* s, const pe_sysg_failure** failures, int32_t* dev_group,
+                             const double** dev_binpack, const double** dev_devices, uint32_t* n) {
+    if (!s || !failures || !dev_group || !dev_binpack || !dev_devices || !n) return PE_EINVAL;
+    if (!s->sysg_met_valid || !s->sysg_valid || !s->h_sysg_fail.p) return PE_ESTATE;
+    *failures = s->h_sysg_fail.as<pe_sysg_failure>();
+    *n = s->sysg_n;
+    *dev_group = s->sysg_n ? s->sysg_dev_group : -1;
+    const double* named = *dev_group >= 0 ? s->h_sysg_named.as<double>() : nullptr;
+    *dev_binpack = named;
+    *dev_devices = named ? named + s->sysg_n : nullptr;
+    return PE_OK;
 }
 
 int pe_system_groups_preempted(const pe_stack* s, const uint32_t** entries, const uint32_t** off,

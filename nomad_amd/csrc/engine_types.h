@@ -561,6 +561,23 @@ struct SysStopArgs {
     uint32_t* n_stopped;              // [1]
 };
 
+// pe_system_place_groups_metrics: what the AllocMetric forms of
+// the walks (k_system_groups_metrics, k_system_groups_evict<W, true>) return
+// beside the outcomes.
+constexpr uint32_t kSysFirstLds = 256;        // listed groups whose first-failure word the eviction walk reduces in LDS
+struct SysMetricsArgs {
+    // [n_tg] the first finally exhausted entry of each listed group in walk
+    // order: list position << 32 | kTr* code of that Select's dimension (0: an
+    // eviction Select that was skipped and records none), reduced with min;
+    // all ones: none. Kept across the chunk launches and the wider rounds.
+    unsigned long long* first;
+    int32_t dev_group;                // the listed group whose ask scores devices (Ask::dev_tw != 0), or -1
+    uint32_t n_list;
+    // dev_group's placed entries by list position: binpack at [pos], devices
+    // at [n_list + pos]; filled with NaN before the walk. Null when dev_group < 0
+    double* dev_named;
+};
+
 constexpr uint32_t kSysgOverflow = 4u;   // SysEvictArgs::flags beside kEvictUnsup / kEvictWider: the append buffer is full
 
 struct SysEvictArgs {
@@ -580,6 +597,7 @@ struct SysEvictArgs {
     uint32_t* n_app;
     uint32_t app_cap;
     uint32_t* flags;                  // [1] kEvictUnsup | kEvictWider | kSysgOverflow
+    SysMetricsArgs M;                 // read by the metrics form only (k_system_groups_evict<W, true>)
 };
 
 }  // namespace pe

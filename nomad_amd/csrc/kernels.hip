@@ -483,6 +483,73 @@ __device__ __forceinline__ uint32_t trace_rec(const TraceSrc& r, uint32_t i) {
     return lo;
 }
 
+// Why BinPack exhausts the (dk+1)-th placement of the group on a loaded node
+// (k_trace's chain, also walked by the multi-group system pass on a lane's
+// register image). trace_offers: the network offers, then
+// AssignDevice, in BinPack's order; the network columns of `in` already hold
+// the dk earlier placements. kTrOption: the offers succeed.
+__device__ __forceinline__ uint32_t trace_offers(const TgTables& t, const Ask& a, uint32_t row, const NodeIn& in,
+                                                 uint32_t dk) {
+    const NodeRec& r = in.r;
+    uint32_t code = kTrOption;
+    if (t.static_gate &&                                           // AssignPorts static ports (network.go:317-363)
+        (t.static_gate[row] == 0u || in.coll_tg + dk + 1u != t.static_gate[row]))
+        code = kTrStaticPort;
+    if (code == kTrOption && (a.tg_dyn > 0 || a.has_task_net)) {   // rank.go:231-295
+        int32_t dyn = r.used_dyn;
+        if (a.tg_dyn > 0) {
+            if (t.alias_ok && !t.alias_ok[row]) code = kTrNoAddr;
+            else if (kDynPortCapacity - dyn - a.static_dyn < 1) code = kTrDynPorts;
+            dyn += a.tg_dyn + a.static_dyn;
+        }
+        const uint32_t md_lim = (code == kTrOption && a.has_task_net && t.md) ? t.md[row].lim : ~0u;
+        if (md_lim != ~0u) {   // a multi-device node: the host's outcome of the first refused placement
+            if (in.coll_tg + dk >= md_lim) code = t.md[row].code;
+        } else if (code == kTrOption && a.has_task_net) {
+            if (r.avail_mbits < 0) code = kTrNoNetworks;
+            else if (r.used_mbits + a.task_mbits > r.avail_mbits) code = kTrBandwidth;
+            else if (t.task_gate && (t.task_gate[row] == 0u || in.coll_tg + dk + 1u != t.task_gate[row])) code = kTrTaskStatic;
+            else if (kDynPortCapacity - dyn < a.task_dyn) code = kTrTaskDyn;
+        }
+    }
+    if (code == kTrOption && a.n_dev > 0) {                         // AssignDevice errors (device.go:32-131)
+        const DevClass& dc = t.dev_cls[r.cls];
+        uint32_t free = dk ? dev_after(a, dc, in.dev_free, dk) : in.dev_free;
+        if (dc.n_groups == 0) code = kTrDevNone;
+        for (int q = 0; q < kMaxDevReq && code == kTrOption; q++) {
+            if (q >= a.n_dev) break;
+            const uint32_t cnt = (uint32_t)a.dev_cnt[q];
+            if (cnt == 0) { code = kTrDevZero; break; }
+            int best = -1;
+            double best_score = 0.0;
+            for (int g = 0; g < kMaxDevGroups; g++) {
+                if (g >= (int)dc.n_groups) break;
+                const uint32_t f = (free >> (8 * g)) & 255u;
+                if (f < cnt || !((dc.match[q] >> g) & 1u)) continue;
+                const double sc = dc.choice[q][g];
+                if (best >= 0 && sc < best_score) continue;
+                best = g;
+                best_score = sc;
+            }
+            if (best < 0) { code = kTrDevNoMatch; break; }
+            free -= cnt << (8 * best);
+        }
+    }
+    return code;
+}
+
+// trace_fit: AllocsFit's dimension in its Superset order (core_out: a chosen
+// reserved core outside the available set). kTrOption: the placement fits.
+__device__ __forceinline__ uint32_t trace_fit(const NodeSoA& s, const Ask& a, uint32_t row, const NodeRec& r, uint32_t dk,
+                                              bool core_out) {
+    const int64_t k1 = (int64_t)dk + 1;
+    if (r.cap_cpu < r.used_cpu + k1 * ask_cpu(s, a, row)) return kTrCpu;
+    if (core_out) return kTrCores;
+    if (r.cap_mem < r.used_mem + k1 * a.mem) return kTrMemory;
+    if (r.cap_disk < r.used_disk + k1 * a.disk) return kTrDisk;
+    return kTrOption;
+}
+
 // dk (TraceSrc): placements of this task group on the row that the state
 // lacks (a speculative run's earlier Selects, traced against the run's
 // starting state; no distinct_property sets then), applied as status_loaded
@@ -515,66 +582,18 @@ __global__ void k_trace(NodeSoA s, TgTables t, Ask a, TraceSrc src, uint32_t n, 
             if (v == kMissing || t.pset_counts[p][v] >= t.pset_allowed[p]) code = kTrDistinctProp | ((uint32_t)p << 8);
         }
     }
-    if (code == kTrOption && t.static_gate &&                      // AssignPorts static ports (network.go:317-363)
-        (t.static_gate[row] == 0u || in.coll_tg + dk + 1u != t.static_gate[row]))
-        code = kTrStaticPort;
     if (dk) {   // the earlier placements' network use
         r.used_dyn += (int32_t)dk * a.commit_dyn;
         r.used_mbits += (int32_t)dk * a.commit_mbits;
     }
-    if (code == kTrOption && (a.tg_dyn > 0 || a.has_task_net)) {   // rank.go:231-295
-        int32_t dyn = r.used_dyn;
-        if (a.tg_dyn > 0) {
-            if (t.alias_ok && !t.alias_ok[row]) code = kTrNoAddr;
-            else if (kDynPortCapacity - dyn - a.static_dyn < 1) code = kTrDynPorts;
-            dyn += a.tg_dyn + a.static_dyn;
-        }
-        const uint32_t md_lim = (code == kTrOption && a.has_task_net && t.md) ? t.md[row].lim : ~0u;
-        if (md_lim != ~0u) {   // a multi-device node: the host's outcome of the first refused placement
-            if (in.coll_tg + dk >= md_lim) code = t.md[row].code;
-        } else if (code == kTrOption && a.has_task_net) {
-            if (r.avail_mbits < 0) code = kTrNoNetworks;
-            else if (r.used_mbits + a.task_mbits > r.avail_mbits) code = kTrBandwidth;
-            else if (t.task_gate && (t.task_gate[row] == 0u || in.coll_tg + dk + 1u != t.task_gate[row])) code = kTrTaskStatic;
-            else if (kDynPortCapacity - dyn < a.task_dyn) code = kTrTaskDyn;
-        }
-    }
-    if (code == kTrOption && a.n_dev > 0) {                         // AssignDevice errors (device.go:32-131)
-        const DevClass& dc = t.dev_cls[c];
-        uint32_t free = dk ? dev_after(a, dc, in.dev_free, dk) : in.dev_free;
-        if (dc.n_groups == 0) code = kTrDevNone;
-        for (int q = 0; q < kMaxDevReq && code == kTrOption; q++) {
-            if (q >= a.n_dev) break;
-            const uint32_t cnt = (uint32_t)a.dev_cnt[q];
-            if (cnt == 0) { code = kTrDevZero; break; }
-            int best = -1;
-            double best_score = 0.0;
-            for (int g = 0; g < kMaxDevGroups; g++) {
-                if (g >= (int)dc.n_groups) break;
-                const uint32_t f = (free >> (8 * g)) & 255u;
-                if (f < cnt || !((dc.match[q] >> g) & 1u)) continue;
-                const double sc = dc.choice[q][g];
-                if (best >= 0 && sc < best_score) continue;
-                best = g;
-                best_score = sc;
-            }
-            if (best < 0) { code = kTrDevNoMatch; break; }
-            free -= cnt << (8 * best);
-        }
-    }
+    if (code == kTrOption) code = trace_offers(t, a, row, in, dk);
     bool core_out = false;
     if (code == kTrOption && a.cores > 0) {                         // reserved cores (rank.go:437-466)
         const CoreFit f = core_fit(s.core_rsvable, s.core_used, s.core_avail, s.core_spc, (uint32_t)a.cores, row, dk);
         if (f.status == 1) code = kTrCores;
         core_out = f.status == 2;
     }
-    if (code == kTrOption) {                                        // AllocsFit → Superset order
-        const int64_t k1 = (int64_t)dk + 1;
-        if (r.cap_cpu < r.used_cpu + k1 * ask_cpu(s, a, row)) code = kTrCpu;
-        else if (core_out) code = kTrCores;
-        else if (r.cap_mem < r.used_mem + k1 * a.mem) code = kTrMemory;
-        else if (r.cap_disk < r.used_disk + k1 * a.disk) code = kTrDisk;
-    }
+    if (code == kTrOption) code = trace_fit(s, a, row, r, dk, core_out);
     if (code == kTrOption) {
         ScoreIn si;
         if (dk) {   // status_loaded applies dk itself: the network columns as loaded
@@ -4227,9 +4246,13 @@ __device__ __forceinline__ uint32_t wave_slot(uint32_t* counter) {
 }
 
 // One plain (node, group) step on a lane's register image: k_system_groups'
-// loop body (the same status_loaded / score_into, so the same bits).
+// loop body (the same status_loaded / score_into, so the same bits). With
+// kNamed (the AllocMetric forms) an option's ScoreNode values
+// go to named[0] (binpack) and named[1] (devices, for an ask that scores them)
+// as k_trace gives them: score_into's parts, the same sum in the same order.
+template <bool kNamed = false>
 __device__ __forceinline__ int sysg_plain(const NodeSoA& soa, const SysGroup& G, double log10, uint32_t row, NodeIn& in,
-                                          uint32_t& cj, uint32_t& df, double* score) {
+                                          uint32_t& cj, uint32_t& df, double* score, double* named = nullptr) {
     in.coll_tg = G.tg.coll_tg[row];
     in.feas = G.tg.node_feas ? G.tg.node_feas[row] : 1u;
     in.dev_free = df;
@@ -4239,7 +4262,14 @@ __device__ __forceinline__ int sysg_plain(const NodeSoA& soa, const SysGroup& G,
     if (st == kOption) {
         lookup_scores(G.tg, nullptr, nullptr, row, in.r.cls, &si);
         uint32_t ns;
-        *score = score_into<false>(G.ask, log10, si, nullptr, &ns);
+        if (kNamed) {
+            double parts[PE_MAX_SCORES];
+            *score = score_into<true>(G.ask, log10, si, parts, &ns);
+            named[0] = parts[0];
+            named[1] = ns > 1u ? parts[1] : 0.0;   // (used for an ask with dev_tw != 0: score_head's second part)
+        } else {
+            *score = score_into<false>(G.ask, log10, si, nullptr, &ns);
+        }
         in.r.used_cpu += G.ask.cpu;
         in.r.used_mem += G.ask.mem;
         in.r.used_disk += G.ask.disk;
@@ -4329,8 +4359,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
 // is stored before the call and loaded again after a commit: a lane reads back
 // its own stores only. A node beyond the width commits nothing from that group
 // on: it keeps its resume group, joins the wider list and raises kEvictWider.
-template <int W>
+//
+// kMetrics (DESIGN.md §34, A.M): evict_eval also returns the dimension of a
+// pair that stays exhausted and an option's named scores; plain placements
+// take sysg_plain's named form. Every finally
+// exhausted entry offers pos << 32 | dimension to its group's first-failure
+// word: the lanes of a wave stand at different groups here, so there is no
+// wave-wide reduction; a lane compares with the word in LDS (groups below
+// kSysFirstLds, flushed with one global atomicMin per workgroup and group) and
+// issues the atomicMin only when it would lower it.
+template <int W, bool kMetrics = false>
 __global__ void __launch_bounds__(256) k_system_groups_evict(SysEvictArgs A) {
+    __shared__ unsigned long long first_lds[kMetrics ? kSysFirstLds : 1];
+    const SysMetricsArgs* M = &A.M;
+    if (kMetrics) {
+        for (uint32_t k = threadIdx.x; k < kSysFirstLds; k += blockDim.x) first_lds[k] = ~0ull;
+        __syncthreads();
+    }
     const SystemGroupsArgs& Gx = A.G;
     const uint32_t n = *A.n_stopped;
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -4355,8 +4400,11 @@ __global__ void __launch_bounds__(256) k_system_groups_evict(SysEvictArgs A) {
             if (k != next) continue;
             int st = kExhausted;
             double score = 0.0;
+            double named[7];   // (kMetrics: sysg_plain fills [0..1], evict_eval all seven)
+            uint32_t dim = 0;
             if (!evict) {
-                st = sysg_plain(Gx.soa, Gx.groups[k], Gx.log10, row, in, cj, df, &score);
+                st = sysg_plain<kMetrics>(Gx.soa, Gx.groups[k], Gx.log10, row, in, cj, df, &score,
+                                          kMetrics ? named : nullptr);
                 dirty = dirty || st == kOption;
                 evict = st == kExhausted;
             }
@@ -4366,8 +4414,11 @@ __global__ void __launch_bounds__(256) k_system_groups_evict(SysEvictArgs A) {
                 const PreemptArgs& P = A.pre[k];
                 NodeEval ev;
                 AMask<W> mask = AMask<W>::zero();
-                uint32_t offers = 0, unsup = 0;
-                const int es = evict_eval<false, false, W>(P, row, &ev, &mask, &offers, &unsup, &ws);
+                uint32_t offers = 0, unsup = 0, nflags = 0;
+                const int es = evict_eval<false, false, W>(P, row, &ev, &mask, &offers, &unsup, &ws,
+                                                           kMetrics ? named : nullptr, kMetrics ? &nflags : nullptr,
+                                                           kMetrics ? &dim : nullptr);
+                if (es != kExhausted) dim = 0;   // (a skipped eviction Select records no dimension)
                 if (unsup) {
                     atomicOr(A.flags, unsup);
                     if (unsup == kEvictWider) {
@@ -4396,6 +4447,20 @@ __global__ void __launch_bounds__(256) k_system_groups_evict(SysEvictArgs A) {
                 }
             }
             out[k] = sys_box(st, score);
+            if (kMetrics) {
+                if (st == kOption && (int32_t)k == M->dev_group) {
+                    M->dev_named[pos] = named[0];
+                    M->dev_named[(size_t)M->n_list + pos] = named[1];
+                }
+                if (st == kExhausted) {
+                    const unsigned long long key = ((unsigned long long)pos << 32) | dim;
+                    if (k < kSysFirstLds) {
+                        if (key < first_lds[k]) atomicMin(&first_lds[k], key);
+                    } else if (key < M->first[k]) {
+                        atomicMin(&M->first[k], key);
+                    }
+                }
+            }
             const uint64_t m0 = __ballot(st == kOption), m1 = __ballot(st == kFiltered), m2 = __ballot(st == kExhausted);
             if (lane == (uint32_t)__ffsll((unsigned long long)(m0 | m1 | m2)) - 1u) {
                 if (m0) atomicAdd(&counts[3 * k + 0], (uint32_t)__popcll(m0));
@@ -4407,6 +4472,119 @@ __global__ void __launch_bounds__(256) k_system_groups_evict(SysEvictArgs A) {
         }
         if (dirty) sysg_store(Gx, row, in, df, df0);
     }
+    if (kMetrics) {
+        __syncthreads();
+        for (uint32_t k = threadIdx.x; k < kSysFirstLds && k < Gx.n_tg; k += blockDim.x)
+            if (first_lds[k] != ~0ull) atomicMin(&M->first[k], first_lds[k]);
+    }
+}
+
+// Min of `key` over the wave's 64 lanes; every lane of the wave calls it.
+__device__ __forceinline__ unsigned long long wave_min64(unsigned long long key) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off);
+        key = o < key ? o : key;
+    }
+    return key;
+}
+
+// k_system_groups and k_system_groups_stop (kStop) with AllocMetric on
+// (DESIGN.md §34): the same walk on the same register image, so the same
+// outcomes and FinalScore bits. Beside them
+//  - the named scores of M.dev_group's plain placements, by list position;
+//  - without kStop, the first exhausted entry of each group in walk order: at
+//    the group where the plain fit is exhausted the lane derives the dimension
+//    from its image (trace_offers, trace_fit: what that Select saw after the
+//    earlier groups' placements on the node); the key pos << 32 | code is
+//    reduced with min over the wave, one LDS atomicMin per wave, one global
+//    atomicMin per workgroup and group. In the row-order form pos is
+//    rank_of[i], not the lane's index. With kStop an exhausted plain fit is not
+//    a final outcome and nothing is recorded for it.
+// The grid-stride loop is over whole workgroup-sized blocks of lanes so that
+// the wave reductions run in uniform control flow; a lane without a node
+// (`act` false) walks nothing.
+template <bool kStop>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+k_system_groups_metrics(SystemGroupsArgs A, SysStopArgs S, SysMetricsArgs M) {
+    __shared__ uint32_t cnt[3 * kSysGroupsChunk];
+    __shared__ unsigned long long first[kSysGroupsChunk];
+    if (threadIdx.x < 3 * kSysGroupsChunk) cnt[threadIdx.x] = 0;
+    if (threadIdx.x < kSysGroupsChunk) first[threadIdx.x] = ~0ull;
+    __syncthreads();
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const uint32_t span = A.rank_of ? A.n_rows : A.n_list;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t base = blockIdx.x * blockDim.x; base < span; base += stride) {
+        const uint32_t i = base + threadIdx.x;
+        bool act = i < span;
+        uint32_t row = i, pos = i;
+        if (act) {
+            if (A.rank_of) {
+                pos = A.rank_of[i];
+                act = pos != PE_NONE;
+            } else {
+                row = A.list[i];
+            }
+        }
+        if (kStop && act && A.k0 > 0 && S.resume[i] < A.k0) act = false;   // stopped in an earlier chunk
+        NodeIn in = {};
+        uint32_t cj = 0, df0 = 0;
+        if (act) {
+            in.r = A.soa.rec[row];
+            cj = A.soa.coll_job[row];
+            df0 = A.dev_free ? A.dev_free[row] : 0u;
+        }
+        uint32_t df = df0;
+        bool dirty = false;
+        uint32_t stop_at = A.n_tg;
+        uint64_t* out = A.res + (size_t)i * A.n_tg + A.k0;
+        for (uint32_t kk = 0; kk < A.nk; kk++) {
+            const SysGroup& G = A.groups[A.k0 + kk];
+            int st = -1;   // no outcome: no node, or stopped
+            double score = 0.0, named[2];
+            if (act && stop_at == A.n_tg) {
+                st = sysg_plain<true>(A.soa, G, A.log10, row, in, cj, df, &score, named);
+                if (kStop && st == kExhausted) {
+                    stop_at = A.k0 + kk;
+                    st = -1;
+                }
+            }
+            if (st >= 0) out[kk] = sys_box(st, score);
+            if (st == kOption) {
+                dirty = true;
+                if ((int32_t)(A.k0 + kk) == M.dev_group) {
+                    M.dev_named[pos] = named[0];
+                    M.dev_named[(size_t)M.n_list + pos] = named[1];
+                }
+            }
+            const uint64_t m0 = __ballot(st == kOption), m1 = __ballot(st == kFiltered), m2 = __ballot(st == kExhausted);
+            if (lane == (uint32_t)__ffsll((unsigned long long)(m0 | m1 | m2)) - 1u) {
+                if (m0) atomicAdd(&cnt[3 * kk + 0], (uint32_t)__popcll(m0));
+                if (m1) atomicAdd(&cnt[3 * kk + 1], (uint32_t)__popcll(m1));
+                if (m2) atomicAdd(&cnt[3 * kk + 2], (uint32_t)__popcll(m2));
+            }
+            if (!kStop && m2) {   // wave-uniform
+                unsigned long long key = ~0ull;
+                if (st == kExhausted) {
+                    uint32_t code = trace_offers(G.tg, G.ask, row, in, 0u);
+                    if (code == kTrOption) code = trace_fit(A.soa, G.ask, row, in.r, 0u, false);
+                    key = ((unsigned long long)pos << 32) | code;
+                }
+                key = wave_min64(key);
+                if (lane == 0) atomicMin(&first[kk], key);
+            }
+        }
+        if (kStop && act) {
+            if (A.k0 == 0 || stop_at < A.n_tg) S.resume[i] = stop_at;
+            if (stop_at < A.n_tg) S.stopped[wave_slot(S.n_stopped)] = i;
+        }
+        if (act && dirty) sysg_store(A, row, in, df, df0);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * A.nk && cnt[threadIdx.x])
+        atomicAdd(&A.counts[(size_t)(blockIdx.x % kPlacedSlots) * 3u * A.n_tg + 3u * A.k0 + threadIdx.x], cnt[threadIdx.x]);
+    if (!kStop && threadIdx.x < A.nk && first[threadIdx.x] != ~0ull)
+        atomicMin(&M.first[A.k0 + threadIdx.x], first[threadIdx.x]);
 }
 
 // The outcome of entry e (position-major, group-minor) from res: 0 placed,
@@ -4699,6 +4877,47 @@ hipError_t pe_launch_system_groups_evict(const pe::SysEvictArgs* a, uint32_t wor
     if (words == 1u) hipLaunchKernelGGL(pe::k_system_groups_evict<1>, dim3(blocks), dim3(256), 0, st, *a);
     else if (words == 8u) hipLaunchKernelGGL(pe::k_system_groups_evict<8>, dim3(blocks), dim3(256), 0, st, *a);
     else if (words == 32u) hipLaunchKernelGGL(pe::k_system_groups_evict<32>, dim3(blocks), dim3(256), 0, st, *a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// The AllocMetric forms, chunked and sized as the plain ones.
+// `s` null: the walk to the end (k_system_groups' form), else the stopping form.
+hipError_t pe_launch_system_groups_metrics(const pe::SystemGroupsArgs* a, const pe::SysStopArgs* s,
+                                           const pe::SysMetricsArgs* m, hipStream_t st) {
+    const uint32_t span = a->rank_of ? a->n_rows : a->n_list;
+    if (!span || !a->n_tg) return hipSuccess;
+    if (!m->first || (m->dev_group >= 0 && !m->dev_named) || m->dev_group >= (int32_t)a->n_tg || m->n_list != a->n_list)
+        return hipErrorInvalidValue;
+    if (s && (!s->resume || !s->stopped || !s->n_stopped)) return hipErrorInvalidValue;
+    uint32_t blocks = (span + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    pe::SystemGroupsArgs c = *a;
+    const pe::SysStopArgs none{nullptr, nullptr, nullptr};
+    for (uint32_t k0 = 0; k0 < a->n_tg; k0 += pe::kSysGroupsChunk) {
+        c.k0 = k0;
+        c.nk = a->n_tg - k0 < pe::kSysGroupsChunk ? a->n_tg - k0 : pe::kSysGroupsChunk;
+        if (s) hipLaunchKernelGGL(pe::k_system_groups_metrics<true>, dim3(blocks), dim3(256), 0, st, c, *s, *m);
+        else hipLaunchKernelGGL(pe::k_system_groups_metrics<false>, dim3(blocks), dim3(256), 0, st, c, none, *m);
+    }
+    return hipGetLastError();
+}
+
+hipError_t pe_launch_system_groups_evict_metrics(const pe::SysEvictArgs* a, uint32_t words, uint32_t max_lanes,
+                                                 hipStream_t st) {
+    const pe::SysMetricsArgs* m = &a->M;
+    if (!max_lanes || !a->G.n_tg) return hipSuccess;
+    if (!a->pre || !a->resume || !a->stopped || !a->n_stopped || !a->wider || !a->n_wider || !a->app || !a->n_app ||
+        !a->flags || !a->preempted || !a->pcount || !a->dev_free_all)
+        return hipErrorInvalidValue;
+    if (!m->first || (m->dev_group >= 0 && !m->dev_named) || m->dev_group >= (int32_t)a->G.n_tg ||
+        m->n_list != a->G.n_list)
+        return hipErrorInvalidValue;
+    uint32_t blocks = (max_lanes + 255) / 256;
+    if (blocks > 1024) blocks = 1024;   // grid-stride beyond
+    if (words == 1u) hipLaunchKernelGGL((pe::k_system_groups_evict<1, true>), dim3(blocks), dim3(256), 0, st, *a);
+    else if (words == 8u) hipLaunchKernelGGL((pe::k_system_groups_evict<8, true>), dim3(blocks), dim3(256), 0, st, *a);
+    else if (words == 32u) hipLaunchKernelGGL((pe::k_system_groups_evict<32, true>), dim3(blocks), dim3(256), 0, st, *a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

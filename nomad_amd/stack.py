@@ -86,6 +86,14 @@ def load_engine():
             lib.pe_system_groups_preempted.restype = C.c_int
             lib.pe_system_groups_preempted.argtypes = [C.c_void_p, C.POINTER(abi.u32p), C.POINTER(abi.u32p),
                                                        C.POINTER(abi.u32p), abi.u32p]
+        if hasattr(lib, "pe_system_place_groups_metrics"):
+            lib.pe_system_place_groups_metrics.restype = C.c_int
+            lib.pe_system_place_groups_metrics.argtypes = [C.c_void_p, abi.u32p, C.c_uint32, abi.f64p, abi.u8p,
+                                                           abi.u32p, abi.u32p]
+            lib.pe_system_groups_metrics.restype = C.c_int
+            lib.pe_system_groups_metrics.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.pe_sysg_failure)),
+                                                     C.POINTER(C.c_int32), C.POINTER(abi.f64p), C.POINTER(abi.f64p),
+                                                     abi.u32p]
         lib.pe_speculation_stats.restype = C.c_int
         lib.pe_speculation_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.pe_comm_unique_id.restype = C.c_int
@@ -276,6 +284,7 @@ class _Stack:
             fn.restype = C.c_int
             fn.argtypes = [C.c_void_p, C.c_int]
             self._check(fn(self._h, int(on)))
+            self._metrics_on = bool(on)
 
     def LastMetrics(self) -> Dict[str, Dict[str, int]]:
         """The last Select's maps: {"ClassFiltered": {...}, "ConstraintFiltered": {...},
@@ -612,6 +621,55 @@ class _Stack:
         device group twice, several task networks)."""
         return self._system_place_groups(tgs, fallback, staged, "system_place_groups_preempt")
 
+    def SystemPlaceGroupsMetrics(self, tgs, fallback: bool = True, staged: bool = False):
+        """SystemPlaceGroupsPreempt for a caller that keeps AllocMetric
+        (pe_system_place_groups_metrics): it runs with EnableMetrics on, on a
+        preempting or a non-preempting system stack. Returns
+        SystemPlaceGroupsPreempt's five results and a `metrics` dict with what
+        computePlacements keeps of the Selects' maps:
+        {"failed": {k: (pos, dimension, node class)}, "scores": {(pos, k):
+        {"binpack": x, "devices": y}}}. `failed[k]` is the first exhausted
+        Select of listed group k in walk order, with the one key of its
+        DimensionExhausted and of its ClassExhausted (None where that Select
+        recorded none); a group without an exhausted entry has no item.
+        `scores` holds the named scores of the placed entries of the one group
+        whose ask scores devices (the other groups' only score is "binpack",
+        equal to the FinalScore). With metrics off the call is
+        SystemPlaceGroupsPreempt and both maps are empty. The fallback is
+        system_place_groups_metrics_by_select."""
+        return self._system_place_groups(tgs, fallback, staged, "system_place_groups_metrics")
+
+    def SystemGroupsMetrics(self, n_tg: int) -> Dict:
+        """pe_system_groups_metrics of the last SystemPlaceGroupsMetrics over
+        `n_tg` groups, in its `metrics` shape. EngineError(PE_ESTATE) when that
+        call ran with metrics off or a pe_system_place* call came since."""
+        fl = C.POINTER(abi.pe_sysg_failure)()
+        dg, bp, dv, nn = C.c_int32(-1), abi.f64p(), abi.f64p(), C.c_uint32(0)
+        self._check(self._lib.pe_system_groups_metrics(self._h, C.byref(fl), C.byref(dg), C.byref(bp), C.byref(dv),
+                                                       C.byref(nn)))
+        cache = getattr(self, "_mkey_cache", None)
+        if cache is None:
+            cache = self._mkey_cache = {}
+
+        def text(key):
+            if key == abi.PE_NONE:
+                return None
+            if key not in cache:
+                cache[key] = self.MetricString(key)
+            return cache[key]
+
+        failed, scores = {}, {}
+        for k in range(n_tg):
+            f = fl[k]
+            if f.pos != abi.PE_NONE:
+                failed[k] = (int(f.pos), text(f.dimension), text(f.node_class))
+        if dg.value >= 0 and nn.value:
+            b = np.ctypeslib.as_array(bp, shape=(nn.value,))
+            d = np.ctypeslib.as_array(dv, shape=(nn.value,))
+            for pos in np.flatnonzero(~np.isnan(b)):
+                scores[(int(pos), int(dg.value))] = {"binpack": float(b[pos]), "devices": float(d[pos])}
+        return {"failed": failed, "scores": scores}
+
     def _system_place_groups(self, tgs, fallback, staged, name):
         idx = [self._tg_index(t) for t in tgs]
         n, G = len(self._visit), len(idx)
@@ -643,13 +701,17 @@ class _Stack:
         except Unsupported:
             if not fallback:
                 raise
+            if name == "system_place_groups_metrics":
+                if getattr(self, "_metrics_on", False):
+                    return system_place_groups_metrics_by_select(self, idx)
+                return system_place_groups_preempt_by_select(self, idx) + ({"failed": {}, "scores": {}},)
             return system_place_groups_preempt_by_select(self, idx)
         p = placed.value
         status = unpack_status2(packed, E)
         score = np.full(E, np.nan)
         score[status == 0] = dense[:p]
         preempted = {}
-        if name == "system_place_groups_preempt":
+        if name != "system_place_groups":
             en, of, al = abi.u32p(), abi.u32p(), abi.u32p()
             ne = C.c_uint32(0)
             self._check(self._lib.pe_system_groups_preempted(self._h, C.byref(en), C.byref(of), C.byref(al),
@@ -658,7 +720,11 @@ class _Stack:
                 offs = np.ctypeslib.as_array(of, shape=(ne.value + 1,)).copy()
                 preempted = preempted_from_csr(np.ctypeslib.as_array(en, shape=(ne.value,)).copy(), offs,
                                                np.ctypeslib.as_array(al, shape=(int(offs[-1]),)).copy(), G)
-        return score.reshape(n, G), status.reshape(n, G), counts.reshape(G, 3).astype(np.uint32), p, preempted
+        out = (score.reshape(n, G), status.reshape(n, G), counts.reshape(G, 3).astype(np.uint32), p, preempted)
+        if name == "system_place_groups_metrics":
+            on = getattr(self, "_metrics_on", False)
+            out += (self.SystemGroupsMetrics(G) if on else {"failed": {}, "scores": {}},)
+        return out
 
 
 def pack_status2(status) -> np.ndarray:
@@ -730,6 +796,48 @@ def system_place_groups_preempt_by_select(stack, tgs):
             counts[k, status[pos, k]] += 1
     stack.SetNodes(rows)
     return score, status, counts, int(counts[:, 0].sum()), preempted
+
+
+def system_place_groups_metrics_by_select(stack, tgs):
+    """system_place_groups_preempt_by_select's loop on a stack with
+    EnableMetrics on (the engine's or the oracle's), keeping of each Select's
+    maps what SystemScheduler.computePlacements keeps
+    (scheduler_system.go:311-382): after a group's first exhausted Select the
+    one key of DimensionExhausted and of ClassExhausted, after a placed one the
+    node's ScoreMetaData scores. Returns SystemPlaceGroupsMetrics' shape; here
+    `scores` has an item for every placed entry."""
+    rows = np.array(stack._visit, dtype=np.uint32, copy=True)
+    n, G = len(rows), len(tgs)
+    score = np.full((n, G), np.nan)
+    status = np.zeros((n, G), dtype=np.uint8)
+    counts = np.zeros((G, 3), dtype=np.uint32)
+    preempted, failed, scores = {}, {}, {}
+
+    def only(m):
+        assert len(m) <= 1, m
+        return next(iter(m), None)
+
+    for pos in range(n):
+        one = rows[pos:pos + 1]
+        for k, tg in enumerate(tgs):
+            stack.SetNodes(one)
+            r = stack.SelectRaw(tg)
+            if r.row >= 0:
+                meta = stack.LastMetrics()["ScoreMetaData"]
+                assert len(meta) == 1, meta
+                scores[(pos, k)] = dict(meta[0][2])
+                stack.Commit(tg, r.row, r.preempted)
+                score[pos, k] = r.final_score
+                if len(r.preempted):
+                    preempted[(pos, k)] = sorted(int(a) for a in r.preempted)
+            else:
+                status[pos, k] = 1 if r.nodes_filtered else 2
+                if status[pos, k] == 2 and k not in failed:
+                    m = stack.LastMetrics()
+                    failed[k] = (pos, only(m["DimensionExhausted"]), only(m["ClassExhausted"]))
+            counts[k, status[pos, k]] += 1
+    stack.SetNodes(rows)
+    return score, status, counts, int(counts[:, 0].sum()), preempted, {"failed": failed, "scores": scores}
 
 
 def inplace_update_by_select(stack, tg, allocs: Sequence[int]):
