@@ -524,6 +524,37 @@ static Tunables read_tunables() {
     return t;
 }
 
+// What the pe_system_place_groups* calls keep: their buffers (reused from call
+// to call) and the last call's results as the accessors hand them out.
+struct SysGroupsState {
+    // the groups' tables, the outcomes by (node, group), the packed result
+    // [outcome bytes | dense scores], the tile counts and the counter slots;
+    // the staged result and the mapped header words (placed, then 3 counters
+    // per group)
+    DevMem d_groups, d_res, d_out, d_tiles, d_counts;
+    PinnedMem h_out, h_hdr;
+    std::vector<uint32_t> counts;
+    uint32_t n = 0, ntg = 0, placed = 0;
+    bool valid = false;                    // pe_system_groups_results
+    const void* counts_zeroed = nullptr;   // the counter block k_sysg_scan last left zero (null: unknown)
+    // pe_system_place_groups_preempt: the resume groups and the two lane
+    // lists of the eviction walk, its control words ([0] / [1] the lists'
+    // counts, [2] appended records, [3] flags), the append buffer; their
+    // staging, and the preempted lists as a CSR [entries | off | allocs]
+    DevMem d_resume, d_lanes, d_ctl, d_app;
+    PinnedMem h_ctl, h_app, h_csr;
+    uint32_t pre_entries = 0;
+    size_t pre_allocs = 0;
+    bool pre_valid = false;                // pe_system_groups_preempted
+    // pe_system_place_groups_metrics: the first-failure words and the device
+    // group's named scores on the device; in staging the failures as the
+    // caller reads them and the two named arrays ([n] binpack, [n] devices)
+    DevMem d_first, d_named;
+    PinnedMem h_first, h_fail, h_named;
+    int32_t dev_group = -1;
+    bool met_valid = false;                // pe_system_groups_metrics
+};
+
 struct pe_stack {
     pe_config cfg{};
     Tunables tun;                      // the environment switches, as read at create
@@ -913,32 +944,7 @@ struct pe_stack {
     // results [records | outcomes] with their page-locked staging
     DevMem d_inplace_upd, d_inplace_off, d_inplace_out;
     PinnedMem h_inplace_out;
-    // pe_system_place_groups: the groups' tables, the outcomes by (node,
-    // group), the packed result [outcome bytes | dense scores], the tile
-    // counts and the counter slots; the staged result and the mapped header
-    // words (placed, then 3 counters per group)
-    DevMem d_sysg_groups, d_sysg_res, d_sysg_out, d_sysg_tiles, d_sysg_counts;
-    PinnedMem h_sysg_out, h_sysg_hdr;
-    std::vector<uint32_t> sysg_counts;
-    uint32_t sysg_n = 0, sysg_ntg = 0, sysg_placed = 0;
-    bool sysg_valid = false;
-    const void* sysg_counts_zeroed = nullptr;   // the counter block k_sysg_scan last left zero (null: unknown)
-    // pe_system_place_groups_preempt: the resume groups and the two lane
-    // lists of the eviction walk, its control words ([0] / [1] the lists'
-    // counts, [2] appended records, [3] flags), the append buffer; their
-    // staging, and the preempted lists as a CSR [entries | off | allocs]
-    DevMem d_sysg_resume, d_sysg_lanes, d_sysg_ctl, d_sysg_app;
-    PinnedMem h_sysg_ctl, h_sysg_app, h_sysg_csr;
-    uint32_t sysg_pre_entries = 0;
-    size_t sysg_pre_allocs = 0;
-    bool sysg_pre_valid = false;
-    // pe_system_place_groups_metrics: the first-failure words and the device
-    // group's named scores on the device; in staging the failures as the
-    // caller reads them and the two named arrays ([n] binpack, [n] devices)
-    DevMem d_sysg_first, d_sysg_named;
-    PinnedMem h_sysg_first, h_sysg_fail, h_sysg_named;
-    int32_t sysg_dev_group = -1;
-    bool sysg_met_valid = false;
+    SysGroupsState sysg;   // pe_system_place_groups*: buffers, and what the accessors read
     bool stopped(uint32_t ai) const { return ai < stop_count.size() && stop_count[ai] > 0; }
 
     // multi-GPU handle (pe_comm_init): an RCCL communicator over the ranks'
@@ -8900,8 +8906,8 @@ static int system_place_impl(pe_stack* s, uint32_t tgi, double* out_score, uint8
         if (frc) return frc;
     }
     if (s->cfg.stack_kind != PE_STACK_SYSTEM) return s->fail(PE_ESTATE, "pe_system_place needs a system stack");
-    s->sysg_pre_valid = false;   // (pe_system_groups_preempted: until the next pe_system_place* call)
-    s->sysg_met_valid = false;   // (pe_system_groups_metrics likewise)
+    s->sysg.pre_valid = false;   // (pe_system_groups_preempted: until the next pe_system_place* call)
+    s->sysg.met_valid = false;   // (pe_system_groups_metrics likewise)
     s->gen++;
     HIP_TRY(s, hipSetDevice(s->device));
     // every node appears once (checked by SetNodes): the single-node Selects are independent
@@ -9787,31 +9793,41 @@ int pe_system_place(pe_stack* s, uint32_t tgi, double* out_score, uint8_t* out_s
     return rc;
 }
 
-// SystemScheduler.computePlacements' loop over (node, task group) in one pass
-// (DESIGN.md §32): results and state equal those of pe_system_place of each
-// listed group in turn. Everything that can refuse the call is checked before
-// anything changes; then system_place_impl's order of work with one upload,
-// the kernels and one wait, and the host mirrors group after group.
-//
-// `pre_call`: pe_system_place_groups_preempt (DESIGN.md §33). On a preempting
-// stack the pass stops a node at its first exhausted group
-// (k_system_groups_stop) and the eviction walk (k_system_groups_evict) takes
-// the stopped nodes from there, BinPack with evict where the plain fit is
-// exhausted; the preempted allocs of every evicting entry are kept as a CSR
-// (pe_system_groups_preempted). Results and state equal those of
-// pe_system_place of each listed group in turn on the preempting stack.
-//
-// `met_call`: pe_system_place_groups_metrics (DESIGN.md §34), the `pre_call`
-// form that runs with AllocMetric on. The walks' metrics forms return each
-// group's first exhausted entry with its dimension and the device group's
-// named scores (pe_system_groups_metrics); the reference memo advances group
-// after group.
-static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n_tg, double* out_score,
-                                    uint8_t* out_status2, uint32_t* counts, uint32_t* placed, bool pre_call,
-                                    bool met_call = false) {
-    const std::string fn = met_call ? "pe_system_place_groups_metrics"
-                                    : (pre_call ? "pe_system_place_groups_preempt" : "pe_system_place_groups");
-    if (placed) *placed = 0;
+// One pe_system_place_groups* call: what its stages share.
+struct SysEvicted { uint32_t e, words; size_t at; };   // an evicting entry, its width, its mask words in ev_masks
+struct SysGroupsCall {
+    std::string fn;                    // the entry point's name, for the refusal texts
+    const uint32_t* tgs = nullptr;     // the listed groups
+    uint32_t n_tg = 0;
+    bool pre_call = false, met_call = false;   // which entry point
+    bool evicting = false, metrics = false;    // what the stack makes of it
+    uint32_t n = 0;                    // listed nodes
+    size_t E = 0;                      // entries, n * n_tg
+    size_t sb = 0;                     // outcome bytes, the scores 8-byte aligned behind them
+    uint32_t p = 0;                    // placed entries
+    int32_t dev_group = -1;            // (metrics) the listed group whose ask scores devices
+    bool by_row = false;               // the row-order form
+    uint32_t lanes = 0;                // lanes of the walks: snapshot rows in the row-order form, else n
+    uint32_t words = 0;                // the eviction width of the last walk
+    size_t app_cap = 0;                // records the append buffer holds
+    uint32_t* hdr = nullptr;           // the mapped header words: placed, then 3 counters per group
+    uint32_t* ctl = nullptr;           // the eviction walk's control words on the device
+    pe::SystemGroupsArgs A;
+    pe::SysMetricsArgs M;
+    pe::SysEvictArgs V;
+    pe::SysCompactArgs Cx;
+    // the evicting entries with their preempted sets: (entry, width, mask words)
+    std::vector<SysEvicted> evicted;
+    std::vector<uint32_t> ev_masks;
+};
+
+// Everything that can refuse the call, checked before anything changes.
+static int sysg_check(pe_stack* s, const SysGroupsCall& c, const double* out_score, const uint8_t* out_status2,
+                      const uint32_t* counts) {
+    const std::string& fn = c.fn;
+    const uint32_t* tgs = c.tgs;
+    const uint32_t n_tg = c.n_tg;
+    const bool pre_call = c.pre_call, met_call = c.met_call;
     if (n_tg == 0 || !tgs) return s->fail(PE_EINVAL, fn + ": no task group listed");
     if ((!out_score) != (!out_status2) || (!out_score) != (!counts))
         return s->fail(PE_EINVAL, fn + ": the output arrays are all null or all set");
@@ -9833,9 +9849,8 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
     else if (s->cfg.preempt && !pre_call) why = "preemption is enabled (BinPack evicts)";
     else if (s->metrics_on && !met_call) why = "AllocMetric maps are on (pe_set_metrics)";
     else if (!s->kids.empty()) why = "a handle over several devices";
-    for (auto& c : s->job_constraints)
-        if (!why && c.op == "distinct_property") why = "distinct_property";
-    const bool metrics = met_call && s->metrics_on;
+    for (auto& jc : s->job_constraints)
+        if (!why && jc.op == "distinct_property") why = "distinct_property";
     for (uint32_t k = 0; k < n_tg && !why; k++) {
         const TgPlan& g = *s->tgs[tgs[k]];
         if (!g.distinct_props.empty()) why = "distinct_property";
@@ -9848,9 +9863,8 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
     for (uint32_t k = 0; k < n_tg; k++)
         if (!s->tgs[tgs[k]]->unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->tgs[tgs[k]]->unsupported);
     if (!s->cores_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->cores_unsupported);
-    const bool evicting = pre_call && s->cfg.preempt;
     plan_settle(s);   // (the deferred entries written out: nothing a caller can observe)
-    if (evicting) {
+    if (c.evicting) {
         // a candidate whose max_parallel penalty reads the plan's preemption
         // counts (preemption.go:220-240): other nodes grow them, the nodes are
         // then ordered and node-major differs from group-major
@@ -9887,7 +9901,15 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
         }
         if (beyond) return s->fail(PE_EUNSUPPORTED, fn + ": a node beyond the widest eviction width");
     }
+    return PE_OK;
+}
 
+// The accepted call begins: the class memos, the call's sizes, and the last
+// call's results are no longer valid.
+static int sysg_begin(pe_stack* s, SysGroupsCall& c) {
+    const std::string& fn = c.fn;
+    const uint32_t* tgs = c.tgs;
+    const uint32_t n_tg = c.n_tg;
     {
         const int frc = spec_flush(s);
         if (frc) return frc;
@@ -9900,406 +9922,501 @@ static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n
         if (g.psets.size() > (size_t)g.n_spread || g.md_on)
             return s->fail(PE_EUNSUPPORTED, fn + ": property sets or multi-device nodes");
     }
-    const uint32_t n = (uint32_t)s->visit.size();
-    const size_t E = (size_t)n * n_tg;
-    if (E >= (size_t(1) << 31)) return s->fail(PE_EUNSUPPORTED, fn + ": more than 2^31 entries");
-    s->sysg_valid = false;
-    s->sysg_pre_valid = false;
-    s->sysg_met_valid = false;
-    s->sysg_counts.assign(3 * (size_t)n_tg, 0);
-    const size_t sb = ((E + 3) / 4 + 7) & ~(size_t)7;   // outcome bytes, the scores 8-byte aligned behind them
-    uint32_t p = 0;
+    c.n = (uint32_t)s->visit.size();
+    c.E = (size_t)c.n * n_tg;
+    if (c.E >= (size_t(1) << 31)) return s->fail(PE_EUNSUPPORTED, fn + ": more than 2^31 entries");
+    s->sysg.valid = false;
+    s->sysg.pre_valid = false;
+    s->sysg.met_valid = false;
+    s->sysg.counts.assign(3 * (size_t)n_tg, 0);
+    c.sb = ((c.E + 3) / 4 + 7) & ~(size_t)7;
+    for (uint32_t k = 0; k < n_tg && c.metrics; k++)
+        if (ask_for(s, *s->tgs[tgs[k]]).dev_tw != 0.0) c.dev_group = (int32_t)k;
+    return PE_OK;
+}
+
+// The device pass, before the timed work: one upload, the buffers and their
+// fills, the kernels' arguments.
+static int sysg_setup(pe_stack* s, SysGroupsCall& c) {
+    SysGroupsState& y = s->sysg;
+    const uint32_t n = c.n, n_tg = c.n_tg;
+    const size_t E = c.E, sb = c.sb;
+    // one upload: the groups' tables and, on a preempting stack, evict_eval's view of each behind them
+    const size_t pre_off = (sizeof(pe::SysGroup) * n_tg + 15) & ~(size_t)15;
+    std::vector<uint8_t> blob(c.evicting ? pre_off + sizeof(pe::PreemptArgs) * n_tg : sizeof(pe::SysGroup) * n_tg);
     bool any_dev = false;
-    int32_t dev_group = -1;   // (metrics) the listed group whose ask scores devices
-    for (uint32_t k = 0; k < n_tg && metrics; k++)
-        if (ask_for(s, *s->tgs[tgs[k]]).dev_tw != 0.0) dev_group = (int32_t)k;
-    // the evicting entries with their preempted sets: (entry, width, mask words)
-    struct Evicted { uint32_t e, words; size_t at; };
-    std::vector<Evicted> evicted;
-    std::vector<uint32_t> ev_masks;
-    if (n) {
-        // one upload: the groups' tables and, on a preempting stack, evict_eval's view of each behind them
-        const size_t pre_off = (sizeof(pe::SysGroup) * n_tg + 15) & ~(size_t)15;
-        std::vector<uint8_t> blob(evicting ? pre_off + sizeof(pe::PreemptArgs) * n_tg : sizeof(pe::SysGroup) * n_tg);
-        for (uint32_t k = 0; k < n_tg; k++) {
-            TgPlan& g = *s->tgs[tgs[k]];
-            pe::SysGroup sg;
-            std::memset(&sg, 0, sizeof(sg));
-            sg.tg = tables_of(g);
-            sg.ask = ask_for(s, g);
-            any_dev = any_dev || sg.ask.n_dev > 0;
-            std::memcpy(blob.data() + sizeof(pe::SysGroup) * k, &sg, sizeof(sg));
-            if (evicting) {
-                const pe::PreemptArgs P = preempt_args(s, g);
-                std::memcpy(blob.data() + pre_off + sizeof(pe::PreemptArgs) * k, &P, sizeof(P));
-            }
+    for (uint32_t k = 0; k < n_tg; k++) {
+        TgPlan& g = *s->tgs[c.tgs[k]];
+        pe::SysGroup sg;
+        std::memset(&sg, 0, sizeof(sg));
+        sg.tg = tables_of(g);
+        sg.ask = ask_for(s, g);
+        any_dev = any_dev || sg.ask.n_dev > 0;
+        std::memcpy(blob.data() + sizeof(pe::SysGroup) * k, &sg, sizeof(sg));
+        if (c.evicting) {
+            const pe::PreemptArgs P = preempt_args(s, g);
+            std::memcpy(blob.data() + pre_off + sizeof(pe::PreemptArgs) * k, &P, sizeof(P));
         }
-        HIP_TRY(s, upload_visit(s, s->visit));
-        HIP_TRY(s, upload_s(s, s->d_sysg_groups, blob));
-        const uint32_t nn = (uint32_t)s->nodes.size();
-        const bool by_row = (uint64_t)n * 4 >= nn;   // system_place_impl's threshold
-        const uint32_t n_tiles = (uint32_t)((E + pe::kSysTile - 1) / pe::kSysTile);
-        const size_t cnt_bytes = sizeof(uint32_t) * pe::kPlacedSlots * 3 * (size_t)n_tg;
-        HIP_TRY(s, s->d_sysg_res.ensure(sizeof(uint64_t) * (by_row ? (size_t)nn * n_tg : E)));
-        HIP_TRY(s, s->d_sysg_out.ensure(sb + sizeof(double) * E));
-        HIP_TRY(s, s->h_sysg_out.ensure(sb + sizeof(double) * E));
-        HIP_TRY(s, s->d_sysg_tiles.ensure(sizeof(uint32_t) * n_tiles));
-        if (cnt_bytes > s->d_sysg_counts.bytes) s->sysg_counts_zeroed = nullptr;   // a new block follows
-        HIP_TRY(s, s->d_sysg_counts.ensure(cnt_bytes));
-        HIP_TRY(s, s->h_sysg_hdr.ensure(sizeof(uint32_t) * (1 + 3 * (size_t)n_tg)));
-        uint32_t* hdr = s->h_sysg_hdr.as<uint32_t>();
-        uint32_t* hdr_dev = s->h_sysg_hdr.dev<uint32_t>();
-        if (!hdr_dev) return s->fail(PE_EHIP, fn + ": no device view of the header words");
-        // k_sysg_scan leaves the slots zero: a memset only for a new block or after a failed call
-        if (s->sysg_counts_zeroed != s->d_sysg_counts.p)
-            HIP_TRY(s, hipMemsetAsync(s->d_sysg_counts.p, 0, s->d_sysg_counts.bytes, s->stream));
-        s->sysg_counts_zeroed = nullptr;
-        // AllocMetric on: the first-failure words (all ones: none) and the
-        // device group's named scores (NaN: not placed), filled by the walks
-        pe::SysMetricsArgs M;
-        std::memset(&M, 0, sizeof(M));
-        M.dev_group = -1;
-        if (metrics) {
-            const size_t fb = sizeof(uint64_t) * n_tg, nb = sizeof(double) * 2 * (size_t)n;
-            HIP_TRY(s, s->d_sysg_first.ensure(fb));
-            HIP_TRY(s, s->h_sysg_first.ensure(fb));
-            HIP_TRY(s, hipMemsetAsync(s->d_sysg_first.p, 0xFF, fb, s->stream));
-            M.first = s->d_sysg_first.as<unsigned long long>();
-            M.n_list = n;
-            if (dev_group >= 0) {
-                HIP_TRY(s, s->d_sysg_named.ensure(nb));
-                HIP_TRY(s, s->h_sysg_named.ensure(nb));
-                HIP_TRY(s, hipMemsetAsync(s->d_sysg_named.p, 0xFF, nb, s->stream));
-                M.dev_group = dev_group;
-                M.dev_named = s->d_sysg_named.as<double>();
-            }
+    }
+    HIP_TRY(s, upload_visit(s, s->visit));
+    HIP_TRY(s, upload_s(s, y.d_groups, blob));
+    const uint32_t nn = (uint32_t)s->nodes.size();
+    c.by_row = (uint64_t)n * 4 >= nn;   // system_place_impl's threshold
+    c.lanes = c.by_row ? nn : n;
+    const uint32_t n_tiles = (uint32_t)((E + pe::kSysTile - 1) / pe::kSysTile);
+    const size_t cnt_bytes = sizeof(uint32_t) * pe::kPlacedSlots * 3 * (size_t)n_tg;
+    HIP_TRY(s, y.d_res.ensure(sizeof(uint64_t) * (c.by_row ? (size_t)nn * n_tg : E)));
+    HIP_TRY(s, y.d_out.ensure(sb + sizeof(double) * E));
+    HIP_TRY(s, y.h_out.ensure(sb + sizeof(double) * E));
+    HIP_TRY(s, y.d_tiles.ensure(sizeof(uint32_t) * n_tiles));
+    if (cnt_bytes > y.d_counts.bytes) y.counts_zeroed = nullptr;   // a new block follows
+    HIP_TRY(s, y.d_counts.ensure(cnt_bytes));
+    HIP_TRY(s, y.h_hdr.ensure(sizeof(uint32_t) * (1 + 3 * (size_t)n_tg)));
+    c.hdr = y.h_hdr.as<uint32_t>();
+    uint32_t* hdr_dev = y.h_hdr.dev<uint32_t>();
+    if (!hdr_dev) return s->fail(PE_EHIP, c.fn + ": no device view of the header words");
+    // k_sysg_scan leaves the slots zero: a memset only for a new block or after a failed call
+    if (y.counts_zeroed != y.d_counts.p) HIP_TRY(s, hipMemsetAsync(y.d_counts.p, 0, y.d_counts.bytes, s->stream));
+    y.counts_zeroed = nullptr;
+    // AllocMetric on: the first-failure words (all ones: none) and the
+    // device group's named scores (NaN: not placed), filled by the walks
+    pe::SysMetricsArgs& M = c.M;
+    std::memset(&M, 0, sizeof(M));
+    M.dev_group = -1;
+    if (c.metrics) {
+        const size_t fb = sizeof(uint64_t) * n_tg, nb = sizeof(double) * 2 * (size_t)n;
+        HIP_TRY(s, y.d_first.ensure(fb));
+        HIP_TRY(s, y.h_first.ensure(fb));
+        HIP_TRY(s, hipMemsetAsync(y.d_first.p, 0xFF, fb, s->stream));
+        M.first = y.d_first.as<unsigned long long>();
+        M.n_list = n;
+        if (c.dev_group >= 0) {
+            HIP_TRY(s, y.d_named.ensure(nb));
+            HIP_TRY(s, y.h_named.ensure(nb));
+            HIP_TRY(s, hipMemsetAsync(y.d_named.p, 0xFF, nb, s->stream));
+            M.dev_group = c.dev_group;
+            M.dev_named = y.d_named.as<double>();
         }
-        // the maps' copies, queued with the results' DMA: one wait for all
-        auto queue_maps = [&]() -> hipError_t {
-            if (!metrics) return hipSuccess;
-            hipError_t e = hipMemcpyAsync(s->h_sysg_first.p, s->d_sysg_first.p, sizeof(uint64_t) * n_tg,
-                                          hipMemcpyDeviceToHost, s->stream);
-            if (e == hipSuccess && dev_group >= 0)
-                e = hipMemcpyAsync(s->h_sysg_named.p, s->d_sysg_named.p, sizeof(double) * 2 * (size_t)n,
-                                   hipMemcpyDeviceToHost, s->stream);
-            return e;
-        };
-        pe::SystemGroupsArgs A;
-        std::memset(&A, 0, sizeof(A));
-        A.soa = soa_of(s);
-        A.groups = s->d_sysg_groups.as<pe::SysGroup>();
-        A.n_tg = n_tg;
-        A.list = s->d_visit.as<uint32_t>();
-        A.n_list = n;
-        A.dev_free = any_dev ? s->d_dev_free.as<uint32_t>() : nullptr;
-        A.log10 = s->log10;
-        A.res = s->d_sysg_res.as<uint64_t>();
-        A.counts = s->d_sysg_counts.as<uint32_t>();
-        HIP_TRY(s, hipEventRecord(s->ev0, s->stream));   // the timed device work
-        if (by_row) {
-            HIP_TRY(s, s->d_rank_of.ensure(sizeof(uint32_t) * (size_t)std::max<uint32_t>(nn, 1)));
-            if (!s->rank_of_valid)
-                HIP_TRY(s, pe_launch_rank_of(s->d_visit.as<uint32_t>(), n, s->d_rank_of.as<uint32_t>(), nn, s->stream));
-            s->rank_of_valid = true;
-            A.rank_of = s->d_rank_of.as<uint32_t>();
-            A.n_rows = nn;
-        }
-        // a preempting stack: the stopping form, then the eviction walk over the stopped nodes
-        const uint32_t lanes = by_row ? nn : n;
-        pe::SysEvictArgs V;
-        std::memset(&V, 0, sizeof(V));
-        uint32_t* ctl = nullptr;
+    }
+    pe::SystemGroupsArgs& A = c.A;
+    std::memset(&A, 0, sizeof(A));
+    A.soa = soa_of(s);
+    A.groups = y.d_groups.as<pe::SysGroup>();
+    A.n_tg = n_tg;
+    A.list = s->d_visit.as<uint32_t>();
+    A.n_list = n;
+    A.dev_free = any_dev ? s->d_dev_free.as<uint32_t>() : nullptr;
+    A.log10 = s->log10;
+    A.res = y.d_res.as<uint64_t>();
+    A.counts = y.d_counts.as<uint32_t>();
+    std::memset(&c.V, 0, sizeof(c.V));
+    if (c.evicting) c.V.pre = reinterpret_cast<const pe::PreemptArgs*>(y.d_groups.as<uint8_t>() + pre_off);
+    pe::SysCompactArgs& Cx = c.Cx;
+    std::memset(&Cx, 0, sizeof(Cx));
+    Cx.res = A.res;
+    Cx.list = c.by_row ? A.list : nullptr;
+    Cx.n_tg = n_tg;
+    Cx.n_entries = (uint32_t)E;
+    Cx.n_tiles = n_tiles;
+    Cx.status2 = y.d_out.as<uint8_t>();
+    Cx.tile_off = y.d_tiles.as<uint32_t>();
+    Cx.score = reinterpret_cast<double*>(y.d_out.as<uint8_t>() + sb);
+    Cx.counts = A.counts;
+    Cx.hdr = hdr_dev;
+    return PE_OK;
+}
+
+// The timed device work and its wait: the walk of the listed groups (on a
+// preempting stack the stopping form, then the eviction walk over the stopped
+// nodes), the compaction, the header words.
+static int sysg_launch(pe_stack* s, SysGroupsCall& c) {
+    SysGroupsState& y = s->sysg;
+    pe::SystemGroupsArgs& A = c.A;
+    const uint32_t n = c.n, n_tg = c.n_tg, lanes = c.lanes;
+    const uint32_t nn = (uint32_t)s->nodes.size();
+    HIP_TRY(s, hipEventRecord(s->ev0, s->stream));   // the timed device work
+    if (c.by_row) {
+        HIP_TRY(s, s->d_rank_of.ensure(sizeof(uint32_t) * (size_t)std::max<uint32_t>(nn, 1)));
+        if (!s->rank_of_valid)
+            HIP_TRY(s, pe_launch_rank_of(s->d_visit.as<uint32_t>(), n, s->d_rank_of.as<uint32_t>(), nn, s->stream));
+        s->rank_of_valid = true;
+        A.rank_of = s->d_rank_of.as<uint32_t>();
+        A.n_rows = nn;
+    }
+    const pe::SysMetricsArgs* m = c.metrics ? &c.M : nullptr;
+    if (c.evicting) {
         // the walk starts at the narrowest width that covers all but at most an
         // eighth of the snapshot's nodes (s->evict_words covers them all): the
         // few wider nodes take the relaunch, the others keep the small workspace
-        uint32_t words = s->evict_words;
-        if (s->n_beyond_w1 <= nn / 8) words = 1;
-        else if (s->n_beyond_w8 <= nn / 8) words = std::min(words, 8u);
-        size_t app_cap = 0;
-        if (evicting) {
-            // an evicting entry preempts at least one alloc and an alloc is preempted once
-            app_cap = std::min<size_t>(E, s->h_palloc_index.size());
-            HIP_TRY(s, s->d_sysg_resume.ensure(sizeof(uint32_t) * lanes));
-            HIP_TRY(s, s->d_sysg_lanes.ensure(sizeof(uint32_t) * 2 * (size_t)lanes));
-            HIP_TRY(s, s->d_sysg_ctl.ensure(sizeof(uint32_t) * 4));
-            HIP_TRY(s, s->h_sysg_ctl.ensure(sizeof(uint32_t) * 4));
-            HIP_TRY(s, s->d_sysg_app.ensure(sizeof(uint32_t) * (1 + words) * std::max<size_t>(app_cap, 1)));
-            HIP_TRY(s, hipMemsetAsync(s->d_sysg_ctl.p, 0, sizeof(uint32_t) * 4, s->stream));
-            ctl = s->d_sysg_ctl.as<uint32_t>();
-            pe::SysStopArgs S;
-            S.resume = s->d_sysg_resume.as<uint32_t>();
-            S.stopped = s->d_sysg_lanes.as<uint32_t>();
-            S.n_stopped = ctl;
-            // (measurement aid, pe_set_kernel_split: events around the stopping pass, the walk, the compaction)
-            hipEvent_t* split = nullptr;
-            s->split_valid = false;
-            if (s->tun.kernel_split) {
-                for (auto& ev : s->ev_split)
-                    if (!ev) HIP_TRY(s, hipEventCreate(&ev));
-                split = s->ev_split;
-                HIP_TRY(s, hipEventRecord(split[0], s->stream));
-            }
-            // (the stopping pass records no failure; its metrics form only for the device group's named scores)
-            if (metrics && dev_group >= 0) HIP_TRY_STATE(s, pe_launch_system_groups_metrics(&A, &S, &M, s->stream));
-            else HIP_TRY_STATE(s, pe_launch_system_groups_stop(&A, &S, s->stream));
-            if (split) HIP_TRY(s, hipEventRecord(split[1], s->stream));
-            V.G = A;
-            V.pre = reinterpret_cast<const pe::PreemptArgs*>(s->d_sysg_groups.as<uint8_t>() + pre_off);
-            V.preempted = s->d_preempted.as<uint8_t>();
-            V.pcount = s->d_pcount.as<uint32_t>();
-            V.dev_free_all = s->d_dev_free.as<uint32_t>();
-            V.resume = S.resume;
-            V.stopped = S.stopped;
-            V.n_stopped = ctl;
-            V.wider = S.stopped + lanes;
-            V.n_wider = ctl + 1;
-            V.app = s->d_sysg_app.as<uint32_t>();
-            V.n_app = ctl + 2;
-            V.app_cap = (uint32_t)app_cap;
-            V.flags = ctl + 3;
-            V.M = M;
-            if (metrics) HIP_TRY_STATE(s, pe_launch_system_groups_evict_metrics(&V, words, lanes, s->stream));
-            else HIP_TRY_STATE(s, pe_launch_system_groups_evict(&V, words, lanes, s->stream));
-            if (split) HIP_TRY(s, hipEventRecord(split[2], s->stream));
-        } else {
-            if (metrics) HIP_TRY_STATE(s, pe_launch_system_groups_metrics(&A, nullptr, &M, s->stream));
-            else HIP_TRY_STATE(s, pe_launch_system_groups(&A, s->stream));
+        c.words = s->evict_words;
+        if (s->n_beyond_w1 <= nn / 8) c.words = 1;
+        else if (s->n_beyond_w8 <= nn / 8) c.words = std::min(c.words, 8u);
+        // an evicting entry preempts at least one alloc and an alloc is preempted once
+        c.app_cap = std::min<size_t>(c.E, s->h_palloc_index.size());
+        HIP_TRY(s, y.d_resume.ensure(sizeof(uint32_t) * lanes));
+        HIP_TRY(s, y.d_lanes.ensure(sizeof(uint32_t) * 2 * (size_t)lanes));
+        HIP_TRY(s, y.d_ctl.ensure(sizeof(uint32_t) * 4));
+        HIP_TRY(s, y.h_ctl.ensure(sizeof(uint32_t) * 4));
+        HIP_TRY(s, y.d_app.ensure(sizeof(uint32_t) * (1 + c.words) * std::max<size_t>(c.app_cap, 1)));
+        HIP_TRY(s, hipMemsetAsync(y.d_ctl.p, 0, sizeof(uint32_t) * 4, s->stream));
+        uint32_t* ctl = c.ctl = y.d_ctl.as<uint32_t>();
+        pe::SysStopArgs S;
+        S.resume = y.d_resume.as<uint32_t>();
+        S.stopped = y.d_lanes.as<uint32_t>();
+        S.n_stopped = ctl;
+        // (measurement aid, pe_set_kernel_split: events around the stopping pass, the walk, the compaction)
+        hipEvent_t* split = nullptr;
+        s->split_valid = false;
+        if (s->tun.kernel_split) {
+            for (auto& ev : s->ev_split)
+                if (!ev) HIP_TRY(s, hipEventCreate(&ev));
+            split = s->ev_split;
+            HIP_TRY(s, hipEventRecord(split[0], s->stream));
         }
-        pe::SysCompactArgs Cx;
-        std::memset(&Cx, 0, sizeof(Cx));
-        Cx.res = A.res;
-        Cx.list = by_row ? A.list : nullptr;
-        Cx.n_tg = n_tg;
-        Cx.n_entries = (uint32_t)E;
-        Cx.n_tiles = n_tiles;
-        Cx.status2 = s->d_sysg_out.as<uint8_t>();
-        Cx.tile_off = s->d_sysg_tiles.as<uint32_t>();
-        Cx.score = reinterpret_cast<double*>(s->d_sysg_out.as<uint8_t>() + sb);
-        Cx.counts = A.counts;
-        Cx.hdr = hdr_dev;
-        HIP_TRY(s, pe_launch_system_compact(&Cx, s->stream));
-        HIP_TRY(s, hipEventRecord(s->ev1, s->stream));
-        if (evicting && s->tun.kernel_split) {
-            HIP_TRY(s, hipEventRecord(s->ev_split[3], s->stream));
-            HIP_TRY(s, hipEventRecord(s->ev_split[4], s->stream));   // (recorded again behind each wider round)
-            s->split_valid = true;
-            s->split_rounds = 1;
+        // (the stopping pass records no failure; its metrics form only for the device group's named scores)
+        HIP_TRY_STATE(s, pe_launch_system_groups(&A, &S, c.dev_group >= 0 ? m : nullptr, s->stream));
+        if (split) HIP_TRY(s, hipEventRecord(split[1], s->stream));
+        pe::SysEvictArgs& V = c.V;
+        V.G = A;
+        V.preempted = s->d_preempted.as<uint8_t>();
+        V.pcount = s->d_pcount.as<uint32_t>();
+        V.dev_free_all = s->d_dev_free.as<uint32_t>();
+        V.resume = S.resume;
+        V.stopped = S.stopped;
+        V.n_stopped = ctl;
+        V.wider = S.stopped + lanes;
+        V.n_wider = ctl + 1;
+        V.app = y.d_app.as<uint32_t>();
+        V.n_app = ctl + 2;
+        V.app_cap = (uint32_t)c.app_cap;
+        V.flags = ctl + 3;
+        V.M = c.M;
+        HIP_TRY_STATE(s, pe_launch_system_groups_evict(&V, c.words, lanes, c.metrics, s->stream));
+        if (split) HIP_TRY(s, hipEventRecord(split[2], s->stream));
+    } else {
+        HIP_TRY_STATE(s, pe_launch_system_groups(&A, nullptr, m, s->stream));
+    }
+    HIP_TRY(s, pe_launch_system_compact(&c.Cx, s->stream));
+    HIP_TRY(s, hipEventRecord(s->ev1, s->stream));
+    if (c.evicting && s->tun.kernel_split) {
+        HIP_TRY(s, hipEventRecord(s->ev_split[3], s->stream));
+        HIP_TRY(s, hipEventRecord(s->ev_split[4], s->stream));   // (recorded again behind each wider round)
+        s->split_valid = true;
+        s->split_rounds = 1;
+    }
+    if (c.evicting)
+        HIP_TRY(s, hipMemcpyAsync(y.h_ctl.p, c.ctl, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));   // the kernels' wait: the header words are in host memory
+    y.counts_zeroed = y.d_counts.p;
+    c.p = c.hdr[0];
+    if ((size_t)c.p > c.E) return s->fail(PE_EINTERNAL, c.fn + ": placed count beyond the entries");
+    std::memcpy(y.counts.data(), c.hdr + 1, sizeof(uint32_t) * 3 * (size_t)n_tg);
+    return PE_OK;
+}
+
+// The results to the staging and the wait for them: one DMA of the outcome
+// bytes and the placed entries' scores behind them, before it the maps'
+// copies (AllocMetric on). Whatever the caller queued just before shares the
+// wait.
+static int sysg_fetch_results(pe_stack* s, const SysGroupsCall& c) {
+    SysGroupsState& y = s->sysg;
+    if (c.metrics) {
+        HIP_TRY(s, hipMemcpyAsync(y.h_first.p, y.d_first.p, sizeof(uint64_t) * c.n_tg, hipMemcpyDeviceToHost, s->stream));
+        if (c.dev_group >= 0)
+            HIP_TRY(s, hipMemcpyAsync(y.h_named.p, y.d_named.p, sizeof(double) * 2 * (size_t)c.n, hipMemcpyDeviceToHost,
+                                      s->stream));
+    }
+    HIP_TRY(s, hipMemcpyAsync(y.h_out.p, y.d_out.p, c.sb + sizeof(double) * (size_t)c.p, hipMemcpyDeviceToHost,
+                              s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    return PE_OK;
+}
+
+// After the eviction walk: its appended records to the host, and one more
+// round per wider eviction width some node needs (none in the common case):
+// the walk over the lanes the last launch left, the compaction again over the
+// completed outcomes; k_sysg_scan hands out and clears the counters each time,
+// so the rounds' counts add up. The last round fetches the results.
+static int sysg_evict_rounds(pe_stack* s, SysGroupsCall& c) {
+    SysGroupsState& y = s->sysg;
+    const std::string& fn = c.fn;
+    const uint32_t lanes = c.lanes;
+    uint32_t* ctl = c.ctl;
+    pe::SysEvictArgs& V = c.V;
+    for (uint32_t round = 0;; round++) {
+        const uint32_t* hc = y.h_ctl.as<uint32_t>();
+        const uint32_t n_app = hc[2], flags = hc[3];
+        if (flags & (pe::kEvictUnsup | pe::kSysgOverflow))
+            return s->fail(PE_EINTERNAL, fn + ": the eviction walk met a node outside the device path");
+        if ((size_t)n_app > c.app_cap) return s->fail(PE_EINTERNAL, fn + ": appended records beyond the buffer");
+        const bool last = !(flags & pe::kEvictWider);
+        const size_t rec = 1 + (size_t)c.words;   // this round's records: [entry | mask words]
+        if (n_app) {
+            HIP_TRY(s, y.h_app.ensure(sizeof(uint32_t) * rec * n_app));
+            HIP_TRY(s, hipMemcpyAsync(y.h_app.p, y.d_app.p, sizeof(uint32_t) * rec * n_app, hipMemcpyDeviceToHost,
+                                      s->stream));
         }
-        if (evicting)
-            HIP_TRY(s, hipMemcpyAsync(s->h_sysg_ctl.p, ctl, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(s, hipStreamSynchronize(s->stream));   // the kernels' wait: the header words are in host memory
-        s->sysg_counts_zeroed = s->d_sysg_counts.p;
-        p = hdr[0];
-        if ((size_t)p > E) return s->fail(PE_EINTERNAL, fn + ": placed count beyond the entries");
-        std::memcpy(s->sysg_counts.data(), hdr + 1, sizeof(uint32_t) * 3 * (size_t)n_tg);
-        // one more round per wider eviction width some node needs (none in the
-        // common case): the walk over the lanes the last launch left, the
-        // compaction again over the completed outcomes; k_sysg_scan hands out
-        // and clears the counters each time, so the rounds' counts add up
-        for (uint32_t round = 0; evicting; round++) {
-            const uint32_t* hc = s->h_sysg_ctl.as<uint32_t>();
-            const uint32_t n_app = hc[2], flags = hc[3];
-            if (flags & (pe::kEvictUnsup | pe::kSysgOverflow))
-                return s->fail(PE_EINTERNAL, fn + ": the eviction walk met a node outside the device path");
-            if ((size_t)n_app > app_cap) return s->fail(PE_EINTERNAL, fn + ": appended records beyond the buffer");
-            if (n_app) {   // this round's records: [entry | mask words]
-                const size_t rec = 1 + (size_t)words, bytes = sizeof(uint32_t) * rec * n_app;
-                HIP_TRY(s, s->h_sysg_app.ensure(bytes));
-                HIP_TRY(s, hipMemcpyAsync(s->h_sysg_app.p, s->d_sysg_app.p, bytes, hipMemcpyDeviceToHost, s->stream));
-                if (!(flags & pe::kEvictWider)) HIP_TRY(s, queue_maps());
-                if (!(flags & pe::kEvictWider))   // with the results' DMA below: one wait for both
-                    HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p,
-                                              hipMemcpyDeviceToHost, s->stream));
-                HIP_TRY(s, hipStreamSynchronize(s->stream));
-                const uint32_t* r = s->h_sysg_app.as<uint32_t>();
-                const size_t base = ev_masks.size();
-                ev_masks.insert(ev_masks.end(), r, r + rec * n_app);   // (the staging is reused by a wider round)
-                evicted.reserve(evicted.size() + n_app);
-                for (uint32_t a = 0; a < n_app; a++, r += rec) {
-                    if ((size_t)r[0] >= E) return s->fail(PE_EINTERNAL, fn + ": an appended entry out of range");
-                    evicted.push_back(Evicted{r[0], words, base + rec * a + 1});
-                }
-            } else if (!(flags & pe::kEvictWider)) {
-                HIP_TRY(s, queue_maps());
-                HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p,
-                                          hipMemcpyDeviceToHost, s->stream));
-                HIP_TRY(s, hipStreamSynchronize(s->stream));
-            }
-            if (!(flags & pe::kEvictWider)) break;
-            words = wider_words(words);
-            if (!words || round >= 2) return s->fail(PE_EINTERNAL, fn + ": a node beyond the widest eviction width");
-            // the lanes left over become this round's list; its own leftovers go to the other half
-            uint32_t* lists = s->d_sysg_lanes.as<uint32_t>();
-            const bool from_second = (round & 1u) == 0;   // the first walk wrote the second half
-            V.stopped = from_second ? lists + lanes : lists;
-            V.n_stopped = from_second ? ctl + 1 : ctl;
-            V.wider = from_second ? lists : lists + lanes;
-            V.n_wider = from_second ? ctl : ctl + 1;
-            HIP_TRY(s, s->d_sysg_app.ensure(sizeof(uint32_t) * (1 + words) * std::max<size_t>(app_cap, 1)));
-            V.app = s->d_sysg_app.as<uint32_t>();
-            HIP_TRY(s, hipMemsetAsync(V.n_wider, 0, sizeof(uint32_t), s->stream));
-            HIP_TRY(s, hipMemsetAsync(ctl + 2, 0, sizeof(uint32_t) * 2, s->stream));
-            if (metrics) HIP_TRY_STATE(s, pe_launch_system_groups_evict_metrics(&V, words, lanes, s->stream));
-            else HIP_TRY_STATE(s, pe_launch_system_groups_evict(&V, words, lanes, s->stream));
-            // the compaction again, now over the completed outcomes. (The one
-            // before read res words that the left-over nodes had not written
-            // yet, stale from an earlier call or never initialised: its packed
-            // outcomes, scores and total are all rewritten here and were not
-            // used, only its counters, which come from the kernels' counts.)
-            HIP_TRY(s, pe_launch_system_compact(&Cx, s->stream));
-            if (s->tun.kernel_split) {
-                HIP_TRY(s, hipEventRecord(s->ev_split[4], s->stream));
-                s->split_rounds++;
-            }
-            HIP_TRY(s, hipMemcpyAsync(s->h_sysg_ctl.p, ctl, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s->stream));
-            HIP_TRY(s, hipStreamSynchronize(s->stream));
-            p = hdr[0];
-            if ((size_t)p > E) return s->fail(PE_EINTERNAL, fn + ": placed count beyond the entries");
-            for (size_t c = 0; c < 3 * (size_t)n_tg; c++) s->sysg_counts[c] += hdr[1 + c];
-        }
-        if (!evicting) {
-            // one DMA: the outcome bytes and the placed entries' scores behind them
-            HIP_TRY(s, queue_maps());
-            HIP_TRY(s, hipMemcpyAsync(s->h_sysg_out.p, s->d_sysg_out.p, sb + sizeof(double) * (size_t)p,
-                                      hipMemcpyDeviceToHost, s->stream));
+        if (last) {   // with the records' copy: one wait for both
+            const int rc = sysg_fetch_results(s, c);
+            if (rc) return rc;
+        } else if (n_app) {
             HIP_TRY(s, hipStreamSynchronize(s->stream));
         }
+        if (n_app) {
+            const uint32_t* r = y.h_app.as<uint32_t>();
+            const size_t base = c.ev_masks.size();
+            c.ev_masks.insert(c.ev_masks.end(), r, r + rec * n_app);   // (the staging is reused by a wider round)
+            c.evicted.reserve(c.evicted.size() + n_app);
+            for (uint32_t a = 0; a < n_app; a++, r += rec) {
+                if ((size_t)r[0] >= c.E) return s->fail(PE_EINTERNAL, fn + ": an appended entry out of range");
+                c.evicted.push_back(SysEvicted{r[0], c.words, base + rec * a + 1});
+            }
+        }
+        if (last) return PE_OK;
+        c.words = wider_words(c.words);
+        if (!c.words || round >= 2) return s->fail(PE_EINTERNAL, fn + ": a node beyond the widest eviction width");
+        // the lanes left over become this round's list; its own leftovers go to the other half
+        uint32_t* lists = y.d_lanes.as<uint32_t>();
+        const bool from_second = (round & 1u) == 0;   // the first walk wrote the second half
+        V.stopped = from_second ? lists + lanes : lists;
+        V.n_stopped = from_second ? ctl + 1 : ctl;
+        V.wider = from_second ? lists : lists + lanes;
+        V.n_wider = from_second ? ctl : ctl + 1;
+        HIP_TRY(s, y.d_app.ensure(sizeof(uint32_t) * (1 + c.words) * std::max<size_t>(c.app_cap, 1)));
+        V.app = y.d_app.as<uint32_t>();
+        HIP_TRY(s, hipMemsetAsync(V.n_wider, 0, sizeof(uint32_t), s->stream));
+        HIP_TRY(s, hipMemsetAsync(ctl + 2, 0, sizeof(uint32_t) * 2, s->stream));
+        HIP_TRY_STATE(s, pe_launch_system_groups_evict(&V, c.words, lanes, c.metrics, s->stream));
+        // the compaction again, now over the completed outcomes. (The one
+        // before read res words that the left-over nodes had not written
+        // yet, stale from an earlier call or never initialised: its packed
+        // outcomes, scores and total are all rewritten here and were not
+        // used, only its counters, which come from the kernels' counts.)
+        HIP_TRY(s, pe_launch_system_compact(&c.Cx, s->stream));
+        if (s->tun.kernel_split) {
+            HIP_TRY(s, hipEventRecord(s->ev_split[4], s->stream));
+            s->split_rounds++;
+        }
+        HIP_TRY(s, hipMemcpyAsync(y.h_ctl.p, ctl, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
+        c.p = c.hdr[0];
+        if ((size_t)c.p > c.E) return s->fail(PE_EINTERNAL, fn + ": placed count beyond the entries");
+        for (size_t k = 0; k < 3 * (size_t)c.n_tg; k++) y.counts[k] += c.hdr[1 + k];
+    }
+}
+
+// The device pass: results in the staging, counts and placed total on the
+// host. An empty list has none.
+static int sysg_device_pass(pe_stack* s, SysGroupsCall& c) {
+    if (c.n) {
+        int rc = sysg_setup(s, c);
+        if (!rc) rc = sysg_launch(s, c);
+        if (!rc) rc = c.evicting ? sysg_evict_rounds(s, c) : sysg_fetch_results(s, c);
+        if (rc) return rc;
         float ms = 0;
         HIP_TRY(s, hipEventElapsedTime(&ms, s->ev0, s->ev1));
         s->last_ms = ms;
         s->last_ms_pending = false;
     }
-    s->sysg_n = n;
-    s->sysg_ntg = n_tg;
-    s->sysg_placed = p;
-    s->sysg_valid = true;
-    if (metrics) {
-        // each group's first failure as the caller reads it: the walk's code
-        // to the dimension key compute_metrics records, the node's class key
-        HIP_TRY(s, s->h_sysg_fail.ensure(sizeof(pe_sysg_failure) * n_tg));
-        pe_sysg_failure* f = s->h_sysg_fail.as<pe_sysg_failure>();
-        const uint64_t* w = n ? s->h_sysg_first.as<uint64_t>() : nullptr;
-        for (uint32_t k = 0; k < n_tg; k++) {
-            f[k] = pe_sysg_failure{PE_NONE, PE_NONE, PE_NONE, 0u};
-            if (!w || w[k] == ~(uint64_t)0) continue;
-            const uint32_t pos = (uint32_t)(w[k] >> 32), code = (uint32_t)w[k];
-            if (pos >= n) return s->fail(PE_EINTERNAL, fn + ": a first failure out of range");
-            f[k].pos = pos;
-            if (code == pe::kTrOption) {
-                // an eviction Select that gave the node up records nothing
-                // (compute_metrics' kSkipped); the plain walk always has a reason
-                if (!evicting) return s->fail(PE_EINTERNAL, fn + ": an exhausted entry without a dimension");
-                continue;
-            }
-            uint32_t kind = 0, key = PE_NONE;
-            if (!trace_key(s, code, &kind, &key) || kind != PE_METRIC_DIMENSION_EXHAUSTED)
-                return s->fail(PE_EINTERNAL, fn + ": unknown dimension code");
-            f[k].dimension = key;
-            f[k].node_class = MetricAcc::mclass(s, s->visit[pos]);
+    s->sysg.n = c.n;
+    s->sysg.ntg = c.n_tg;
+    s->sysg.placed = c.p;
+    s->sysg.valid = true;
+    return PE_OK;
+}
+
+// AllocMetric on: what pe_system_groups_metrics hands out, and the reference
+// memo as the Selects in turn leave it.
+static int sysg_metrics_finish(pe_stack* s, const SysGroupsCall& c) {
+    const std::string& fn = c.fn;
+    const uint32_t* tgs = c.tgs;
+    const uint32_t n = c.n, n_tg = c.n_tg;
+    // each group's first failure as the caller reads it: the walk's code
+    // to the dimension key compute_metrics records, the node's class key
+    HIP_TRY(s, s->sysg.h_fail.ensure(sizeof(pe_sysg_failure) * n_tg));
+    pe_sysg_failure* f = s->sysg.h_fail.as<pe_sysg_failure>();
+    const uint64_t* w = n ? s->sysg.h_first.as<uint64_t>() : nullptr;
+    for (uint32_t k = 0; k < n_tg; k++) {
+        f[k] = pe_sysg_failure{PE_NONE, PE_NONE, PE_NONE, 0u};
+        if (!w || w[k] == ~(uint64_t)0) continue;
+        const uint32_t pos = (uint32_t)(w[k] >> 32), code = (uint32_t)w[k];
+        if (pos >= n) return s->fail(PE_EINTERNAL, fn + ": a first failure out of range");
+        f[k].pos = pos;
+        if (code == pe::kTrOption) {
+            // an eviction Select that gave the node up records nothing
+            // (compute_metrics' kSkipped); the plain walk always has a reason
+            if (!c.evicting) return s->fail(PE_EINTERNAL, fn + ": an exhausted entry without a dimension");
+            continue;
         }
-        // the reference memo shadow as the Selects leave it: every node of a
-        // computed class shares a verdict, so the final memo does not depend on
-        // the visiting order and each group walks the list once. Only a
-        // class's first listed node can change an entry (unless the job's
-        // constraints escape the classes, where the job verdict is per node),
-        // so the walk is over those nodes and evaluates no constraint for the
-        // others
-        MetricAcc acc;
-        std::vector<uint32_t> passed, firsts;
-        const std::vector<uint32_t>* order = &s->visit;
-        if (n && !s->job_escaped) {
-            jf_ready(s);
-            std::vector<uint8_t> seen(s->ncls, 0);
-            for (uint32_t r : s->visit) {
-                const uint32_t c = s->jf_cls[r];
-                if (c < seen.size() && !seen[c]) {
-                    seen[c] = 1;
-                    firsts.push_back(r);
-                }
-            }
-            order = &firsts;
-        }
-        for (uint32_t k = 0; k < n_tg && n; k++) {
-            acc.reset();
-            passed.clear();
-            metrics_walk(s, *s->tgs[tgs[k]], *order, 0, (uint32_t)order->size(), acc, passed);
-        }
-        s->sysg_dev_group = dev_group;
-        s->sysg_met_valid = true;
-        s->metrics_valid = false;   // no "last Select"
+        uint32_t kind = 0, key = PE_NONE;
+        if (!trace_key(s, code, &kind, &key) || kind != PE_METRIC_DIMENSION_EXHAUSTED)
+            return s->fail(PE_EINTERNAL, fn + ": unknown dimension code");
+        f[k].dimension = key;
+        f[k].node_class = MetricAcc::mclass(s, s->visit[pos]);
     }
+    // the reference memo shadow as the Selects leave it: every node of a
+    // computed class shares a verdict, so the final memo does not depend on
+    // the visiting order and each group walks the list once. Only a
+    // class's first listed node can change an entry (unless the job's
+    // constraints escape the classes, where the job verdict is per node),
+    // so the walk is over those nodes and evaluates no constraint for the
+    // others
+    MetricAcc acc;
+    std::vector<uint32_t> passed, firsts;
+    const std::vector<uint32_t>* order = &s->visit;
+    if (n && !s->job_escaped) {
+        jf_ready(s);
+        std::vector<uint8_t> seen(s->ncls, 0);
+        for (uint32_t r : s->visit) {
+            const uint32_t cls = s->jf_cls[r];
+            if (cls < seen.size() && !seen[cls]) {
+                seen[cls] = 1;
+                firsts.push_back(r);
+            }
+        }
+        order = &firsts;
+    }
+    for (uint32_t k = 0; k < n_tg && n; k++) {
+        acc.reset();
+        passed.clear();
+        metrics_walk(s, *s->tgs[tgs[k]], *order, 0, (uint32_t)order->size(), acc, passed);
+    }
+    s->sysg.dev_group = c.dev_group;
+    s->sysg.met_valid = true;
+    s->metrics_valid = false;   // no "last Select"
+    return PE_OK;
+}
+
+// The caller's arrays, and Plan.AppendAlloc of every placed entry: written
+// when the plan is next read.
+static void sysg_outputs(pe_stack* s, const SysGroupsCall& c, double* out_score, uint8_t* out_status2, uint32_t* counts,
+                         uint32_t* placed) {
+    const uint32_t n = c.n, n_tg = c.n_tg;
     if (out_score && n) {
-        const uint8_t* h = s->h_sysg_out.as<uint8_t>();
-        std::memcpy(out_status2, h, (E + 3) / 4);
-        std::memcpy(out_score, h + sb, sizeof(double) * (size_t)p);
+        const uint8_t* h = s->sysg.h_out.as<uint8_t>();
+        std::memcpy(out_status2, h, (c.E + 3) / 4);
+        std::memcpy(out_score, h + c.sb, sizeof(double) * (size_t)c.p);
     }
-    if (counts) std::memcpy(counts, s->sysg_counts.data(), sizeof(uint32_t) * 3 * (size_t)n_tg);
-    if (placed) *placed = p;
+    if (counts) std::memcpy(counts, s->sysg.counts.data(), sizeof(uint32_t) * 3 * (size_t)n_tg);
+    if (placed) *placed = c.p;
     // the host mirrors, group after group, as the calls in turn leave them
     s->gen += n_tg;
     if (n) {   // Plan.AppendAlloc of every placed entry: written when the plan is next read
         s->plan_defer.active = true;
         s->plan_defer.n = n;
         s->plan_defer.names.resize(n_tg);
-        for (uint32_t k = 0; k < n_tg; k++) s->plan_defer.names[k] = s->tgs[tgs[k]]->name;
-        s->plan_defer.status2 = s->h_sysg_out.as<uint8_t>();
+        for (uint32_t k = 0; k < n_tg; k++) s->plan_defer.names[k] = s->tgs[c.tgs[k]]->name;
+        s->plan_defer.status2 = s->sysg.h_out.as<uint8_t>();
         s->plan_defer.evicting.clear();
     }
-    if (pre_call) {
-        // Plan.AppendPreemptedAlloc of every evicting entry, as set_preempted
-        // mirrors it: the masks become alloc-table rows in increasing CSR slot,
-        // kept as a CSR by increasing entry
-        const auto by_entry = [](const Evicted& a, const Evicted& b) { return a.e < b.e; };
-        if (evicted.size() * 16 < (size_t)n) {
-            std::sort(evicted.begin(), evicted.end(), by_entry);
-        } else {   // many: a counting sort over the list positions, then the few entries of one position
-            std::vector<uint32_t> at(n + 1, 0);
-            for (const Evicted& v : evicted) at[v.e / n_tg + 1]++;
-            for (uint32_t i = 0; i < n; i++) at[i + 1] += at[i];
-            std::vector<Evicted> sorted(evicted.size());
-            for (const Evicted& v : evicted) sorted[at[v.e / n_tg]++] = v;   // at[pos] ends as the end of pos
-            for (uint32_t i = 0, b = 0; i < n; b = at[i++])
-                if (at[i] - b > 1) std::sort(sorted.begin() + b, sorted.begin() + at[i], by_entry);
-            evicted.swap(sorted);
-        }
-        std::vector<uint32_t> off(1, 0), rows_of;
-        off.reserve(evicted.size() + 1);
-        rows_of.reserve(evicted.size() + evicted.size() / 4);
-        s->plan_defer.evicting.reserve(evicted.size());
-        bool any = false;
-        for (const Evicted& v : evicted) {
-            const uint32_t row = s->visit[v.e / n_tg];
-            const uint32_t b = s->h_node_alloc_off[row], m = s->h_node_alloc_off[row + 1] - b;
-            const uint32_t* mask = ev_masks.data() + v.at;
-            for (uint32_t w = 0; w < v.words && 32u * w < m; w++)
-                for (uint32_t bits = mask[w]; bits; bits &= bits - 1) {   // increasing slot
-                    const uint32_t i = 32u * w + (uint32_t)__builtin_ctz(bits);
-                    if (i >= m) break;
-                    const uint32_t a = s->h_palloc_index[b + i];
-                    rows_of.push_back(a);
-                    s->h_preempted[b + i] = 1;
-                    core_hold(s, a, false);
-                    any = true;
-                }
-            off.push_back((uint32_t)rows_of.size());
-            s->plan_defer.evicting.push_back(v.e);
-        }
-        if (any) invalidate_static(s);
-        const size_t ne = evicted.size();
-        HIP_TRY(s, s->h_sysg_csr.ensure(sizeof(uint32_t) * (2 * ne + 1 + rows_of.size())));
-        uint32_t* w = s->h_sysg_csr.as<uint32_t>();
-        for (size_t i = 0; i < ne; i++) w[i] = evicted[i].e;
-        std::memcpy(w + ne, off.data(), sizeof(uint32_t) * (ne + 1));
-        if (!rows_of.empty()) std::memcpy(w + 2 * ne + 1, rows_of.data(), sizeof(uint32_t) * rows_of.size());
-        s->sysg_pre_entries = (uint32_t)ne;
-        s->sysg_pre_allocs = rows_of.size();
-        s->sysg_pre_valid = true;
+}
+
+// Plan.AppendPreemptedAlloc of every evicting entry, as set_preempted mirrors
+// it: the masks become alloc-table rows in increasing CSR slot, kept as a CSR
+// by increasing entry (pe_system_groups_preempted). After sysg_outputs: the
+// evicting entries join the deferred plan entries it set up.
+static int sysg_mirror_preempted(pe_stack* s, SysGroupsCall& c) {
+    const uint32_t n = c.n, n_tg = c.n_tg;
+    std::vector<SysEvicted>& evicted = c.evicted;
+    const std::vector<uint32_t>& ev_masks = c.ev_masks;
+    const auto by_entry = [](const SysEvicted& a, const SysEvicted& b) { return a.e < b.e; };
+    if (evicted.size() * 16 < (size_t)n) {
+        std::sort(evicted.begin(), evicted.end(), by_entry);
+    } else {   // many: a counting sort over the list positions, then the few entries of one position
+        std::vector<uint32_t> at(n + 1, 0);
+        for (const SysEvicted& v : evicted) at[v.e / n_tg + 1]++;
+        for (uint32_t i = 0; i < n; i++) at[i + 1] += at[i];
+        std::vector<SysEvicted> sorted(evicted.size());
+        for (const SysEvicted& v : evicted) sorted[at[v.e / n_tg]++] = v;   // at[pos] ends as the end of pos
+        for (uint32_t i = 0, b = 0; i < n; b = at[i++])
+            if (at[i] - b > 1) std::sort(sorted.begin() + b, sorted.begin() + at[i], by_entry);
+        evicted.swap(sorted);
     }
+    std::vector<uint32_t> off(1, 0), rows_of;
+    off.reserve(evicted.size() + 1);
+    rows_of.reserve(evicted.size() + evicted.size() / 4);
+    s->plan_defer.evicting.reserve(evicted.size());
+    bool any = false;
+    for (const SysEvicted& v : evicted) {
+        const uint32_t row = s->visit[v.e / n_tg];
+        const uint32_t b = s->h_node_alloc_off[row], m = s->h_node_alloc_off[row + 1] - b;
+        const uint32_t* mask = ev_masks.data() + v.at;
+        for (uint32_t w = 0; w < v.words && 32u * w < m; w++)
+            for (uint32_t bits = mask[w]; bits; bits &= bits - 1) {   // increasing slot
+                const uint32_t i = 32u * w + (uint32_t)__builtin_ctz(bits);
+                if (i >= m) break;
+                const uint32_t a = s->h_palloc_index[b + i];
+                rows_of.push_back(a);
+                s->h_preempted[b + i] = 1;
+                core_hold(s, a, false);
+                any = true;
+            }
+        off.push_back((uint32_t)rows_of.size());
+        s->plan_defer.evicting.push_back(v.e);
+    }
+    if (any) invalidate_static(s);
+    const size_t ne = evicted.size();
+    HIP_TRY(s, s->sysg.h_csr.ensure(sizeof(uint32_t) * (2 * ne + 1 + rows_of.size())));
+    uint32_t* w = s->sysg.h_csr.as<uint32_t>();
+    for (size_t i = 0; i < ne; i++) w[i] = evicted[i].e;
+    std::memcpy(w + ne, off.data(), sizeof(uint32_t) * (ne + 1));
+    if (!rows_of.empty()) std::memcpy(w + 2 * ne + 1, rows_of.data(), sizeof(uint32_t) * rows_of.size());
+    s->sysg.pre_entries = (uint32_t)ne;
+    s->sysg.pre_allocs = rows_of.size();
+    s->sysg.pre_valid = true;
+    return PE_OK;
+}
+
+// The rest of the host mirrors.
+static void sysg_tail(pe_stack* s, const SysGroupsCall& c) {
     sys_deactivate(s);   // rows committed on the device: the per-row cache is stale
-    for (uint32_t k = 0; k < n_tg; k++) {
-        elig_log_span(s, tgs[k], 0, n);   // one single-node Select per row and group
-        invalidate_job_distinct(s, tgs[k]);
+    for (uint32_t k = 0; k < c.n_tg; k++) {
+        elig_log_span(s, c.tgs[k], 0, c.n);   // one single-node Select per row and group
+        invalidate_job_distinct(s, c.tgs[k]);
     }
+}
+
+// SystemScheduler.computePlacements' loop over (node, task group) in one pass
+// (DESIGN.md §32): results and state equal those of pe_system_place of each
+// listed group in turn. Everything that can refuse the call is checked before
+// anything changes; then system_place_impl's order of work with one upload,
+// the kernels and one wait, and the host mirrors group after group.
+//
+// `pre_call`: pe_system_place_groups_preempt (DESIGN.md §33). On a preempting
+// stack the pass stops a node at its first exhausted group
+// (k_system_groups<true, *>) and the eviction walk (k_system_groups_evict) takes
+// the stopped nodes from there, BinPack with evict where the plain fit is
+// exhausted; the preempted allocs of every evicting entry are kept as a CSR
+// (pe_system_groups_preempted). Results and state equal those of
+// pe_system_place of each listed group in turn on the preempting stack.
+//
+// `met_call`: pe_system_place_groups_metrics (DESIGN.md §34), the `pre_call`
+// form that runs with AllocMetric on. The walks' metrics forms return each
+// group's first exhausted entry with its dimension and the device group's
+// named scores (pe_system_groups_metrics); the reference memo advances group
+// after group.
+static int system_place_groups_impl(pe_stack* s, const uint32_t* tgs, uint32_t n_tg, double* out_score,
+                                    uint8_t* out_status2, uint32_t* counts, uint32_t* placed, bool pre_call,
+                                    bool met_call = false) {
+    SysGroupsCall c;
+    c.fn = met_call ? "pe_system_place_groups_metrics"
+                    : (pre_call ? "pe_system_place_groups_preempt" : "pe_system_place_groups");
+    c.tgs = tgs;
+    c.n_tg = n_tg;
+    c.pre_call = pre_call;
+    c.met_call = met_call;
+    c.evicting = pre_call && s->cfg.preempt;
+    c.metrics = met_call && s->metrics_on;
+    if (placed) *placed = 0;
+    int rc = sysg_check(s, c, out_score, out_status2, counts);
+    if (!rc) rc = sysg_begin(s, c);
+    if (!rc) rc = sysg_device_pass(s, c);
+    if (!rc && c.metrics) rc = sysg_metrics_finish(s, c);
+    if (rc) return rc;
+    sysg_outputs(s, c, out_score, out_status2, counts, placed);
+    if (pre_call) rc = sysg_mirror_preempted(s, c);
+    if (rc) return rc;
+    sysg_tail(s, c);
     return PE_OK;
 }
 
@@ -10330,40 +10447,40 @@ int pe_system_place_groups_metrics(pe_stack* s, const uint32_t* tg_indices, uint
 int pe_system_groups_metrics(const pe_stack* s, const pe_sysg_failure** failures, int32_t* dev_group,
                              const double** dev_binpack, const double** dev_devices, uint32_t* n) {
     if (!s || !failures || !dev_group || !dev_binpack || !dev_devices || !n) return PE_EINVAL;
-    if (!s->sysg_met_valid || !s->sysg_valid || !s->h_sysg_fail.p) return PE_ESTATE;
-    *failures = s->h_sysg_fail.as<pe_sysg_failure>();
-    *n = s->sysg_n;
-    *dev_group = s->sysg_n ? s->sysg_dev_group : -1;
-    const double* named = *dev_group >= 0 ? s->h_sysg_named.as<double>() : nullptr;
+    if (!s->sysg.met_valid || !s->sysg.valid || !s->sysg.h_fail.p) return PE_ESTATE;
+    *failures = s->sysg.h_fail.as<pe_sysg_failure>();
+    *n = s->sysg.n;
+    *dev_group = s->sysg.n ? s->sysg.dev_group : -1;
+    const double* named = *dev_group >= 0 ? s->sysg.h_named.as<double>() : nullptr;
     *dev_binpack = named;
-    *dev_devices = named ? named + s->sysg_n : nullptr;
+    *dev_devices = named ? named + s->sysg.n : nullptr;
     return PE_OK;
 }
 
 int pe_system_groups_preempted(const pe_stack* s, const uint32_t** entries, const uint32_t** off,
                                const uint32_t** allocs, uint32_t* n_entries) {
     if (!s || !entries || !off || !allocs || !n_entries) return PE_EINVAL;
-    if (!s->sysg_pre_valid || !s->h_sysg_csr.p) return PE_ESTATE;
-    const uint32_t* w = s->h_sysg_csr.as<uint32_t>();
+    if (!s->sysg.pre_valid || !s->sysg.h_csr.p) return PE_ESTATE;
+    const uint32_t* w = s->sysg.h_csr.as<uint32_t>();
     *entries = w;
-    *off = w + s->sysg_pre_entries;
-    *allocs = w + 2 * (size_t)s->sysg_pre_entries + 1;
-    *n_entries = s->sysg_pre_entries;
+    *off = w + s->sysg.pre_entries;
+    *allocs = w + 2 * (size_t)s->sysg.pre_entries + 1;
+    *n_entries = s->sysg.pre_entries;
     return PE_OK;
 }
 
 int pe_system_groups_results(const pe_stack* s, const double** score, const uint8_t** status2,
                              const uint32_t** counts, uint32_t* n, uint32_t* n_tg, uint32_t* placed) {
     if (!s || !score || !status2 || !counts || !n || !n_tg || !placed) return PE_EINVAL;
-    if (!s->sysg_valid) return PE_ESTATE;
-    const size_t E = (size_t)s->sysg_n * s->sysg_ntg;
+    if (!s->sysg.valid) return PE_ESTATE;
+    const size_t E = (size_t)s->sysg.n * s->sysg.ntg;
     const size_t sb = ((E + 3) / 4 + 7) & ~(size_t)7;
-    *status2 = s->h_sysg_out.as<uint8_t>();
-    *score = s->h_sysg_out.p ? reinterpret_cast<const double*>(s->h_sysg_out.as<uint8_t>() + sb) : nullptr;
-    *counts = s->sysg_counts.data();
-    *n = s->sysg_n;
-    *n_tg = s->sysg_ntg;
-    *placed = s->sysg_placed;
+    *status2 = s->sysg.h_out.as<uint8_t>();
+    *score = s->sysg.h_out.p ? reinterpret_cast<const double*>(s->sysg.h_out.as<uint8_t>() + sb) : nullptr;
+    *counts = s->sysg.counts.data();
+    *n = s->sysg.n;
+    *n_tg = s->sysg.ntg;
+    *placed = s->sysg.placed;
     return PE_OK;
 }
 

@@ -552,9 +552,9 @@ struct SysCompactArgs {
 };
 
 // pe_system_place_groups_preempt: the stopping form of the
-// pass (k_system_groups_stop) and the eviction walk over the nodes it stopped
-// (k_system_groups_evict). A lane index is a snapshot row in the row-order
-// form and a list position otherwise, as in k_system_groups.
+// pass (k_system_groups<true, *>) and the eviction walk over the nodes it
+// stopped (k_system_groups_evict). A lane index is a snapshot row in the
+// row-order form and a list position otherwise.
 struct SysStopArgs {
     uint32_t* resume;                 // [lanes] the group a node stopped at; n_tg: walked to the end
     uint32_t* stopped;                // [lanes] the lane indices that stopped, in any order
@@ -562,7 +562,7 @@ struct SysStopArgs {
 };
 
 // pe_system_place_groups_metrics: what the AllocMetric forms of
-// the walks (k_system_groups_metrics, k_system_groups_evict<W, true>) return
+// the walks (k_system_groups<*, true>, k_system_groups_evict<W, true>) return
 // beside the outcomes.
 constexpr uint32_t kSysFirstLds = 256;        // listed groups whose first-failure word the eviction walk reduces in LDS
 struct SysMetricsArgs {

@@ -4153,86 +4153,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
     }
 }
 
-// SystemScheduler.computePlacements' loop (scheduler_system.go:283-425) over
-// every (node, task group) pair of a job with several groups: the nodes are
-// independent, the groups of one node are not (an earlier group's ask shrinks
-// what a later one finds). One lane per list position (or per snapshot row in
-// the row-order form, as k_system_rows) loads the node once, keeps its record
-// in registers and walks the listed groups in order with the pipeline every
-// other path runs; an option adds the group's ask to the registers as
-// k_system's commit does. The groups' tables are one HBM array: every lane of
-// a wave reads the same element. coll_job is written through (status_loaded
-// reads the column); the record is stored once, only if something was placed.
-// Outcomes go to res (sys_box); the per-group outcome counts are one ballot
-// per code and wave, summed in LDS, one atomic per workgroup and counter.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_system_groups(SystemGroupsArgs A) {
-    __shared__ uint32_t cnt[3 * kSysGroupsChunk];
-    if (threadIdx.x < 3 * kSysGroupsChunk) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t stride = gridDim.x * blockDim.x;
-    const uint32_t span = A.rank_of ? A.n_rows : A.n_list;
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < span; i += stride) {
-        uint32_t row = i;
-        if (A.rank_of) {
-            if (A.rank_of[i] == PE_NONE) continue;
-        } else {
-            row = A.list[i];
-        }
-        NodeIn in;
-        in.r = A.soa.rec[row];
-        uint32_t cj = A.soa.coll_job[row];
-        const uint32_t df0 = A.dev_free ? A.dev_free[row] : 0u;
-        uint32_t df = df0;
-        bool dirty = false;
-        uint64_t* out = A.res + (size_t)i * A.n_tg + A.k0;
-        for (uint32_t kk = 0; kk < A.nk; kk++) {
-            const SysGroup& G = A.groups[A.k0 + kk];
-            in.coll_tg = G.tg.coll_tg[row];
-            in.feas = G.tg.node_feas ? G.tg.node_feas[row] : 1u;
-            in.dev_free = df;
-            ScoreIn si;
-            const int st = status_loaded<false>(A.soa, G.tg, G.tg.class_ok, G.ask, 0u, row, in, &si);
-            double score = 0.0;
-            if (st == kOption) {
-                lookup_scores(G.tg, nullptr, nullptr, row, in.r.cls, &si);
-                uint32_t ns;
-                score = score_into<false>(G.ask, A.log10, si, nullptr, &ns);
-                // Plan.AppendAlloc: the later groups of this node see it
-                in.r.used_cpu += G.ask.cpu;
-                in.r.used_mem += G.ask.mem;
-                in.r.used_disk += G.ask.disk;
-                in.r.used_mbits += G.ask.commit_mbits;
-                in.r.used_dyn += G.ask.commit_dyn;
-                cj += 1u;
-                A.soa.coll_job[row] = cj;
-                G.tg.coll_tg[row] = in.coll_tg + 1u;
-                if (G.ask.n_dev > 0) df = dev_after(G.ask, G.tg.dev_cls[in.r.cls], df, 1);
-                dirty = true;
-            }
-            out[kk] = sys_box(st, score);
-            const uint64_t m0 = __ballot(st == kOption), m1 = __ballot(st == kFiltered), m2 = __ballot(st == kExhausted);
-            if (lane == (uint32_t)__ffsll((unsigned long long)(m0 | m1 | m2)) - 1u) {
-                if (m0) atomicAdd(&cnt[3 * kk + 0], (uint32_t)__popcll(m0));
-                if (m1) atomicAdd(&cnt[3 * kk + 1], (uint32_t)__popcll(m1));
-                if (m2) atomicAdd(&cnt[3 * kk + 2], (uint32_t)__popcll(m2));
-            }
-        }
-        if (!dirty) continue;
-        NodeRec& r = A.soa.rec[row];
-        r.used_cpu = in.r.used_cpu;
-        r.used_mem = in.r.used_mem;
-        r.used_disk = in.r.used_disk;
-        r.used_mbits = in.r.used_mbits;
-        r.used_dyn = in.r.used_dyn;
-        if (df != df0) A.dev_free[row] = df;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 * A.nk && cnt[threadIdx.x])
-        atomicAdd(&A.counts[(size_t)(blockIdx.x % kPlacedSlots) * 3u * A.n_tg + 3u * A.k0 + threadIdx.x], cnt[threadIdx.x]);
-}
-
-// ---- the same pass on a preempting stack -------------------
+// ---- system jobs with several task groups in one pass ---
 
 // A distinct slot of `counter` for every active lane: one atomic per wave.
 __device__ __forceinline__ uint32_t wave_slot(uint32_t* counter) {
@@ -4245,8 +4166,8 @@ __device__ __forceinline__ uint32_t wave_slot(uint32_t* counter) {
     return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
 }
 
-// One plain (node, group) step on a lane's register image: k_system_groups'
-// loop body (the same status_loaded / score_into, so the same bits). With
+// One plain (node, group) step on a lane's register image: the pipeline every
+// other path runs (the same status_loaded / score_into, so the same bits). With
 // kNamed (the AllocMetric forms) an option's ScoreNode values
 // go to named[0] (binpack) and named[1] (devices, for an ask that scores them)
 // as k_trace gives them: score_into's parts, the same sum in the same order.
@@ -4295,58 +4216,132 @@ __device__ __forceinline__ void sysg_store(const SystemGroupsArgs& A, uint32_t r
     if (df != df0) A.dev_free[row] = df;
 }
 
-// k_system_groups' stopping form: at the first group whose plain fit is
-// exhausted the lane stops. That entry and the later ones stay unwritten and
-// uncounted, the node's image goes back to HBM as at the end of the walk, the
-// group is kept in resume[lane] and the lane joins the stopped list (one
-// atomic per wave; the list's order is free, the nodes are independent). A
-// later chunk skips the lanes an earlier chunk stopped.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_system_groups_stop(SystemGroupsArgs A,
-                                                                                                   SysStopArgs S) {
+// Min of `key` over the wave's 64 lanes; every lane of the wave calls it.
+__device__ __forceinline__ unsigned long long wave_min64(unsigned long long key) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(key, off);
+        key = o < key ? o : key;
+    }
+    return key;
+}
+
+// SystemScheduler.computePlacements' loop (scheduler_system.go:283-425) over
+// every (node, task group) pair of a job with several groups: the nodes are
+// independent, the groups of one node are not (an earlier group's ask shrinks
+// what a later one finds). One lane per list position (or per snapshot row in
+// the row-order form, as k_system_rows) loads the node once, keeps its record
+// in registers and walks the chunk's groups in order with the pipeline every
+// other path runs (sysg_plain); an option adds the group's ask to the
+// registers as k_system's commit does. The groups' tables are one HBM array:
+// every lane of a wave reads the same element. coll_job is written through
+// (status_loaded reads the column); the record is stored once, only if
+// something was placed. Outcomes go to res (sys_box); the per-group outcome
+// counts are one ballot per code and wave, summed in LDS, one atomic per
+// workgroup and counter. The grid-stride loop is over whole workgroup-sized
+// blocks of lanes so that the wave reductions run in uniform control flow; a
+// lane without a node (`act` false) walks nothing.
+//
+// kStop (a preempting stack): at the first group whose plain
+// fit is exhausted the lane stops. That entry and the later ones stay
+// unwritten and uncounted, the node's image goes back to HBM as at the end of
+// the walk, the group is kept in resume[lane] and the lane joins the stopped
+// list (one atomic per wave; the list's order is free, the nodes are
+// independent). A later chunk skips the lanes an earlier chunk stopped.
+//
+// kMetrics (AllocMetric on): the same walk on the same register
+// image, so the same outcomes and FinalScore bits. Beside them
+//  - the named scores of M.dev_group's plain placements, by list position;
+//  - without kStop, the first exhausted entry of each group in walk order: at
+//    the group where the plain fit is exhausted the lane derives the dimension
+//    from its image (trace_offers, trace_fit: what that Select saw after the
+//    earlier groups' placements on the node); the key pos << 32 | code is
+//    reduced with min over the wave, one LDS atomicMin per wave, one global
+//    atomicMin per workgroup and group. In the row-order form pos is
+//    rank_of[i], not the lane's index. With kStop an exhausted plain fit is not
+//    a final outcome and nothing is recorded for it.
+template <bool kStop, bool kMetrics>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+k_system_groups(SystemGroupsArgs A, SysStopArgs S, SysMetricsArgs M) {
+    constexpr bool kFirst = kMetrics && !kStop;
     __shared__ uint32_t cnt[3 * kSysGroupsChunk];
+    __shared__ unsigned long long first[kFirst ? kSysGroupsChunk : 1];
     if (threadIdx.x < 3 * kSysGroupsChunk) cnt[threadIdx.x] = 0;
+    if (kFirst && threadIdx.x < kSysGroupsChunk) first[threadIdx.x] = ~0ull;
     __syncthreads();
     const uint32_t stride = gridDim.x * blockDim.x;
     const uint32_t span = A.rank_of ? A.n_rows : A.n_list;
     const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < span; i += stride) {
-        uint32_t row = i;
-        if (A.rank_of) {
-            if (A.rank_of[i] == PE_NONE) continue;
-        } else {
-            row = A.list[i];
+    for (uint32_t base = blockIdx.x * blockDim.x; base < span; base += stride) {
+        const uint32_t i = base + threadIdx.x;
+        bool act = i < span;
+        uint32_t row = i, pos = i;
+        if (act) {
+            if (A.rank_of) {
+                pos = A.rank_of[i];
+                act = pos != PE_NONE;
+            } else {
+                row = A.list[i];
+            }
         }
-        if (A.k0 > 0 && S.resume[i] < A.k0) continue;   // stopped in an earlier chunk
-        NodeIn in;
-        in.r = A.soa.rec[row];
-        uint32_t cj = A.soa.coll_job[row];
-        const uint32_t df0 = A.dev_free ? A.dev_free[row] : 0u;
+        if (kStop && act && A.k0 > 0 && S.resume[i] < A.k0) act = false;   // stopped in an earlier chunk
+        NodeIn in = {};
+        uint32_t cj = 0, df0 = 0;
+        if (act) {
+            in.r = A.soa.rec[row];
+            cj = A.soa.coll_job[row];
+            df0 = A.dev_free ? A.dev_free[row] : 0u;
+        }
         uint32_t df = df0;
         bool dirty = false;
         uint32_t stop_at = A.n_tg;
         uint64_t* out = A.res + (size_t)i * A.n_tg + A.k0;
         for (uint32_t kk = 0; kk < A.nk; kk++) {
-            double score;
-            const int st = sysg_plain(A.soa, A.groups[A.k0 + kk], A.log10, row, in, cj, df, &score);
-            if (st == kExhausted) {
-                stop_at = A.k0 + kk;
-                break;
+            const SysGroup& G = A.groups[A.k0 + kk];
+            int st = -1;   // no outcome: no node, or stopped
+            double score = 0.0, named[2];
+            if (act && stop_at == A.n_tg) {
+                st = sysg_plain<kMetrics>(A.soa, G, A.log10, row, in, cj, df, &score, kMetrics ? named : nullptr);
+                if (kStop && st == kExhausted) {
+                    stop_at = A.k0 + kk;
+                    st = -1;
+                }
             }
-            dirty = dirty || st == kOption;
-            out[kk] = sys_box(st, score);
-            const uint64_t m0 = __ballot(st == kOption), m1 = __ballot(st == kFiltered);
-            if (lane == (uint32_t)__ffsll((unsigned long long)(m0 | m1)) - 1u) {
+            if (st >= 0) out[kk] = sys_box(st, score);
+            if (st == kOption) {
+                dirty = true;
+                if (kMetrics && (int32_t)(A.k0 + kk) == M.dev_group) {
+                    M.dev_named[pos] = named[0];
+                    M.dev_named[(size_t)M.n_list + pos] = named[1];
+                }
+            }
+            const uint64_t m0 = __ballot(st == kOption), m1 = __ballot(st == kFiltered), m2 = __ballot(st == kExhausted);
+            if (lane == (uint32_t)__ffsll((unsigned long long)(m0 | m1 | m2)) - 1u) {
                 if (m0) atomicAdd(&cnt[3 * kk + 0], (uint32_t)__popcll(m0));
                 if (m1) atomicAdd(&cnt[3 * kk + 1], (uint32_t)__popcll(m1));
+                if (m2) atomicAdd(&cnt[3 * kk + 2], (uint32_t)__popcll(m2));
+            }
+            if (kFirst && m2) {   // wave-uniform
+                unsigned long long key = ~0ull;
+                if (st == kExhausted) {
+                    uint32_t code = trace_offers(G.tg, G.ask, row, in, 0u);
+                    if (code == kTrOption) code = trace_fit(A.soa, G.ask, row, in.r, 0u, false);
+                    key = ((unsigned long long)pos << 32) | code;
+                }
+                key = wave_min64(key);
+                if (lane == 0) atomicMin(&first[kk], key);
             }
         }
-        if (A.k0 == 0 || stop_at < A.n_tg) S.resume[i] = stop_at;
-        if (stop_at < A.n_tg) S.stopped[wave_slot(S.n_stopped)] = i;
-        if (dirty) sysg_store(A, row, in, df, df0);
+        if (kStop && act) {
+            if (A.k0 == 0 || stop_at < A.n_tg) S.resume[i] = stop_at;
+            if (stop_at < A.n_tg) S.stopped[wave_slot(S.n_stopped)] = i;
+        }
+        if (act && dirty) sysg_store(A, row, in, df, df0);
     }
     __syncthreads();
     if (threadIdx.x < 3 * A.nk && cnt[threadIdx.x])
         atomicAdd(&A.counts[(size_t)(blockIdx.x % kPlacedSlots) * 3u * A.n_tg + 3u * A.k0 + threadIdx.x], cnt[threadIdx.x]);
+    if (kFirst && threadIdx.x < A.nk && first[threadIdx.x] != ~0ull)
+        atomicMin(&M.first[A.k0 + threadIdx.x], first[threadIdx.x]);
 }
 
 // The eviction walk over the stopped nodes, one lane per node, at eviction
@@ -4354,7 +4349,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
 // read by every lane at once); a lane acts at its resume group and after it:
 // BinPack with evict (evict_eval) where the plain fit is exhausted, on an
 // option k_commit_evicted's commit of one row and a record [entry, W mask
-// words] in the append buffer, then the plain walk as k_system_groups_stop to
+// words] in the append buffer, then the plain walk as k_system_groups<true, *> to
 // the next exhausted group. evict_eval and the commit work on HBM, so the image
 // is stored before the call and loaded again after a commit: a lane reads back
 // its own stores only. A node beyond the width commits nothing from that group
@@ -4477,114 +4472,6 @@ __global__ void __launch_bounds__(256) k_system_groups_evict(SysEvictArgs A) {
         for (uint32_t k = threadIdx.x; k < kSysFirstLds && k < Gx.n_tg; k += blockDim.x)
             if (first_lds[k] != ~0ull) atomicMin(&M->first[k], first_lds[k]);
     }
-}
-
-// Min of `key` over the wave's 64 lanes; every lane of the wave calls it.
-__device__ __forceinline__ unsigned long long wave_min64(unsigned long long key) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(key, off);
-        key = o < key ? o : key;
-    }
-    return key;
-}
-
-// k_system_groups and k_system_groups_stop (kStop) with AllocMetric on
-// (DESIGN.md §34): the same walk on the same register image, so the same
-// outcomes and FinalScore bits. Beside them
-//  - the named scores of M.dev_group's plain placements, by list position;
-//  - without kStop, the first exhausted entry of each group in walk order: at
-//    the group where the plain fit is exhausted the lane derives the dimension
-//    from its image (trace_offers, trace_fit: what that Select saw after the
-//    earlier groups' placements on the node); the key pos << 32 | code is
-//    reduced with min over the wave, one LDS atomicMin per wave, one global
-//    atomicMin per workgroup and group. In the row-order form pos is
-//    rank_of[i], not the lane's index. With kStop an exhausted plain fit is not
-//    a final outcome and nothing is recorded for it.
-// The grid-stride loop is over whole workgroup-sized blocks of lanes so that
-// the wave reductions run in uniform control flow; a lane without a node
-// (`act` false) walks nothing.
-template <bool kStop>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
-k_system_groups_metrics(SystemGroupsArgs A, SysStopArgs S, SysMetricsArgs M) {
-    __shared__ uint32_t cnt[3 * kSysGroupsChunk];
-    __shared__ unsigned long long first[kSysGroupsChunk];
-    if (threadIdx.x < 3 * kSysGroupsChunk) cnt[threadIdx.x] = 0;
-    if (threadIdx.x < kSysGroupsChunk) first[threadIdx.x] = ~0ull;
-    __syncthreads();
-    const uint32_t stride = gridDim.x * blockDim.x;
-    const uint32_t span = A.rank_of ? A.n_rows : A.n_list;
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t base = blockIdx.x * blockDim.x; base < span; base += stride) {
-        const uint32_t i = base + threadIdx.x;
-        bool act = i < span;
-        uint32_t row = i, pos = i;
-        if (act) {
-            if (A.rank_of) {
-                pos = A.rank_of[i];
-                act = pos != PE_NONE;
-            } else {
-                row = A.list[i];
-            }
-        }
-        if (kStop && act && A.k0 > 0 && S.resume[i] < A.k0) act = false;   // stopped in an earlier chunk
-        NodeIn in = {};
-        uint32_t cj = 0, df0 = 0;
-        if (act) {
-            in.r = A.soa.rec[row];
-            cj = A.soa.coll_job[row];
-            df0 = A.dev_free ? A.dev_free[row] : 0u;
-        }
-        uint32_t df = df0;
-        bool dirty = false;
-        uint32_t stop_at = A.n_tg;
-        uint64_t* out = A.res + (size_t)i * A.n_tg + A.k0;
-        for (uint32_t kk = 0; kk < A.nk; kk++) {
-            const SysGroup& G = A.groups[A.k0 + kk];
-            int st = -1;   // no outcome: no node, or stopped
-            double score = 0.0, named[2];
-            if (act && stop_at == A.n_tg) {
-                st = sysg_plain<true>(A.soa, G, A.log10, row, in, cj, df, &score, named);
-                if (kStop && st == kExhausted) {
-                    stop_at = A.k0 + kk;
-                    st = -1;
-                }
-            }
-            if (st >= 0) out[kk] = sys_box(st, score);
-            if (st == kOption) {
-                dirty = true;
-                if ((int32_t)(A.k0 + kk) == M.dev_group) {
-                    M.dev_named[pos] = named[0];
-                    M.dev_named[(size_t)M.n_list + pos] = named[1];
-                }
-            }
-            const uint64_t m0 = __ballot(st == kOption), m1 = __ballot(st == kFiltered), m2 = __ballot(st == kExhausted);
-            if (lane == (uint32_t)__ffsll((unsigned long long)(m0 | m1 | m2)) - 1u) {
-                if (m0) atomicAdd(&cnt[3 * kk + 0], (uint32_t)__popcll(m0));
-                if (m1) atomicAdd(&cnt[3 * kk + 1], (uint32_t)__popcll(m1));
-                if (m2) atomicAdd(&cnt[3 * kk + 2], (uint32_t)__popcll(m2));
-            }
-            if (!kStop && m2) {   // wave-uniform
-                unsigned long long key = ~0ull;
-                if (st == kExhausted) {
-                    uint32_t code = trace_offers(G.tg, G.ask, row, in, 0u);
-                    if (code == kTrOption) code = trace_fit(A.soa, G.ask, row, in.r, 0u, false);
-                    key = ((unsigned long long)pos << 32) | code;
-                }
-                key = wave_min64(key);
-                if (lane == 0) atomicMin(&first[kk], key);
-            }
-        }
-        if (kStop && act) {
-            if (A.k0 == 0 || stop_at < A.n_tg) S.resume[i] = stop_at;
-            if (stop_at < A.n_tg) S.stopped[wave_slot(S.n_stopped)] = i;
-        }
-        if (act && dirty) sysg_store(A, row, in, df, df0);
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 * A.nk && cnt[threadIdx.x])
-        atomicAdd(&A.counts[(size_t)(blockIdx.x % kPlacedSlots) * 3u * A.n_tg + 3u * A.k0 + threadIdx.x], cnt[threadIdx.x]);
-    if (!kStop && threadIdx.x < A.nk && first[threadIdx.x] != ~0ull)
-        atomicMin(&M.first[A.k0 + threadIdx.x], first[threadIdx.x]);
 }
 
 // The outcome of entry e (position-major, group-minor) from res: 0 placed,
@@ -4833,92 +4720,53 @@ hipError_t pe_launch_inplace(const pe::InplaceArgs* a, hipStream_t st) {
     return hipGetLastError();
 }
 
-// One launch per chunk of kSysGroupsChunk listed groups, in list order on the
-// stream (a later chunk's lanes read what the earlier chunk's stored).
-hipError_t pe_launch_system_groups(const pe::SystemGroupsArgs* a, hipStream_t st) {
-    const uint32_t span = a->rank_of ? a->n_rows : a->n_list;
-    if (!span || !a->n_tg) return hipSuccess;
-    uint32_t blocks = (span + 255) / 256;
-    if (blocks > 8192) blocks = 8192;   // grid-stride beyond
-    pe::SystemGroupsArgs c = *a;
-    for (uint32_t k0 = 0; k0 < a->n_tg; k0 += pe::kSysGroupsChunk) {
-        c.k0 = k0;
-        c.nk = a->n_tg - k0 < pe::kSysGroupsChunk ? a->n_tg - k0 : pe::kSysGroupsChunk;
-        hipLaunchKernelGGL(pe::k_system_groups, dim3(blocks), dim3(256), 0, st, c);
-    }
-    return hipGetLastError();
+static bool sysg_metrics_ok(const pe::SysMetricsArgs& m, const pe::SystemGroupsArgs& a) {
+    return m.first && (m.dev_group < 0 || m.dev_named) && m.dev_group < (int32_t)a.n_tg && m.n_list == a.n_list;
 }
 
-// The stopping form, chunked as above (a later chunk skips the stopped lanes).
-hipError_t pe_launch_system_groups_stop(const pe::SystemGroupsArgs* a, const pe::SysStopArgs* s, hipStream_t st) {
+// The chunked walk: one launch per chunk of kSysGroupsChunk listed groups, in
+// list order on the stream (a later chunk's lanes read what the earlier
+// chunk's stored, and skip the lanes it stopped). `s` set: the stopping form;
+// `m` set: the AllocMetric form.
+hipError_t pe_launch_system_groups(const pe::SystemGroupsArgs* a, const pe::SysStopArgs* s,
+                                   const pe::SysMetricsArgs* m, hipStream_t st) {
     const uint32_t span = a->rank_of ? a->n_rows : a->n_list;
     if (!span || !a->n_tg) return hipSuccess;
-    if (!s->resume || !s->stopped || !s->n_stopped) return hipErrorInvalidValue;
+    if (s && (!s->resume || !s->stopped || !s->n_stopped)) return hipErrorInvalidValue;
+    if (m && !sysg_metrics_ok(*m, *a)) return hipErrorInvalidValue;
     uint32_t blocks = (span + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
+    if (blocks > 8192) blocks = 8192;   // grid-stride beyond
+    auto* kernel = s ? (m ? pe::k_system_groups<true, true> : pe::k_system_groups<true, false>)
+                     : (m ? pe::k_system_groups<false, true> : pe::k_system_groups<false, false>);
+    const pe::SysStopArgs sv = s ? *s : pe::SysStopArgs{nullptr, nullptr, nullptr};
+    const pe::SysMetricsArgs mv = m ? *m : pe::SysMetricsArgs{nullptr, -1, 0u, nullptr};
     pe::SystemGroupsArgs c = *a;
     for (uint32_t k0 = 0; k0 < a->n_tg; k0 += pe::kSysGroupsChunk) {
         c.k0 = k0;
         c.nk = a->n_tg - k0 < pe::kSysGroupsChunk ? a->n_tg - k0 : pe::kSysGroupsChunk;
-        hipLaunchKernelGGL(pe::k_system_groups_stop, dim3(blocks), dim3(256), 0, st, c, *s);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, c, sv, mv);
     }
     return hipGetLastError();
 }
 
 // The eviction walk at width `words` over the lanes listed in a->stopped
-// (their count is read on the device; at most `max_lanes`).
-hipError_t pe_launch_system_groups_evict(const pe::SysEvictArgs* a, uint32_t words, uint32_t max_lanes, hipStream_t st) {
+// (their count is read on the device; at most `max_lanes`); `metrics`: its
+// AllocMetric form, which fills a->M.
+hipError_t pe_launch_system_groups_evict(const pe::SysEvictArgs* a, uint32_t words, uint32_t max_lanes, bool metrics,
+                                         hipStream_t st) {
     if (!max_lanes || !a->G.n_tg) return hipSuccess;
     if (!a->pre || !a->resume || !a->stopped || !a->n_stopped || !a->wider || !a->n_wider || !a->app || !a->n_app ||
         !a->flags || !a->preempted || !a->pcount || !a->dev_free_all)
         return hipErrorInvalidValue;
+    if (metrics && !sysg_metrics_ok(a->M, a->G)) return hipErrorInvalidValue;
     uint32_t blocks = (max_lanes + 255) / 256;
     if (blocks > 1024) blocks = 1024;   // grid-stride beyond
-    if (words == 1u) hipLaunchKernelGGL(pe::k_system_groups_evict<1>, dim3(blocks), dim3(256), 0, st, *a);
-    else if (words == 8u) hipLaunchKernelGGL(pe::k_system_groups_evict<8>, dim3(blocks), dim3(256), 0, st, *a);
-    else if (words == 32u) hipLaunchKernelGGL(pe::k_system_groups_evict<32>, dim3(blocks), dim3(256), 0, st, *a);
+    void (*kernel)(pe::SysEvictArgs) = nullptr;
+    if (words == 1u) kernel = metrics ? pe::k_system_groups_evict<1, true> : pe::k_system_groups_evict<1>;
+    else if (words == 8u) kernel = metrics ? pe::k_system_groups_evict<8, true> : pe::k_system_groups_evict<8>;
+    else if (words == 32u) kernel = metrics ? pe::k_system_groups_evict<32, true> : pe::k_system_groups_evict<32>;
     else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-// The AllocMetric forms, chunked and sized as the plain ones.
-// `s` null: the walk to the end (k_system_groups' form), else the stopping form.
-hipError_t pe_launch_system_groups_metrics(const pe::SystemGroupsArgs* a, const pe::SysStopArgs* s,
-                                           const pe::SysMetricsArgs* m, hipStream_t st) {
-    const uint32_t span = a->rank_of ? a->n_rows : a->n_list;
-    if (!span || !a->n_tg) return hipSuccess;
-    if (!m->first || (m->dev_group >= 0 && !m->dev_named) || m->dev_group >= (int32_t)a->n_tg || m->n_list != a->n_list)
-        return hipErrorInvalidValue;
-    if (s && (!s->resume || !s->stopped || !s->n_stopped)) return hipErrorInvalidValue;
-    uint32_t blocks = (span + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    pe::SystemGroupsArgs c = *a;
-    const pe::SysStopArgs none{nullptr, nullptr, nullptr};
-    for (uint32_t k0 = 0; k0 < a->n_tg; k0 += pe::kSysGroupsChunk) {
-        c.k0 = k0;
-        c.nk = a->n_tg - k0 < pe::kSysGroupsChunk ? a->n_tg - k0 : pe::kSysGroupsChunk;
-        if (s) hipLaunchKernelGGL(pe::k_system_groups_metrics<true>, dim3(blocks), dim3(256), 0, st, c, *s, *m);
-        else hipLaunchKernelGGL(pe::k_system_groups_metrics<false>, dim3(blocks), dim3(256), 0, st, c, none, *m);
-    }
-    return hipGetLastError();
-}
-
-hipError_t pe_launch_system_groups_evict_metrics(const pe::SysEvictArgs* a, uint32_t words, uint32_t max_lanes,
-                                                 hipStream_t st) {
-    const pe::SysMetricsArgs* m = &a->M;
-    if (!max_lanes || !a->G.n_tg) return hipSuccess;
-    if (!a->pre || !a->resume || !a->stopped || !a->n_stopped || !a->wider || !a->n_wider || !a->app || !a->n_app ||
-        !a->flags || !a->preempted || !a->pcount || !a->dev_free_all)
-        return hipErrorInvalidValue;
-    if (!m->first || (m->dev_group >= 0 && !m->dev_named) || m->dev_group >= (int32_t)a->G.n_tg ||
-        m->n_list != a->G.n_list)
-        return hipErrorInvalidValue;
-    uint32_t blocks = (max_lanes + 255) / 256;
-    if (blocks > 1024) blocks = 1024;   // grid-stride beyond
-    if (words == 1u) hipLaunchKernelGGL((pe::k_system_groups_evict<1, true>), dim3(blocks), dim3(256), 0, st, *a);
-    else if (words == 8u) hipLaunchKernelGGL((pe::k_system_groups_evict<8, true>), dim3(blocks), dim3(256), 0, st, *a);
-    else if (words == 32u) hipLaunchKernelGGL((pe::k_system_groups_evict<32, true>), dim3(blocks), dim3(256), 0, st, *a);
-    else return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, *a);
     return hipGetLastError();
 }
 

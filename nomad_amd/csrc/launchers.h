@@ -9,13 +9,10 @@ size_t pe_place_lds_bytes(bool full, int hash_bits, bool packed, size_t pset_byt
 hipError_t pe_launch_place(const pe::BatchArgs* a, uint32_t n_evals, bool full, hipStream_t st);
 hipError_t pe_launch_system(const pe::SystemArgs* a, hipStream_t st);
 hipError_t pe_launch_inplace(const pe::InplaceArgs* a, hipStream_t st);
-hipError_t pe_launch_system_groups(const pe::SystemGroupsArgs* a, hipStream_t st);
-hipError_t pe_launch_system_groups_stop(const pe::SystemGroupsArgs* a, const pe::SysStopArgs* s, hipStream_t st);
-hipError_t pe_launch_system_groups_evict(const pe::SysEvictArgs* a, uint32_t words, uint32_t max_lanes, hipStream_t st);
-hipError_t pe_launch_system_groups_metrics(const pe::SystemGroupsArgs* a, const pe::SysStopArgs* s,
-                                           const pe::SysMetricsArgs* m, hipStream_t st);
-hipError_t pe_launch_system_groups_evict_metrics(const pe::SysEvictArgs* a, uint32_t words, uint32_t max_lanes,
-                                                 hipStream_t st);
+hipError_t pe_launch_system_groups(const pe::SystemGroupsArgs* a, const pe::SysStopArgs* s_or_null,
+                                   const pe::SysMetricsArgs* m_or_null, hipStream_t st);
+hipError_t pe_launch_system_groups_evict(const pe::SysEvictArgs* a, uint32_t words, uint32_t max_lanes, bool metrics,
+                                         hipStream_t st);
 hipError_t pe_launch_system_compact(const pe::SysCompactArgs* a, hipStream_t st);
 hipError_t pe_launch_rank_of(const uint32_t* list, uint32_t n_list, uint32_t* rank_of, uint32_t n_rows, hipStream_t st);
 hipError_t pe_launch_upload(void* dst, const void* src_mapped, size_t bytes, hipStream_t st);

@@ -157,9 +157,11 @@ def _after(st, rows, extra):
                                                   np.bincount(ss, minlength=3)[:3].reshape(1, 3), p)
 
 
-def _parity(nodes, allocs, job, rows, tgs, extra, oracle=None, cfg=None):
+def _parity(nodes, allocs, job, rows, tgs, extra, oracle=None, cfg=None, after_rows=None):
     """The batched call (a), the sequential calls (b) and the oracle loop (o),
-    compared; returns the three stacks' results."""
+    compared; returns the three stacks' results. `after_rows`: the list of the
+    further SystemPlace (default: the call's)."""
+    after_rows = rows if after_rows is None else after_rows
     a = _setup(_engine(config=cfg), nodes, allocs, job, rows)
     b = _setup(_engine(config=cfg), nodes, allocs, job, rows)
     ra = a.SystemPlaceGroups(tgs, fallback=False)
@@ -167,13 +169,13 @@ def _parity(nodes, allocs, job, rows, tgs, extra, oracle=None, cfg=None):
     if oracle is None:
         o = _setup(OracleSystemStack(config=cfg), nodes, allocs, job, rows)
         ro = system_place_groups_by_select(o, tgs)
-        eo, xo = _after(o, rows, extra)
+        eo, xo = _after(o, after_rows, extra)
     else:
         ro, eo, xo = oracle
     _same_exact(ra, rb)
     _same_oracle(ra, ro)
-    ea, xa = _after(a, rows, extra)
-    eb, xb = _after(b, rows, extra)
+    ea, xa = _after(a, after_rows, extra)
+    eb, xb = _after(b, after_rows, extra)
     assert ea == eb == eo
     _same_exact(xa, xb)
     _same_oracle(xa, xo)
@@ -234,6 +236,30 @@ def test_list_order_form():
     nodes, allocs, job = _c4()
     order = (WEB, BIG, TINY)
     _parity(nodes, allocs, job, _c4_rows(500), list(order), EXTRA, oracle=_c4_oracle(order, 500))
+
+
+def _half_listed(n, seed):
+    """Half of an n-row snapshot, shuffled: 4 * len >= n takes the row-order
+    form, and every wave of 64 rows holds rows that are not listed."""
+    rows = np.ascontiguousarray(synth.shuffle(n, seed)[:n // 2])
+    listed = np.zeros(n, dtype=bool)
+    listed[rows] = True
+    assert all(listed[w:w + 64].any() and not listed[w:w + 64].all() for w in range(0, n, 64))
+    return rows
+
+
+@gpu
+def test_row_order_form_with_unlisted_rows():
+    """150 of 300 rows listed: in the row-order form the unlisted rows are lanes
+    without a node inside every wave, which take part in the wave's ballots.
+    The further SystemPlace runs over all 300 rows: the rows the call must not
+    have touched are compared too."""
+    nodes, allocs = synth.cluster_c4(300, seed=11)
+    job = _c4()[2]
+    rows = _half_listed(300, 7)
+    _, _, ro = _parity(nodes, allocs, job, rows, [WEB, BIG, TINY], EXTRA,
+                       after_rows=np.arange(300, dtype=np.uint32))
+    assert (ro[1] == 0).any() and (ro[1] == 2).any()   # placed and exhausted entries
 
 
 @gpu

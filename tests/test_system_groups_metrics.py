@@ -199,18 +199,22 @@ def _after(st, rows, extra):
                                                   np.bincount(ss, minlength=3)[:3].reshape(1, 3), p, {})
 
 
-def _oracle_run(nodes, allocs, job, rows, tgs, cfg, extra):
+def _oracle_run(nodes, allocs, job, rows, tgs, cfg, extra, after_rows=None):
     o = _setup(OracleSystemStack(config=cfg), nodes, allocs, job, rows)
     ro = system_place_groups_metrics_by_select(o, list(tgs))
-    return (ro,) + (_after(o, rows, extra) if extra is not None else (None, None))
+    after_rows = rows if after_rows is None else after_rows
+    return (ro,) + (_after(o, after_rows, extra) if extra is not None else (None, None))
 
 
-def _parity(nodes, allocs, job, rows, tgs, cfg=PLAIN, dev_k=None, extra=None, oracle=None, staged=False):
+def _parity(nodes, allocs, job, rows, tgs, cfg=PLAIN, dev_k=None, extra=None, oracle=None, staged=False,
+            after_rows=None):
     """The batched call with metrics on (a), the helper on a second engine
     handle with metrics on (b) and on the oracle (o), SystemPlaceGroupsPreempt
-    on a third handle with metrics off (c)."""
+    on a third handle with metrics off (c). `after_rows`: the list of the
+    further SystemPlace (default: the call's)."""
     tgs = list(tgs)
-    ro, eo, xo = oracle if oracle is not None else _oracle_run(nodes, allocs, job, rows, tgs, cfg, extra)
+    after_rows = rows if after_rows is None else after_rows
+    ro, eo, xo = oracle if oracle is not None else _oracle_run(nodes, allocs, job, rows, tgs, cfg, extra, after_rows)
     a = _setup(_engine(config=cfg), nodes, allocs, job, rows)
     b = _setup(_engine(config=cfg), nodes, allocs, job, rows)
     c = _setup(_engine(config=cfg), nodes, allocs, job, rows, metrics=False)
@@ -225,8 +229,8 @@ def _parity(nodes, allocs, job, rows, tgs, cfg=PLAIN, dev_k=None, extra=None, or
         a.LastMetrics()
     assert getattr(e.value, "code", None) == abi.PE_ESTATE
     if extra is not None:
-        ea, xa = _after(a, rows, extra)
-        eb, xb = _after(b, rows, extra)
+        ea, xa = _after(a, after_rows, extra)
+        eb, xb = _after(b, after_rows, extra)
         assert ea == eb == eo
         _same_exact(xa, xb)
         _same_oracle(xa, xo)
@@ -391,6 +395,27 @@ def test_preempting_stack(order):
     assert any(key in ra[4] for key in ra[5]["scores"])                # a device entry placed by eviction
     assert any(key not in ra[4] for key in ra[5]["scores"])            # and plainly placed ones
     assert len({key[1] for key in ra[4]}) >= 2
+
+
+@gpu
+@pytest.mark.parametrize("cfg", [PLAIN, PRE], ids=["plain", "preempting"])
+def test_row_order_form_with_unlisted_rows(cfg):
+    """150 of 300 rows listed: in the row-order form the unlisted rows are lanes
+    without a node inside every wave, which take part in the wave's ballots and
+    reductions; the first-failure positions and the device group's named scores
+    are by list position, not by row. The further SystemPlace runs over all 300
+    rows: the rows the call must not have touched are compared too."""
+    nodes, allocs, job = _c5()
+    rows = np.ascontiguousarray(synth.shuffle(300, 12)[:150])
+    listed = np.zeros(300, dtype=bool)
+    listed[rows] = True
+    assert 4 * len(rows) >= 300   # the row-order form
+    assert all(listed[w:w + 64].any() and not listed[w:w + 64].all() for w in range(0, 300, 64))
+    _, _, ro = _parity(nodes, allocs, job, rows, (GPU_TG, BIG, NET), cfg=cfg, dev_k=0, extra=EXTRA,
+                       after_rows=np.arange(300, dtype=np.uint32))
+    assert (ro[1] == 0).any() and (ro[1] == 2).any()   # placed and exhausted entries
+    assert ro[5]["failed"] and ro[5]["scores"]
+    assert (len(ro[4]) >= 1) == (cfg is PRE)           # evicting entries on the preempting stack
 
 
 # -- nine groups on 40 nodes: across the 8-group chunk

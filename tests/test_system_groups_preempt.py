@@ -140,12 +140,13 @@ def _same_oracle(a, o):
         assert a[4] == o[4]   # the preempted allocs of every evicting entry
 
 
-def _after(st, rows, extra, tg):
+def _after(st, rows, extra, tg, after_rows=None):
     """What the tests compare after the placements: the eligibility maps, a
-    further SystemPlace of a group that was not listed, and one per-Select
-    Select with Preempt of `tg` over the first rows of the list."""
+    further SystemPlace of a group that was not listed (over `after_rows`,
+    default the list), and one per-Select Select with Preempt of `tg` over the
+    first rows of the list."""
     el = st.Eligibility()
-    st.SetNodes(rows)
+    st.SetNodes(rows if after_rows is None else after_rows)
     sc, ss, p = st.SystemPlace(extra)
     st.SetNodes(rows[:16])
     r = st.SelectRaw(tg, SelectOptions(preempt=True))
@@ -172,16 +173,18 @@ def _does_its_work(ro):
     assert all(st[pos, k] == 0 for (pos, k) in pre)
 
 
-def _parity(nodes, allocs, job, rows, tgs, extra, oracle=None, cfg=PRE, staged=False, check=True, before=None):
+def _parity(nodes, allocs, job, rows, tgs, extra, oracle=None, cfg=PRE, staged=False, check=True, before=None,
+            after_rows=None):
     """The batched call (a), the sequential calls (b) and the oracle loop (o),
     compared; returns the engine stacks and the results. `before`: run on
-    each stack after its setup."""
+    each stack after its setup. `after_rows`: the list of the further
+    SystemPlace (default: the call's)."""
     before = before or (lambda st: None)
     if oracle is None:
         o = _setup(OracleSystemStack(config=cfg), nodes, allocs, job, rows)
         before(o)
         ro = system_place_groups_preempt_by_select(o, tgs)
-        eo, xo, so = _after(o, rows, extra, tgs[0])
+        eo, xo, so = _after(o, rows, extra, tgs[0], after_rows)
     else:
         ro, eo, xo, so = oracle
     if check:
@@ -194,8 +197,8 @@ def _parity(nodes, allocs, job, rows, tgs, extra, oracle=None, cfg=PRE, staged=F
     rb = _sequential(b, tgs)
     _same_exact(ra, rb)
     _same_oracle(ra, ro)
-    ea, xa, sa = _after(a, rows, extra, tgs[0])
-    eb, xb, sb = _after(b, rows, extra, tgs[0])
+    ea, xa, sa = _after(a, rows, extra, tgs[0], after_rows)
+    eb, xb, sb = _after(b, rows, extra, tgs[0], after_rows)
     assert ea == eb == eo
     _same_exact(xa, xb)
     _same_oracle(xa, xo)
@@ -263,6 +266,23 @@ def test_list_order_form():
     nodes, allocs, job = _c5(300, 9)
     order = (GPU_TG, BIG, NET)
     _parity(nodes, allocs, job, _c5_rows(300, 12, 60), list(order), EXTRA, oracle=_c5_oracle(300, 9, 12, order, 60))
+
+
+@gpu
+def test_row_order_form_with_unlisted_rows():
+    """150 of 300 rows listed: in the row-order form the unlisted rows are lanes
+    without a node inside every wave of the stopping pass, which take part in
+    the wave's ballots. The further SystemPlace runs over all 300 rows: the
+    rows the call must not have touched are compared too."""
+    nodes, allocs, job = _c5(300, 9)
+    rows = _c5_rows(300, 12, 150)
+    listed = np.zeros(300, dtype=bool)
+    listed[rows] = True
+    assert 4 * len(rows) >= 300   # the row-order form
+    assert all(listed[w:w + 64].any() and not listed[w:w + 64].all() for w in range(0, 300, 64))
+    _, _, ro = _parity(nodes, allocs, job, rows, [GPU_TG, BIG, NET], EXTRA, after_rows=np.arange(300, dtype=np.uint32))
+    assert (ro[1] == 0).any() and (ro[1] == 2).any()   # placed and exhausted entries
+    assert len(ro[4]) >= 1                             # and evicting ones
 
 
 def _nine():
