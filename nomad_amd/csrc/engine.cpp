@@ -2616,6 +2616,15 @@ struct MdIndex {
         for (auto& x : extra) if (x.first == ip && x.second == v) return true;
         return false;
     }
+    // AssignPorts of the group network (network.go:317-363): its static ports
+    // on the host network's address, one dynamic port left in the range.
+    bool group_ok() const {
+        if (!g->has_network) return true;
+        for (auto& rp : g->rports)
+            if (alias_ip == PE_NONE || rp.first < 0 || rp.first >= 65536 || port_used(alias_ip, rp.first)) return false;
+        if (g->ask.tg_dyn > 0 && (alias_ip == PE_NONE || pe::kDynPortCapacity - dyn - g->ask.static_dyn < 1)) return false;
+        return true;
+    }
     // One AssignNetwork (yieldIP over the networks, one address each):
     // bandwidth, the ask's ReservedPorts on the address, the dynamic ports.
     // The refusal is the last network's (err is overwritten per address).
@@ -2684,20 +2693,23 @@ static void go_sort_by(std::vector<uint32_t>& v, const std::vector<double>& key)
     if (!v.empty()) pe::go_sort(v.data(), (int)v.size(), Less{key.data()});
 }
 
-// PreemptForNetwork (preemption.go:270-455) for the task network's ask on a
-// multi-device node, then the retried AssignNetwork; the same steps as the
-// device's preempt_for_network (evict.inc), with the candidates grouped by
-// device. Fills the MdNet's ev / pre and *choice (kMdPre).
-static void md_preempt(const MdIndex& x0, const std::map<std::tuple<uint32_t, uint32_t, uint32_t>, int>& pcount,
-                       pe::MdNet* m, int* choice) {
+using MdPcount = std::map<std::tuple<uint32_t, uint32_t, uint32_t>, int>;
+using MdPorts = std::vector<std::pair<int32_t, uint32_t>>;
+
+// PreemptForNetwork (preemption.go:270-455) on a multi-device node for an ask
+// of `needed` MBits and the ReservedPorts `ports` (the task network's, or the
+// group network's with no MBits): the same steps as the device's
+// preempt_for_network (evict.inc), with the candidates grouped by device.
+// Returns kMdPre with the allocs to preempt in *res (CSR-relative), kMdSkip
+// for PreemptForNetwork's nil, or kMdUnsup.
+static uint8_t md_for_network(const MdIndex& x0, const MdPcount& pcount, int32_t needed, const MdPorts& ports,
+                              std::vector<uint32_t>* res) {
     pe_stack* s = x0.s;
-    const TgPlan& g = *x0.g;
-    const int32_t needed = g.ask.task_mbits;
     std::vector<uint32_t> lst;
     std::map<uint32_t, std::set<int32_t>> filtered;
     std::set<uint32_t> devs;
     for (uint32_t k = x0.b; k < x0.e; k++) {
-        if (s->h_preempted[k]) continue;
+        if (s->h_preempted[k] || x0.removed[k - x0.b]) continue;
         const HostAlloc& a = s->allocs[s->h_palloc_index[k]];
         if ((a.job == s->job_id && a.ns == s->job_ns) || !a.has_net) continue;   // SetCandidates; Networks[0]
         const uint32_t d = x0.alloc_dev(a);
@@ -2708,32 +2720,31 @@ static void md_preempt(const MdIndex& x0, const std::map<std::tuple<uint32_t, ui
         devs.insert(d);
         lst.push_back(k - x0.b);
     }
-    m->ev = pe::kMdSkip;
-    if (devs.empty()) return;
-    if (devs.size() > 1) { m->ev = pe::kMdUnsup; return; }   // deviceToAllocs in Go map order
+    if (devs.empty()) return pe::kMdSkip;
+    if (devs.size() > 1) return pe::kMdUnsup;   // deviceToAllocs in Go map order
     const uint32_t D = *devs.begin();
     const int32_t total = x0.avail_of(D);
-    if (total < needed) return;
+    if (total < needed) return pe::kMdSkip;
     int32_t used_d = 0;
     for (auto& u : x0.used) if (u.first == D) used_d = u.second;
     const int32_t free_bw = total - used_d;
     auto al = [&](uint32_t rel) -> const HostAlloc& { return s->allocs[s->h_palloc_index[x0.b + rel]]; };
     std::vector<uint32_t> pre;
     int32_t pbw = 0;
-    if (!g.trports.empty()) {   // the reserved ports first (preemption.go:309-342)
+    if (!ports.empty()) {   // the reserved ports first (preemption.go:309-342)
         std::map<int32_t, uint32_t> holder;
         for (uint32_t rel : lst) {
             const HostAlloc& a = al(rel);
             for (uint32_t q = a.port_begin; q < a.port_end; q++) holder[s->alloc_ports[q].second] = rel;
         }
-        for (auto& rp : g.trports) {
+        for (auto& rp : ports) {
             auto it = holder.find(rp.first);
             if (it != holder.end()) {
-                if (std::find(pre.begin(), pre.end(), it->second) != pre.end()) { m->ev = pe::kMdUnsup; return; }
+                if (std::find(pre.begin(), pre.end(), it->second) != pre.end()) return pe::kMdUnsup;
                 pbw += al(it->second).mbits;
                 pre.push_back(it->second);
             } else if (filtered[D].count(rp.first)) {
-                return;   // a higher-priority alloc holds it: the next device, and there is none
+                return pe::kMdSkip;   // a higher-priority alloc holds it: the next device, and there is none
             }
         }
         size_t n = lst.size();   // RemoveAllocs: swap with the last
@@ -2767,7 +2778,7 @@ static void md_preempt(const MdIndex& x0, const std::map<std::tuple<uint32_t, ui
             if (pbw + free_bw >= needed) { met = true; break; }
         }
     }
-    if (!met || pre.empty()) return;
+    if (!met || pre.empty()) return pe::kMdSkip;
     for (uint32_t rel : pre) key[rel] = -dist(rel);   // filterSuperset: distance descending
     go_sort_by(pre, key);
     int32_t avail = free_bw;
@@ -2777,22 +2788,55 @@ static void md_preempt(const MdIndex& x0, const std::map<std::tuple<uint32_t, ui
         avail += al(rel).mbits;
         if (avail != 0 && needed != 0 && avail >= needed) break;
     }
-    if (out.size() > 8 || *std::max_element(out.begin(), out.end()) > 254u) { m->ev = pe::kMdUnsup; return; }
-    // the retried AssignNetwork on a fresh index of the remaining allocs: the
-    // group's port offer is not in it (rank.go:362-371)
-    MdIndex x1 = x0;
+    *res = out;
+    return pe::kMdPre;
+}
+
+// `out` leaves the proposed list (RemoveAllocs, then a fresh NetworkIndex of
+// the rest).
+static void md_remove(MdIndex& x, const std::vector<uint32_t>& out) {
     for (uint32_t rel : out) {
-        const HostAlloc& a = al(rel);
-        x1.removed[rel] = 1;
-        if (a.mbits) x1.used_of(x1.alloc_dev(a)) -= a.mbits;
-        x1.dyn -= a.dyn;
+        const HostAlloc& a = x.s->allocs[x.s->h_palloc_index[x.b + rel]];
+        x.removed[rel] = 1;
+        if (a.mbits) x.used_of(x.alloc_dev(a)) -= a.mbits;
+        x.dyn -= a.dyn;
     }
+}
+
+// The Preempt Select's network steps on a multi-device node (rank.go:248-379)
+// when an offer fails on the state `x`: with `group`, AssignPorts of the group
+// network failed, so PreemptForNetwork on the group's ask (no MBits, its
+// static ports) and the retried AssignPorts; then AssignNetwork of the task
+// network and, where that fails, PreemptForNetwork on the task's ask and the
+// retry on a fresh index of the remaining allocs (the group's port offer is
+// not in it, rank.go:362-371). Fills the MdNet's ev / pre and *choice (kMdPre).
+static void md_preempt(MdIndex x, const MdPcount& pcount, bool group, pe::MdNet* m, int* choice) {
+    const TgPlan& g = *x.g;
+    const int32_t tg_part = g.ask.tg_dyn > 0 ? g.ask.tg_dyn + g.ask.static_dyn : 0;
+    std::vector<uint32_t> all, out;
     uint32_t code;
-    if (!x1.assign(x1.dyn, choice, &code)) return;
+    m->ev = pe::kMdSkip;
+    bool fits = false;
+    if (group) {
+        const uint8_t ev = md_for_network(x, pcount, 0, g.rports, &out);
+        if (ev != pe::kMdPre) { m->ev = ev; return; }
+        all = out;
+        md_remove(x, out);
+        if (!x.group_ok()) return;
+        fits = x.assign(x.dyn + tg_part, choice, &code);
+    }
+    if (!fits) {
+        const uint8_t ev = md_for_network(x, pcount, g.ask.task_mbits, g.trports, &out);
+        if (ev != pe::kMdPre) { m->ev = ev; return; }
+        all.insert(all.end(), out.begin(), out.end());
+        md_remove(x, out);
+        if (!x.assign(x.dyn, choice, &code)) return;
+    }
+    if (all.size() > 8 || *std::max_element(all.begin(), all.end()) > 254u) { m->ev = pe::kMdUnsup; return; }
     m->ev = pe::kMdPre;
-    m->n_pre = (uint8_t)out.size();
+    m->n_pre = (uint8_t)all.size();
     m->pre = ~0ull;
-    for (size_t i = 0; i < out.size(); i++) m->pre = (m->pre & ~(0xFFull << (8 * i))) | ((uint64_t)out[i] << (8 * i));
+    for (size_t i = 0; i < all.size(); i++) m->pre = (m->pre & ~(0xFFull << (8 * i))) | ((uint64_t)all[i] << (8 * i));
 }
 
 // The group's MdNet per node (TgTables::md) from the host mirror: the plan's
@@ -2829,8 +2873,11 @@ static int build_md(pe_stack* s, TgPlan& g) {
         else ++it;
     }
     const int32_t tg_part = g.ask.tg_dyn > 0 ? g.ask.tg_dyn + g.ask.static_dyn : 0;
-    const bool changes = g.ask.commit_mbits != 0 || g.ask.commit_dyn != 0 ||
-                         (g.has_network && g.net_ports > 0 ? !g.rports.empty() : !g.trports.empty());
+    // whether a placement changes anything assign() reads (the device's used
+    // bandwidth, the dynamic count, the task ports in `extra`): the group
+    // ports apply() records are the static gate's, never assign()'s
+    const bool shared = g.has_network && g.net_ports > 0;
+    const bool changes = g.ask.commit_mbits != 0 || g.ask.commit_dyn != 0 || (!shared && !g.trports.empty());
     for (uint32_t r = 0; r < n; r++) {
         if (!md_node(s, r)) continue;
         MdIndex x;
@@ -2881,12 +2928,13 @@ static int build_md(pe_stack* s, TgPlan& g) {
         // the Preempt Select's verdict (built on this state; the Select rebuilds)
         int ch0 = -1;
         uint32_t code0 = 0;
-        if (x.assign(x.dyn + tg_part, &ch0, &code0)) {
+        m.gpre = x.group_ok() ? 0 : 1;   // the group's AssignPorts fails: its PreemptForNetwork comes first
+        if (!m.gpre && x.assign(x.dyn + tg_part, &ch0, &code0)) {
             m.ev = pe::kMdFit;
             g.md_vdev[r] = (uint8_t)ch0;
         } else {
             int chp = -1;
-            md_preempt(x, pcount, &m, &chp);
+            md_preempt(x, pcount, m.gpre != 0, &m, &chp);
             if (m.ev == pe::kMdPre) g.md_vdev[r] = (uint8_t)chp;
         }
         // first fit for the plain Selects: placements admitted, the refusal after

@@ -104,13 +104,15 @@ struct NodeSoA {
 // coll: the offer fits as is, PreemptForNetwork (preemption.go:270-455)
 // preempts the listed allocs (CSR-relative indices, one byte each) and the
 // retried offer fits, the node is skipped, or outside the modelled surface
-// (candidates on two devices: the reference ranges over a Go map).
+// (candidates on two devices: the reference ranges over a Go map). `gpre`:
+// at that state the group network's AssignPorts fails, and `ev` / `pre` hold
+// the group's PreemptForNetwork and retry followed by the task network's.
 enum : uint8_t { kMdFit = 0, kMdPre = 1, kMdSkip = 2, kMdUnsup = 3 };
 constexpr uint32_t kMdCoded = 1u << 17;         // a kTrTaskStatic code whose port index is in bits 8-15
 constexpr uint32_t kMdInvalidPort = 1u << 16;   // ... and that port is out of range
 struct alignas(8) MdNet {
     uint32_t lim, coll, code;
-    uint8_t ev, n_pre, _pad[2];
+    uint8_t ev, n_pre, gpre, _pad;
     uint64_t pre;
 };
 static_assert(sizeof(MdNet) == 24, "MdNet is 24 bytes");

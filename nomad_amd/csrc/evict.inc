@@ -628,14 +628,18 @@ __device__ int evict_eval(const PreemptArgs& A, uint32_t row, NodeEval* out, AMa
                 if (np.test(i)) { bw -= c.na[i].mbits; dyn -= c.na[i].dyn; }
         };
         int32_t idx_dyn = dyn;
+        bool md_group = false;   // a multi-device node whose group offer failed: the host's verdict covers it
         if (a.tg_dyn > 0 || t.static_gate) {
             const bool alias = !(t.alias_ok && !t.alias_ok[row]);
             auto dyn_ok = [&]() { return a.tg_dyn == 0 || (alias && kDynPortCapacity - dyn - a.static_dyn >= 1); };
-            if (!g_ok || !dyn_ok()) {
+            if (md && (!g_ok || !dyn_ok())) {
+                // candidates grouped per device: the host ran the group's
+                // PreemptForNetwork and retry before the task network's (MdNet::gpre)
+                md_group = true;
+            } else if (!g_ok || !dyn_ok()) {
                 // AssignPorts failed (rank.go:265-300): PreemptForNetwork on the
                 // group's ask (no MBits; its static ports' holders first)
                 if (!ctx_ok) { *unsupported |= kEvictWider; return kFiltered; }
-                if (md) { *unsupported |= kEvictUnsup; return kFiltered; }   // candidates grouped per device
                 if (t.static_gate && (pinfo & kPortUnsup)) { *unsupported |= kEvictUnsup; return kFiltered; }
                 const Mask np = t.static_gate ? preempt_for_network(c, 0, total, bw, pdep, plist, pinfo)
                                               : preempt_for_network(c, 0, total, bw, pdep);
@@ -652,7 +656,10 @@ __device__ int evict_eval(const PreemptArgs& A, uint32_t row, NodeEval* out, AMa
             // listed allocs leave and the retried offer fits, or the node is
             // skipped (nil from PreemptForNetwork or from the retry)
             const MdNet m = *md;
-            if (m.ev == kMdUnsup || in.coll_tg != m.coll) { *unsupported |= kEvictUnsup; return kFiltered; }
+            if (m.ev == kMdUnsup || in.coll_tg != m.coll || (m.gpre != 0) != md_group) {
+                *unsupported |= kEvictUnsup;
+                return kFiltered;
+            }
             if (m.ev == kMdSkip) return kSkipped;
             if (m.ev == kMdPre) {
                 if (!ctx_ok) { *unsupported |= kEvictWider; return kFiltered; }
