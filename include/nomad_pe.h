@@ -400,6 +400,9 @@ int pe_last_exchange_stats(const pe_stack* s, double* out4);
 /* Counters of the speculative loop: out[0] runs started, [1] Selects answered
  * from records, [2] rollbacks (the caller deviated), [3] records computed. */
 int pe_speculation_stats(const pe_stack* s, uint64_t* out4);
+/* Counters of the chain's wide phase launches (PE_CHAIN_WIDE): out[0] phases
+ * they resolved, [1] phases they declined (left to k_chain). */
+int pe_chain_wide_stats(const pe_stack* s, uint64_t* out2);
 /* Plan.AppendAlloc plus Plan.AppendPreemptedAlloc of each preempted alloc
  * (handlePreemptions, generic_sched.go:794-816): `preempted` are alloc-table
  * rows, as returned in pe_ranked_node.preempted by a Select with Preempt. */

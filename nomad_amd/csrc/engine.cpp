@@ -488,6 +488,7 @@ struct Tunables {
     bool spin_wait = true;             // PE_SPIN_WAIT=0: chain launches wait with a stream sync
     bool counts_defer_ok = true;       // PE_COUNTS_DEFER=0: SetJob launches its counts at once
     bool kernel_split = false;         // PE_KERNEL_SPLIT=1 (or pe_set_kernel_split): per-kernel chain events
+    bool chain_wide = true;            // PE_CHAIN_WIDE=0: no wide phase launches before k_chain
     // profiling, printed to stderr
     bool api_prof = false;             // PE_API_PROF=1
     bool place_prof = false;           // PE_PLACE_PROF set
@@ -516,6 +517,7 @@ static Tunables read_tunables() {
     flag("PE_SPIN_WAIT", &t.spin_wait);
     flag("PE_COUNTS_DEFER", &t.counts_defer_ok);
     flag("PE_KERNEL_SPLIT", &t.kernel_split);
+    flag("PE_CHAIN_WIDE", &t.chain_wide);
     flag("PE_API_PROF", &t.api_prof);
     t.place_prof = is_set("PE_PLACE_PROF");
     t.chain_prof = is_set("PE_CHAIN_PROF");
@@ -702,6 +704,9 @@ struct pe_stack {
     PinnedMem h_stage;                 // upload staging ring (upload_s)
     unsigned char* stage_dev = nullptr;   // the ring as seen from the device (k_upload reads it)
     DevMem d_emit, d_emit_ov, d_emit_n;   // k_chain deferred records (k_emit)
+    // wide phases (k_phase): bitmaps (6 of k_base's, 2 of winners), slot per
+    // position, [seeds | error word], [phases resolved, declined]
+    DevMem d_wide_bits, d_wide_slot, d_wide_state, d_wide_stats;
     size_t stage_off = 0;
     double phase_ms[4] = {0, 0, 0, 0};   // host prep, kernels, result copy, total (last batch)
     std::vector<pe::NodeRec> h_base_rec;     // snapshot proposed state (no plan)
@@ -4759,6 +4764,26 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
         A.emit_out = s->h_emit_out.dev<pe::EmitRec>();
         if (!A.emit_out) return s->fail(PE_EHIP, "mapped result buffers unavailable");
         A.full_out = nullptr;
+        // a rotation's Selects on many CUs before k_chain (k_phase): the
+        // unfused chain of one window with a writeback, plain asks
+        if (!fused && s->tun.chain_wide && n > 0 && (uint32_t)n <= pe_chain_max_n() && commit &&
+            A.ask.n_dev == 0 && A.ask.cores == 0) {
+            const uint32_t words = ((uint32_t)n + 31u) / 32u;
+            HIP_TRY(s, s->d_wide_bits.ensure(sizeof(uint32_t) * 8u * words));
+            HIP_TRY(s, s->d_wide_slot.ensure(sizeof(uint32_t) * (size_t)n));
+            HIP_TRY(s, s->d_wide_state.ensure(2 * sizeof(pe::ChainSeed) + 16));
+            if (!s->d_wide_stats.p) {
+                HIP_TRY(s, s->d_wide_stats.ensure(2 * sizeof(unsigned long long)));
+                HIP_TRY(s, hipMemsetAsync(s->d_wide_stats.p, 0, 2 * sizeof(unsigned long long), s->stream));
+            }
+            A.wide.bits = s->d_wide_bits.as<uint32_t>();
+            A.wide.won = A.wide.bits + 6u * (size_t)words;
+            A.wide.slot = s->d_wide_slot.as<uint32_t>();
+            A.wide.seed = s->d_wide_state.as<pe::ChainSeed>();
+            A.wide.err = reinterpret_cast<uint32_t*>(A.wide.seed + 2);
+            A.wide.stats = s->d_wide_stats.as<unsigned long long>();
+            A.wide.words = words;
+        }
     }
     double total_ms = 0;
     uint32_t done = 0;
@@ -4785,6 +4810,7 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
         const uint32_t c = std::min(chunk, count - done);
         A.count = c;
         A.offset0 = *new_offset;
+        A.wide.phases = (uint64_t)c * A.limit > (uint64_t)n ? 2u : 1u;
         const double t0 = hprof ? now_us() : 0.0;
         if (spin) {
             A.done_seq = ++s->place_seq;
@@ -4892,6 +4918,7 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
             A.base_by_pos = 0;
             A.emit = nullptr;
             A.emit_out = nullptr;
+            A.wide = pe::ChainWide{};
             A.full_out = s->h_place_out.dev<pe_ranked_node>();
             A.done_flag = nullptr;
             spin = false;
@@ -8651,6 +8678,20 @@ int pe_speculation_stats(const pe_stack* s, uint64_t* out4) {
     if (!s || !out4) return PE_EINVAL;
     view_take(const_cast<pe_stack*>(s));
     for (int i = 0; i < 4; i++) out4[i] = s->spec_stats[i];
+    return PE_OK;
+}
+
+int pe_chain_wide_stats(const pe_stack* cs, uint64_t* out2) {
+    if (!cs || !out2) return PE_EINVAL;
+    pe_stack* s = const_cast<pe_stack*>(cs);
+    view_take(s);
+    out2[0] = out2[1] = 0;
+    if (!s->d_wide_stats.p) return PE_OK;
+    unsigned long long v[2];
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    HIP_TRY(s, hipMemcpy(v, s->d_wide_stats.p, sizeof(v), hipMemcpyDeviceToHost));
+    out2[0] = v[0];
+    out2[1] = v[1];
     return PE_OK;
 }
 

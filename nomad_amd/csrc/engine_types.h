@@ -190,6 +190,32 @@ struct ChainEmit {
     double score;                 // FinalScore
 };
 
+// State the wide phase launches (k_phase) hand on: phase p reads seed[p - 1]
+// (phase 0 the launch's arguments) and stores seed[p]; k_chain starts from the
+// last one. No launch reads a word that a workgroup of the same launch stores.
+struct ChainSeed {
+    uint32_t status;              // kSeedOk, or kSeedDeclined: k_chain resolves the rest
+    uint32_t placed;              // Selects resolved so far
+    uint32_t cur;                 // the cursor after them
+    uint32_t pos_used;            // visit positions they consumed
+};
+constexpr uint32_t kSeedDeclined = 0, kSeedOk = 1;
+
+// A rotation's Selects resolved across many workgroups before k_chain
+// ("wide phases"); bits null: the launch is not armed.
+struct ChainWide {
+    // k_base's bitmaps by visit position, `words` words each: table (base,
+    // base1) x predicate (option, filtered, non-positive option)
+    uint32_t* bits;
+    uint32_t* won;                // 2 x words: positions whose row won in phase 0 / in phase 1
+    uint32_t* slot;               // [n_visit]: the emit_ov slot of a phase 0 winner's position
+    ChainSeed* seed;              // [2]
+    uint32_t* err;                // a bounds guard of k_phase tripped
+    unsigned long long* stats;    // [0] phases resolved, [1] phases declined (pe_chain_wide_stats)
+    uint32_t words;               // ceil(n_visit / 32)
+    uint32_t phases;              // k_phase launches of this chain launch: 1 or 2
+};
+
 // Per-node count arrays rewritten by one k_counts launch (own allocs, job and
 // task-group collisions); null entries are skipped.
 constexpr int kMaxCountDst = 32;
@@ -308,6 +334,7 @@ struct BatchArgs {
     // k_chain scratch, kChainMaxN doubles per workgroup: the window's values
     // by relative position (one thread per Select walks its own positions)
     double* chain_vs;
+    ChainWide wide;               // wide phase launches before k_chain (wide.bits null: none)
     FoldArgs fold;                // a fold carried by this launch (fold.feas null: none)
     CountArgs counts;             // SetJob's counts carried by a fused k_chain (counts.nd 0: none)
     // Short lists, one evaluation: k_chain alone (no k_base / k_emit /

@@ -1578,7 +1578,22 @@ __device__ __forceinline__ double encode_eval(const NodeEval& ev) {
 // of the table, so the main loop's dk == 0 lane stores its row's node_feas and
 // no separate pass over the table runs.
 constexpr int kBaseBlock = 64;
-template <bool FOLD>
+static_assert(kBaseBlock == 64, "k_base's bitmaps: one wave per workgroup, 32 positions x 2 tables");
+
+// bits 0, 2, 4, .. of x packed into the low 32 bits
+__device__ __forceinline__ uint32_t even_bits(uint64_t x) {
+    x &= 0x5555555555555555ull;
+    x = (x | (x >> 1)) & 0x3333333333333333ull;
+    x = (x | (x >> 2)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x >> 16)) & 0x00000000FFFFFFFFull;
+    return (uint32_t)x;
+}
+
+// WIDE: the launch is armed for the wide phases (BatchArgs::wide) and stores
+// their bitmaps; a launch that is not runs the kernel without that code.
+template <bool FOLD, bool WIDE = false>
 __global__ void __launch_bounds__(kBaseBlock) k_base(BatchArgs A) {
     __shared__ uint8_t cls_ok[FOLD ? kFoldMaxClasses : 1];
     const uint32_t stride = gridDim.x * kBaseBlock;
@@ -1656,7 +1671,29 @@ __global__ void __launch_bounds__(kBaseBlock) k_base(BatchArgs A) {
         NodeEval ev;
         ev.score = 0.0;
         eval_loaded<false, false>(A.soa, tg, class_ok, A.ask, dk, A.penalty_bits, A.log10, nullptr, row, in, &ev);
-        (dk ? A.base1 : A.base)[j] = encode_eval(ev);
+        const double v = encode_eval(ev);
+        (dk ? A.base1 : A.base)[j] = v;
+        if (WIDE) {
+            // the wide phases' bitmaps by visit position: a wave holds 32
+            // positions, the two tables' lanes interleaved (a lane past the
+            // list's end is not in the ballot, so the last word ends in zeros)
+            const bool is_o = v > -__builtin_inf() && v < __builtin_inf();
+            const uint64_t bo = __ballot(is_o), bf = __ballot(v == -__builtin_inf()),
+                           bn = __ballot(is_o && v <= 0.0);
+            const uint32_t w = (t - threadIdx.x) >> 6, nw = A.wide.words;
+            if (threadIdx.x == 0 && sh && w < nw) {
+                uint32_t* b = A.wide.bits + w;
+                b[0] = even_bits(bo);
+                b[nw] = even_bits(bo >> 1);
+                b[2 * nw] = even_bits(bf);
+                b[3 * nw] = even_bits(bf >> 1);
+                b[4 * nw] = even_bits(bn);
+                b[5 * nw] = even_bits(bn >> 1);
+                A.wide.won[w] = 0u;
+                A.wide.won[nw + w] = 0u;
+                if (w == 0) *A.wide.err = 0u;
+            }
+        }
     }
 }
 
@@ -1987,8 +2024,11 @@ __device__ __forceinline__ void counts_apply(const CountDsts& D, uint32_t nd, ui
 // the records into the mapped output, writes the placements back and raises
 // done_flag[0].
 constexpr uint32_t kFusedMaxClasses = 4096;
-template <int ITEMS, bool FUSED>
+// WIDE (BatchArgs::wide armed, not FUSED): the kernel starts from what the wide
+// phase launches resolved (ChainSeed); every other launch runs without that code.
+template <int ITEMS, bool FUSED, bool WIDE = false>
 __global__ void __launch_bounds__(kChainBlock) k_chain(BatchArgs A, uint32_t n_evals) {
+    static_assert(!(FUSED && WIDE), "the wide phases precede the unfused chain only");
     using Shp = ChainShape<ITEMS>;
     static_assert(Shp::kMaxN <= (1u << kIdxBits), "option index packing");
     static_assert(kChainMaxSel <= (1 << (32 - 2 * kIdxBits + kIdxBits)), "select id packing");
@@ -2014,6 +2054,25 @@ __global__ void __launch_bounds__(kChainBlock) k_chain(BatchArgs A, uint32_t n_e
     uint16_t* nb = reinterpret_cast<uint16_t*>(ov.keys + (A.packed_overlay ? H : 2 * H));   // [n + 2]
     uint16_t* nx = nb + ((Wfull + 2 + 1) & ~1u);   // [W + 2]: next Select start per option, then Select id per option
 
+    // what the wide phase launches resolved before this one (none: placed 0)
+    ChainSeed seed;
+    seed.status = kSeedDeclined;
+    seed.placed = seed.cur = seed.pos_used = 0;
+    if (WIDE) {
+        seed = A.wide.seed[A.wide.phases - 1];
+        const bool werr = *A.wide.err != 0u || seed.placed > A.count || seed.cur >= (n ? n : 1u);
+        if (werr || seed.placed == A.count) {
+            // a guard of k_phase tripped (the host fails the call), or the
+            // count is reached: the records and the writeback entries are there
+            if (tid == 0) {
+                A.eval_status[0] = werr ? 0u : seed.placed;
+                A.eval_status[1] = werr ? kChainError : seed.cur;
+                A.emit_n[0] = werr ? 0u : seed.placed;
+                A.emit_n[1] = werr || !A.writeback ? 0u : seed.placed;
+            }
+            return;
+        }
+    }
     uint64_t prof_t = A.prof ? __builtin_readcyclecounter() : 0;
     int prof_ph = 0;   // profile slot group: phase (capped at 3)
     if (FUSED && A.counts.nd) {
@@ -2068,6 +2127,26 @@ __global__ void __launch_bounds__(kChainBlock) k_chain(BatchArgs A, uint32_t n_e
             o.row = -1; o.nodes_evaluated = 0; o.final_score = 0.0;
         }
         __syncthreads();
+        if (WIDE && seed.placed) {
+            // the wide phases' placements into the overlay and the position
+            // bitmaps, from their records; the phase loop goes on after them
+            for (uint32_t i = tid; i < seed.placed; i += kChainBlock) {
+                const int32_t r = A.emit[i].row;
+                const uint32_t p = A.emit[i].pos;
+                if (r < 0 || p >= n || n > Shp::kMaxN) {
+                    sh.err = 1u;
+                    continue;
+                }
+                ov_add_atomic(ov, (uint32_t)r);
+                const uint32_t bit = 1u << (p & 31);
+                if (atomicOr(&sh.bm1[p >> 5], bit) & bit) atomicOr(&sh.bm2[p >> 5], bit);
+            }
+            placed = seed.placed;
+            cur = seed.cur;
+            pos_used = seed.pos_used;
+            if (tid == 0) sh.n_emit = placed;
+            __syncthreads();
+        }
         while (!done) {
             PE_PROF_MARK(0);
             // positions of this phase: the full window, or after the first
@@ -2697,6 +2776,7 @@ __global__ void __launch_bounds__(256) k_emit_writeback(BatchArgs A) {
     const uint32_t x = blockIdx.x * 256 + threadIdx.x;
     if (x >= A.emit_n[1]) return;
     const uint2 e = A.emit_ov[x];
+    if (e.y == 0) return;   // a wide phase's second win of a row: counted in the first one's slot
     NodeRec& r = A.soa.rec[e.x];
     r.used_cpu += (int64_t)e.y * ask_cpu(A.soa, A.ask, e.x);
     core_take(A.soa, A.ask, e.x, e.y);
@@ -2707,6 +2787,300 @@ __global__ void __launch_bounds__(256) k_emit_writeback(BatchArgs A) {
     A.soa.coll_job[e.x] += e.y;
     A.tg.coll_tg[e.x] += e.y;
     if (A.ask.n_dev > 0) A.tg.dev_free[e.x] = dev_after(A.ask, A.tg.dev_cls[r.cls], A.tg.dev_free[e.x], e.y);
+}
+
+// ---- wide phases: one rotation's Selects on many CUs ----------------------------
+//
+// Inside one phase of the chain the Selects do not depend on each other (the
+// window's values are fixed at the phase's start, see above), and in the closed
+// form (no non-positive option in the window) Select s returns exactly the
+// options [s L, (s + 1) L) in visit order. All a Select needs beyond the values
+// is the rank of every option: a prefix popcount over k_base's option bitmap,
+// which every workgroup scans for itself (n / 32 words). k_phase(p) resolves
+// phase p of the unfused single-evaluation chain, one Select per lane, and
+// writes the ChainEmit entries k_chain's step 6 would write; k_chain then
+// starts from ChainSeed and has nothing left to do when the count is reached.
+// A phase the closed form does not cover is declined as a whole (nothing but
+// the seed stored) and k_chain resolves it.
+// Launch-to-launch state only: phase p reads seed[p - 1] and won[0] (phase 0's
+// winners), stores seed[p] and won[p], so no workgroup reads what another
+// workgroup of the same launch stores. emit_ov gets one slot per Select: a
+// row's second win (phase 1 on a phase 0 winner) raises the first slot's count
+// to two and leaves its own slot empty.
+constexpr int kWideBlock = 64;
+constexpr uint32_t kWideMaxWords = kChainMaxN / 32;
+static_assert(kWideMaxWords % kWideBlock == 0, "k_phase: whole rounds of bitmap words per lane");
+
+__device__ __forceinline__ void wide_fail(const ChainWide& Wd) { atomicOr(Wd.err, 1u); }
+
+// set bits of the bitmap at absolute positions [0, p), p in [0, n]
+__device__ __forceinline__ uint32_t wide_prefix(const uint32_t* pre, const uint32_t* bits, uint32_t nw, uint32_t p) {
+    const uint32_t w = p >> 5;
+    if (w >= nw) return pre[nw];
+    return pre[w] + (uint32_t)__popc(bits[w] & ((1u << (p & 31u)) - 1u));
+}
+
+// position of the set bit of absolute rank r < pre[nw]; the word index and the
+// word's bits from that one upwards in *w / *rest. False: no such bit.
+__device__ __forceinline__ bool wide_select(const uint32_t* pre, const uint32_t* bits, uint32_t nw, uint32_t r,
+                                            uint32_t* w, uint32_t* rest) {
+    uint32_t lo = 0, hi = nw;   // first word index in [1, nw] whose prefix exceeds r, minus one
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pre[mid + 1] <= r) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= nw) return false;
+    uint32_t word = bits[lo];
+    for (uint32_t k = r - pre[lo]; k; k--) word &= word - 1u;
+    *w = lo;
+    *rest = word;
+    return word != 0u;
+}
+
+__global__ void __launch_bounds__(kWideBlock) k_phase(BatchArgs A, uint32_t phase) {
+    __shared__ uint32_t s_opt[kWideMaxWords], s_fil[kWideMaxWords], s_won[kWideMaxWords];
+    __shared__ uint32_t p_opt[kWideMaxWords + 1], p_fil[kWideMaxWords + 1];
+    const ChainWide& Wd = A.wide;
+    const uint32_t lane = threadIdx.x, n = A.n_visit, L = A.limit, nw = Wd.words;
+    const bool first = blockIdx.x == 0 && lane == 0;   // the one lane that stores the seed
+    if (phase > 1) return;   // a row holds at most one placement per phase: dk <= 1 below
+    // One round of loads for everything the prologue reads: the lane's words
+    // of every bitmap (index clamped to the last word, so no load needs a
+    // guard) and, in phase 1, the seed (a vector load, one field per lane, so
+    // it travels with the rest). All of them have landed at the pins below.
+    constexpr int kPer = (int)(kWideMaxWords / kWideBlock);
+    const bool args_ok = n != 0 && nw == (n + 31u) / 32u && nw <= kWideMaxWords && L != 0 && L <= kMaxChainLimit;
+    uint32_t r_o[kPer], r_f[kPer], r_n[kPer], r_w[kPer], r_seed = 0;
+#pragma unroll
+    for (int i = 0; i < kPer; i++) r_o[i] = r_f[i] = r_n[i] = r_w[i] = 0u;
+    if (args_ok) {
+        if (phase) r_seed = reinterpret_cast<const uint32_t*>(Wd.seed + (phase - 1))[lane & 3u];
+#pragma unroll
+        for (int i = 0; i < kPer; i++) {
+            if ((uint32_t)i * kWideBlock >= nw) break;
+            const uint32_t* b = Wd.bits + min(lane + (uint32_t)i * kWideBlock, nw - 1u);
+            r_o[i] = b[0];
+            r_f[i] = b[2 * nw];
+            r_n[i] = b[4 * nw];
+        }
+        if (phase) {
+            // table 1 where the row won in phase 0
+            uint32_t t_o[kPer], t_f[kPer], t_n[kPer];
+#pragma unroll
+            for (int i = 0; i < kPer; i++) {
+                t_o[i] = t_f[i] = t_n[i] = 0u;
+                if ((uint32_t)i * kWideBlock >= nw) break;
+                const uint32_t wc = min(lane + (uint32_t)i * kWideBlock, nw - 1u);
+                const uint32_t* b = Wd.bits + wc;
+                r_w[i] = Wd.won[wc];
+                t_o[i] = b[nw];
+                t_f[i] = b[3 * nw];
+                t_n[i] = b[5 * nw];
+            }
+            // (the pins: an empty statement the compiler must hand the loaded
+            // registers to, so every load above is issued before the first
+            // value is used. Without them the loads may sink to their uses
+            // behind the seed test and run as one dependent round per word.)
+#pragma unroll
+            for (int i = 0; i < kPer; i++) {
+                asm volatile("" : "+v"(t_o[i]), "+v"(t_f[i]), "+v"(t_n[i]), "+v"(r_w[i]));
+                r_o[i] = (r_o[i] & ~r_w[i]) | (t_o[i] & r_w[i]);
+                r_f[i] = (r_f[i] & ~r_w[i]) | (t_f[i] & r_w[i]);
+                r_n[i] = (r_n[i] & ~r_w[i]) | (t_n[i] & r_w[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < kPer; i++) asm volatile("" : "+v"(r_o[i]), "+v"(r_f[i]), "+v"(r_n[i]));
+        asm volatile("" : "+v"(r_seed));
+    }
+    ChainSeed in;
+    in.status = kSeedOk;
+    in.placed = 0;
+    in.cur = wrap_pos(A.offset0, n ? n : 1u);
+    in.pos_used = 0;
+    if (phase) {
+        if (args_ok) {
+            in.status = (uint32_t)__shfl((int)r_seed, 0);
+            in.placed = (uint32_t)__shfl((int)r_seed, 1);
+            in.cur = (uint32_t)__shfl((int)r_seed, 2);
+            in.pos_used = (uint32_t)__shfl((int)r_seed, 3);
+        } else {
+            in = Wd.seed[phase - 1];
+        }
+    }
+    if (in.status != kSeedOk || in.placed >= A.count) {
+        if (first) Wd.seed[phase] = in;
+        return;
+    }
+    const uint32_t cur = in.cur;
+    bool ok = args_ok && cur < n;
+    uint32_t tot_o = 0, ns = 0, c_opt = 0, c_fil = 0, tot_f = 0;
+    if (ok) {
+        uint32_t any_n = 0;
+#pragma unroll
+        for (int i = 0; i < kPer; i++) {
+            const uint32_t w = lane + (uint32_t)i * kWideBlock;
+            if (w < nw) {
+                s_opt[w] = r_o[i];
+                s_fil[w] = r_f[i];
+                s_won[w] = r_w[i];
+                any_n |= r_n[i];
+            }
+        }
+        __syncthreads();
+        // exclusive word prefixes (absolute positions), the totals at [nw]
+        const uint32_t per = (nw + kWideBlock - 1) / kWideBlock;
+        const uint32_t w0 = min(lane * per, nw), w1 = min(w0 + per, nw);
+        uint32_t so = 0, sf = 0;
+        for (uint32_t w = w0; w < w1; w++) {
+            so += (uint32_t)__popc(s_opt[w]);
+            sf += (uint32_t)__popc(s_fil[w]);
+        }
+        uint32_t io = so, iff = sf;
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t xo = (uint32_t)__shfl_up((int)io, off), xf = (uint32_t)__shfl_up((int)iff, off);
+            if ((int)lane >= off) { io += xo; iff += xf; }
+        }
+        uint32_t eo = io - so, ef = iff - sf;
+        for (uint32_t w = w0; w < w1; w++) {
+            p_opt[w] = eo;
+            p_fil[w] = ef;
+            eo += (uint32_t)__popc(s_opt[w]);
+            ef += (uint32_t)__popc(s_fil[w]);
+        }
+        if (lane == kWideBlock - 1) {
+            p_opt[nw] = io;
+            p_fil[nw] = iff;
+        }
+        __syncthreads();
+        tot_o = p_opt[nw];
+        tot_f = p_fil[nw];
+        ns = min(A.count - in.placed, tot_o / L);
+        // non-positive options (the Selects set them aside), or no whole Select
+        // in the window (k_chain's Retry / Stall / Exhausted modes): k_chain's
+        if (__ballot(any_n != 0u) != 0ull || ns == 0) ok = false;
+    }
+    if (!ok) {
+        if (first) {
+            in.status = kSeedDeclined;
+            Wd.seed[phase] = in;
+            Wd.stats[1] += 1ull;
+        }
+        return;
+    }
+    c_opt = wide_prefix(p_opt, s_opt, nw, cur);
+    c_fil = wide_prefix(p_fil, s_fil, nw, cur);
+    // filtered positions among the relative positions [0, x), x in [0, n]
+    auto fil_before = [&](uint32_t x) {
+        const uint32_t a = cur + x;
+        if (a <= n) return wide_prefix(p_fil, s_fil, nw, a) - c_fil;
+        return tot_f - c_fil + wide_prefix(p_fil, s_fil, nw, a - n);
+    };
+    auto rel_of = [&](uint32_t p) { return p >= cur ? p - cur : p + n - cur; };
+    // the visit position (absolute) of the option of relative rank k < tot_o
+    auto opt_at = [&](uint32_t k, uint32_t* w, uint32_t* rest) {
+        uint32_t r = c_opt + k;
+        if (r >= tot_o) r -= tot_o;
+        return r < tot_o && wide_select(p_opt, s_opt, nw, r, w, rest);
+    };
+    for (uint32_t s = blockIdx.x * kWideBlock + lane; s < ns; s += gridDim.x * kWideBlock) {
+        // the Select's options s L .. s L + L - 1: their values, rows and (on a
+        // phase 0 winner's position) writeback slots in one round of loads, so
+        // the winner's row does not cost a round trip of its own
+        uint32_t w = 0, word = 0;
+        bool good = opt_at(s * L, &w, &word);
+        uint32_t pos[kMaxChainLimit], prow[kMaxChainLimit], pslot[kMaxChainLimit];
+        double val[kMaxChainLimit];
+#pragma unroll
+        for (uint32_t k = 0; k < kMaxChainLimit; k++) {
+            pos[k] = 0;
+            prow[k] = 0;
+            pslot[k] = ~0u;
+            val[k] = 0.0;
+            if (k >= L || !good) continue;
+            for (uint32_t hop = 0; word == 0u && hop <= nw; hop++) {   // the next word that holds an option
+                w = w + 1u < nw ? w + 1u : 0u;
+                word = s_opt[w];
+            }
+            if (word == 0u) { good = false; continue; }
+            const uint32_t bit = (uint32_t)__ffs((int)word) - 1u;
+            word &= word - 1u;
+            const uint32_t p = w * 32u + bit;
+            if (p >= n) { good = false; continue; }
+            const bool had = (s_won[w] >> bit) & 1u;
+            pos[k] = p;
+            val[k] = (had ? A.base1 : A.base)[p];
+            prow[k] = A.perms[p];
+            if (had) pslot[k] = Wd.slot[p];
+        }
+        // the previous Select's stop (its last option), for the span's start
+        uint32_t start = 0;
+        if (s && good) {
+            uint32_t pw = 0, prest = 0;
+            good = opt_at(s * L - 1u, &pw, &prest);
+            if (good) start = rel_of(pw * 32u + (uint32_t)__ffs((int)prest) - 1u) + 1u;
+        }
+        const uint32_t it = in.placed + s;
+        if (!good || it >= A.count) {
+            wide_fail(Wd);
+            continue;
+        }
+        // first strict maximum in visit order (chain_walk's rule without set-aside options)
+        double best = val[0];
+        uint32_t bp = pos[0], stop = pos[0], row = prow[0], sl = pslot[0];
+#pragma unroll
+        for (uint32_t k = 1; k < kMaxChainLimit; k++) {
+            if (k >= L) continue;
+            stop = pos[k];
+            if (val[k] > best) { best = val[k]; bp = pos[k]; row = prow[k]; sl = pslot[k]; }
+        }
+        const uint32_t stop_rel = rel_of(stop);
+        const uint32_t consumed = stop_rel + 1u - start;
+        const uint32_t nf = fil_before(stop_rel + 1u) - fil_before(start);
+        if (stop_rel >= n || stop_rel < start || consumed < L + nf) {
+            wide_fail(Wd);
+            continue;
+        }
+        const uint32_t dk = (s_won[bp >> 5] >> (bp & 31u)) & 1u;
+        if (dk && sl >= A.count) {   // the slot phase 0 stored for this position
+            wide_fail(Wd);
+            continue;
+        }
+        ChainEmit& m = A.emit[it];
+        m.row = (int32_t)row;
+        m.dk = dk;
+        m.consumed = consumed;
+        m.filtered = nf;
+        m.exhausted = consumed - L - nf;
+        m.new_offset = wrap_pos(cur + stop_rel + 1u, n);
+        m.pos = bp;
+        m.score = best;
+        // the writeback's entry: one per row
+        if (dk) {
+            A.emit_ov[sl] = make_uint2(row, 2u);
+            A.emit_ov[it] = make_uint2(row, 0u);
+        } else {
+            A.emit_ov[it] = make_uint2(row, 1u);
+            if (phase == 0) Wd.slot[bp] = it;
+        }
+        atomicOr(&Wd.won[phase * nw + (bp >> 5)], 1u << (bp & 31u));
+    }
+    if (first) {
+        uint32_t w = 0, rest = 0;
+        if (!opt_at(ns * L - 1u, &w, &rest)) {
+            wide_fail(Wd);
+            in.status = kSeedDeclined;
+            Wd.seed[phase] = in;
+            return;
+        }
+        const uint32_t used = rel_of(w * 32u + (uint32_t)__ffs((int)rest) - 1u) + 1u;
+        in.placed += ns;
+        in.cur = wrap_pos(cur + used, n);
+        in.pos_used += used;
+        Wd.seed[phase] = in;
+        Wd.stats[0] += 1ull;
+    }
 }
 
 // The placed count of a 256-lane workgroup, one atomic per workgroup into one
@@ -4643,10 +5017,20 @@ hipError_t pe_launch_chain(const pe::BatchArgs* a, uint32_t n_evals, uint32_t ma
     // list_covers: k_base's pass over the list is the only writer of node_feas
     if (a->fold.list_covers && (!a->fold.feas || a->fused || !a->base_by_pos || a->n_visit != a->soa.n))
         return hipErrorInvalidValue;
+    // wide phases: the unfused, by-position, single-evaluation chain with
+    // deferred records and a writeback, no device asks or reserved cores
+    const pe::ChainWide& wd = a->wide;
+    if (wd.bits &&
+        (n_evals != 1 || a->fused || !a->base_by_pos || !a->base1 || !a->emit || !a->emit_ov || !a->emit_n ||
+         a->out || a->full_out || !a->commit || !a->writeback || a->ask.n_dev != 0 || a->ask.cores != 0 ||
+         a->n_visit == 0 || a->n_visit > pe::kChainMaxN || wd.words != (a->n_visit + 31u) / 32u || !wd.won ||
+         !wd.slot || !wd.seed || !wd.err || !wd.stats || wd.phases < 1 || wd.phases > 2))
+        return hipErrorInvalidValue;
     const size_t lds = pe_chain_lds_bytes(a->hash_bits, a->packed_overlay != 0, a->n_visit);
     uint32_t grid = n_evals < max_blocks ? n_evals : max_blocks;
     if (grid == 0) grid = 1;
     const int items = pe_chain_shape(a->n_visit, forced_items);
+    if (wd.bits && items != 1 && items != 4 && items != pe::kChainItems) return hipErrorInvalidValue;
     if (a->fused) {
         // one launch: fold, first-phase values, chain, records, writeback
         if (n_evals != 1 || !a->base_by_pos || a->base1 || !a->emit || !a->emit_out || items > 4 ||
@@ -4663,15 +5047,39 @@ hipError_t pe_launch_chain(const pe::BatchArgs* a, uint32_t n_evals, uint32_t ma
     if (blocks > 8192) blocks = 8192;
     if (blocks == 0) blocks = 1;
     if (split) (void)hipEventRecord(split[0], st);
-    if (a->fold.feas) hipLaunchKernelGGL(pe::k_base<true>, dim3(blocks), dim3(pe::kBaseBlock), 0, st, *a);
-    else hipLaunchKernelGGL(pe::k_base<false>, dim3(blocks), dim3(pe::kBaseBlock), 0, st, *a);
+    if (wd.bits) {
+        if (a->fold.feas) hipLaunchKernelGGL((pe::k_base<true, true>), dim3(blocks), dim3(pe::kBaseBlock), 0, st, *a);
+        else hipLaunchKernelGGL((pe::k_base<false, true>), dim3(blocks), dim3(pe::kBaseBlock), 0, st, *a);
+    } else if (a->fold.feas) {
+        hipLaunchKernelGGL(pe::k_base<true>, dim3(blocks), dim3(pe::kBaseBlock), 0, st, *a);
+    } else {
+        hipLaunchKernelGGL(pe::k_base<false>, dim3(blocks), dim3(pe::kBaseBlock), 0, st, *a);
+    }
     if (split) (void)hipEventRecord(split[1], st);
-    switch (items) {
-    case 1: hipLaunchKernelGGL((pe::k_chain<1, false>), dim3(grid), dim3(pe::kChainBlock), lds, st, *a, n_evals); break;
-    case 4: hipLaunchKernelGGL((pe::k_chain<4, false>), dim3(grid), dim3(pe::kChainBlock), lds, st, *a, n_evals); break;
-    default:
-        hipLaunchKernelGGL((pe::k_chain<pe::kChainItems, false>), dim3(grid), dim3(pe::kChainBlock), lds, st, *a,
-                           n_evals);
+    if (wd.bits) {
+        // one Select per lane; the second rotation only when the count reaches it
+        const uint32_t wg = (a->count + pe::kWideBlock - 1) / pe::kWideBlock;
+        for (uint32_t ph = 0; ph < wd.phases; ph++)
+            hipLaunchKernelGGL(pe::k_phase, dim3(wg ? wg : 1), dim3(pe::kWideBlock), 0, st, *a, ph);
+    }
+    if (wd.bits) {
+        // an armed launch runs the instantiation that starts from the seed
+        // (the shape was checked above: no other one can take its place)
+        switch (items) {
+        case 1: hipLaunchKernelGGL((pe::k_chain<1, false, true>), dim3(1), dim3(pe::kChainBlock), lds, st, *a, 1u); break;
+        case 4: hipLaunchKernelGGL((pe::k_chain<4, false, true>), dim3(1), dim3(pe::kChainBlock), lds, st, *a, 1u); break;
+        default:
+            hipLaunchKernelGGL((pe::k_chain<pe::kChainItems, false, true>), dim3(1), dim3(pe::kChainBlock), lds, st, *a,
+                               1u);
+        }
+    } else {
+        switch (items) {
+        case 1: hipLaunchKernelGGL((pe::k_chain<1, false>), dim3(grid), dim3(pe::kChainBlock), lds, st, *a, n_evals); break;
+        case 4: hipLaunchKernelGGL((pe::k_chain<4, false>), dim3(grid), dim3(pe::kChainBlock), lds, st, *a, n_evals); break;
+        default:
+            hipLaunchKernelGGL((pe::k_chain<pe::kChainItems, false>), dim3(grid), dim3(pe::kChainBlock), lds, st, *a,
+                               n_evals);
+        }
     }
     if (split) (void)hipEventRecord(split[2], st);
     if (a->emit) {

@@ -96,6 +96,8 @@ def load_engine():
                                                      abi.u32p]
         lib.pe_speculation_stats.restype = C.c_int
         lib.pe_speculation_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.pe_chain_wide_stats.restype = C.c_int
+        lib.pe_chain_wide_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.pe_comm_unique_id.restype = C.c_int
         lib.pe_comm_unique_id.argtypes = [abi.u8p, C.c_size_t]
         lib.pe_comm_init.restype = C.c_int
@@ -977,6 +979,13 @@ class GenericStack(_Stack):
         the speculative count loop behind Select / Commit (pe_speculation_stats)."""
         buf = (C.c_uint64 * 4)()
         self._check(self._lib.pe_speculation_stats(self._h, buf))
+        return tuple(int(x) for x in buf)
+
+    def ChainWideStats(self):
+        """(phases resolved, phases declined) by the chain's wide phase launches
+        (pe_chain_wide_stats); a declined phase is left to k_chain."""
+        buf = (C.c_uint64 * 2)()
+        self._check(self._lib.pe_chain_wide_stats(self._h, buf))
         return tuple(int(x) for x in buf)
 
     def last_phase_ms(self):
