@@ -451,9 +451,45 @@ int pe_plan_pop_update(pe_stack* s, uint32_t alloc);
  * listed twice. PE_EUNSUPPORTED (nothing changed; the per-call sequence
  * answers): spreads or distinct_property, reserved-cores asks, static ports,
  * multi-device network nodes, a handle over several devices, pe_set_metrics on,
- * a system stack with preemption enabled. */
+ * a system stack with preemption enabled (pe_inplace_update_preempt below
+ * answers that one). */
 int pe_inplace_update(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n,
                       pe_ranked_node* out, uint8_t* status, uint32_t* updated);
+/* pe_inplace_update for a system stack with preemption enabled, the reference's
+ * default for system jobs (nomad/config.go:448-455): the Select of every update
+ * is SystemStack.Select's, BinPack with evict (stack.go:267-278) where the
+ * plain fit fails. Arguments, result layout, status codes and the node-list
+ * rule are pe_inplace_update's; out[i] of an evicting Select carries the
+ * eviction's FinalScore and score parts, n_preempted the whole count and the
+ * first PE_MAX_PREEMPT alloc-table rows inline (the whole lists:
+ * pe_inplace_update_preempted). inplaceUpdate never reads
+ * option.PreemptedAllocs (util.go:759-802): the evicted allocs stay in the
+ * proposed state, Plan.NodePreemptions and its counts do not move, and a later
+ * update on the node may evict the same alloc again, all as the per-call
+ * sequence (pe_select then pe_commit, never pe_commit_preempt) leaves it. On a
+ * generic stack, or a system stack without preemption, the call is
+ * pe_inplace_update. One launch pair and one synchronisation, plus one of each
+ * per wider eviction width some listed node needs.
+ *
+ * PE_EINVAL as pe_inplace_update. PE_EUNSUPPORTED (checked before anything
+ * changes): everything pe_inplace_update refuses except preemption itself, and
+ * on a preempting system stack: a device ask in the group (the in-place
+ * update keeps the old alloc's instances, util.go:767-782, which the packed
+ * free counts cannot hold beside evicted holders that stay in the plan);
+ * several task networks in the group; a snapshot outside the on-device
+ * eviction limits; a listed node of more than 1024 allocs, or whose allocs
+ * plus the plan's placements on it plus the listed updates on it exceed 2048. */
+int pe_inplace_update_preempt(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n,
+                              pe_ranked_node* out, uint8_t* status, uint32_t* updated);
+/* The preempted allocs of the last pe_inplace_update_preempt, a CSR in the
+ * engine's page-locked staging, valid until the next pe_inplace_update* call on
+ * the handle: updates[n_entries] holds the list positions whose Select
+ * preempted something, increasing; allocs[off[i] .. off[i + 1]) their
+ * alloc-table rows in the order pe_select's record lists them (increasing slot
+ * of the node's alloc list). No PE_MAX_PREEMPT cap. PE_ESTATE: no such call
+ * yet, or a pe_inplace_update since. */
+int pe_inplace_update_preempted(const pe_stack* s, const uint32_t** updates, const uint32_t** off,
+                                const uint32_t** allocs, uint32_t* n_entries);
 /* Fused count loop of GenericScheduler.computePlacements (generic_sched.go:493-649)
  * for `count` fresh placements of one task group (no preferred / penalty nodes):
  * Select -> AppendAlloc repeated on the device; stops at the first nil option

@@ -235,6 +235,7 @@ ENGINE_SYMBOLS = [
     "pe_system_place_groups_preempt", "pe_system_groups_preempted",
     "pe_system_place_groups_metrics", "pe_system_groups_metrics",
     "pe_chain_wide_stats",
+    "pe_inplace_update_preempt", "pe_inplace_update_preempted",
 ]
 
 

@@ -949,6 +949,13 @@ struct pe_stack {
     // results [records | outcomes] with their page-locked staging
     DevMem d_inplace_upd, d_inplace_off, d_inplace_out;
     PinnedMem h_inplace_out;
+    // pe_inplace_update_preempt: the groups' resume indices and the two group
+    // lists of the eviction walk; the preempted allocs of the last call as a
+    // CSR [updates | off | allocs] (pe_inplace_update_preempted)
+    DevMem d_inplace_lanes;
+    PinnedMem h_inplace_csr;
+    uint32_t inplace_pre_entries = 0;
+    bool inplace_pre_valid = false;
     SysGroupsState sysg;   // pe_system_place_groups*: buffers, and what the accessors read
     bool stopped(uint32_t ai) const { return ai < stop_count.size() && stop_count[ai] > 0; }
 
@@ -8312,14 +8319,44 @@ static int plan_pop_update_one(pe_stack* s, uint32_t alloc) {
     return apply_stop_delta(s, gone, -1);
 }
 
+// pe_inplace_update_preempted's CSR [updates | off | allocs] from the evicting
+// updates (list position, rows) in increasing position.
+static int inplace_csr_set(pe_stack* s, const std::vector<std::pair<uint32_t, std::vector<uint32_t>>>& ev) {
+    size_t total = 0;
+    for (auto& e : ev) total += e.second.size();
+    const size_t ne = ev.size();
+    HIP_TRY(s, s->h_inplace_csr.ensure(sizeof(uint32_t) * (2 * ne + 1 + total)));
+    uint32_t* w = s->h_inplace_csr.as<uint32_t>();
+    uint32_t at = 0;
+    for (size_t i = 0; i < ne; i++) {
+        w[i] = ev[i].first;
+        w[ne + i] = at;
+        std::memcpy(w + 2 * ne + 1 + at, ev[i].second.data(), sizeof(uint32_t) * ev[i].second.size());
+        at += (uint32_t)ev[i].second.size();
+    }
+    w[2 * ne] = at;
+    s->inplace_pre_entries = (uint32_t)ne;
+    s->inplace_pre_valid = true;
+    return PE_OK;
+}
+
 // inplaceUpdate's loop (util.go:692-806) in one launch: per
 // listed alloc the sequence pe_plan_stop, pe_set_nodes([its node]), pe_select,
 // pe_plan_pop_update and, on an option, pe_plan_stop + pe_commit, with the
 // same results and the same state afterwards. Everything that can refuse the
 // call is checked before anything changes.
+//
+// `pre_call`: pe_inplace_update_preempt. On a preempting
+// system stack the walk stops a node group at its first exhausted update
+// (k_inplace<true>) and the eviction walk (k_inplace_evict) takes the stopped
+// groups from there, BinPack with evict where the plain fit is exhausted. The
+// commit stays the plain one: inplaceUpdate never reads PreemptedAllocs
+// (util.go:759-802), so nothing about the evicted allocs enters h_preempted,
+// pcount or the plan; they are kept as a CSR (pe_inplace_update_preempted).
 static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
-                              uint8_t* status, uint32_t* updated) {
+                              uint8_t* status, uint32_t* updated, bool pre_call) {
     if (!s) return PE_EINVAL;
+    const std::string fn = pre_call ? "pe_inplace_update_preempt: " : "pe_inplace_update: ";
     if (updated) *updated = 0;
     if (n && (!allocs || !status)) return s->fail(PE_EINVAL, "null alloc list or status array");
     if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
@@ -8333,13 +8370,18 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
         if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
             return s->fail(PE_EINVAL, "an alloc is listed twice");
     }
-    if (n == 0) return PE_OK;
+    if (n == 0) {
+        s->inplace_pre_valid = false;
+        return pre_call ? inplace_csr_set(s, {}) : PE_OK;
+    }
     TgPlan& g = *s->tgs[tgi];
+    const bool evicting = pre_call && s->cfg.stack_kind != PE_STACK_GENERIC && s->cfg.preempt;
     // what the batched path does not model: the caller's per-Select loop answers
     const char* why = nullptr;
     if (!s->kids.empty()) why = "a handle over several devices";
     else if (s->metrics_on) why = "AllocMetric maps are on (pe_set_metrics)";
-    else if (s->cfg.stack_kind != PE_STACK_GENERIC && s->cfg.preempt) why = "a system stack with preemption (BinPack evicts)";
+    else if (s->cfg.stack_kind != PE_STACK_GENERIC && s->cfg.preempt && !pre_call)
+        why = "a system stack with preemption (BinPack evicts)";
     else if (g.ask.cores > 0) why = "a reserved-cores ask";
     else if (has_static(g)) why = "static ports";
     else if (!g.spreads.empty() || !s->job_spreads.empty()) why = "spreads";
@@ -8347,11 +8389,41 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     else if (tg_md(s, g)) why = "a task network on multi-device nodes";
     for (auto& c : s->job_constraints)
         if (!why && c.op == "distinct_property") why = "distinct_property";
-    if (why) return s->fail(PE_EUNSUPPORTED, std::string("pe_inplace_update: ") + why);
+    if (why) return s->fail(PE_EUNSUPPORTED, fn + why);
     if (!g.unsupported.empty()) return s->fail(PE_EUNSUPPORTED, g.unsupported);
     if (!s->cores_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->cores_unsupported);
+    // the eviction walk: what evict_eval would flag kEvictUnsup for (a device
+    // ask: PreemptForDevice, and the old alloc's instances stay with it,
+    // util.go:767-782, while a preempting Select would offer instances whose
+    // holders stay in the plan; several task networks: AssignNetwork per
+    // task), and the widest width this call can need: a listed node's allocs,
+    // and its ProposedAllocs with the plan's placements and this call's
+    uint32_t words_max = 1;
+    if (evicting) {
+        if (!g.dev_reqs.empty()) return s->fail(PE_EUNSUPPORTED, fn + "a device ask under preemption");
+        if (g.ask.has_task_net > 1) return s->fail(PE_EUNSUPPORTED, fn + "several task networks in the group");
+        if (!s->preempt_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, "preemption: " + s->preempt_unsupported);
+        std::unordered_map<uint32_t, uint32_t> on_row;   // plan placements + listed updates per listed row
+        for (uint32_t i = 0; i < n; i++) on_row[s->allocs[allocs[i]].row]++;
+        for (auto& e : plan_of(s)) {
+            const auto it = on_row.find(e.second);
+            if (it != on_row.end()) it->second++;
+        }
+        for (auto& e : on_row) {
+            const uint64_t m = s->h_node_alloc_off[e.first + 1] - s->h_node_alloc_off[e.first];
+            const uint64_t l = m + e.second;
+            if (m > pe::kEvictMaxAllocs || l > 64ull * pe::kEvictMaxWords)
+                return s->fail(PE_EUNSUPPORTED, fn + "a node beyond the widest eviction width");
+            for (uint32_t w : pe::kEvictWidths)
+                if (m <= 32ull * w && l <= 64ull * w) {
+                    words_max = std::max(words_max, w);
+                    break;
+                }
+        }
+    }
     int rc = spec_flush(s);
     if (rc) return rc;
+    s->inplace_pre_valid = false;
     s->gen++;
     s->metrics_valid = false;
     s->pre_overflow.clear();
@@ -8371,7 +8443,7 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     invalidate_tables(s);
     rc = prepare_tg(s, tgi, s->visit, 0);
     if (rc) return rc;
-    if (!g.psets.empty() || g.md_on) return s->fail(PE_EUNSUPPORTED, "pe_inplace_update: property sets or multi-device nodes");
+    if (!g.psets.empty() || g.md_on) return s->fail(PE_EUNSUPPORTED, fn + "property sets or multi-device nodes");
 
     // group by node row (stable: list order within a group), longest groups
     // first so that the lanes of a wave walk groups of similar length
@@ -8420,9 +8492,25 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     HIP_TRY(s, upload_s(s, s->d_inplace_upd, upd));
     HIP_TRY(s, upload_s(s, s->d_inplace_off, group_off));
     const size_t st_off = out ? sizeof(pe::EmitRec) * (size_t)n : 0;
-    const size_t bytes = st_off + n;
-    HIP_TRY(s, s->d_inplace_out.ensure(bytes));
-    HIP_TRY(s, s->h_inplace_out.ensure(bytes));
+    // the eviction walk's part of the results, behind the outcomes so that one
+    // DMA brings everything: its four control words (stopped, wider, appended,
+    // flags), then the appended records [list position | mask words], at most
+    // one per update. The walk starts at the narrowest width that covers all
+    // but at most an eighth of the snapshot's nodes, as system_place_groups does
+    const size_t ctl_off = (st_off + n + 15) & ~(size_t)15;
+    const size_t app_off = ctl_off + 4 * sizeof(uint32_t);
+    uint32_t words = 0;
+    if (evicting) {
+        const uint32_t nn = (uint32_t)s->nodes.size();
+        words = s->evict_words;
+        if (s->n_beyond_w1 <= nn / 8) words = 1;
+        else if (s->n_beyond_w8 <= nn / 8) words = std::min(words, 8u);
+        words_max = std::max(words_max, words);
+    }
+    const auto dma_bytes = [&](uint32_t w) { return evicting ? app_off + sizeof(uint32_t) * (1 + (size_t)w) * n : st_off + n; };
+    const size_t bytes = dma_bytes(words);
+    HIP_TRY(s, s->d_inplace_out.ensure(dma_bytes(words_max)));
+    HIP_TRY(s, s->h_inplace_out.ensure(dma_bytes(words_max)));
     unsigned char* dres = s->d_inplace_out.as<unsigned char>();
     pe::InplaceArgs A;
     std::memset(&A, 0, sizeof(A));
@@ -8439,8 +8527,40 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     A.log10 = s->log10;
     A.out = out ? reinterpret_cast<pe::EmitRec*>(dres) : nullptr;
     A.status = dres + st_off;
+    pe::InplaceEvictArgs V;
+    const uint32_t ng = A.n_groups;
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(dres + ctl_off);
+    if (evicting) {
+        HIP_TRY(s, s->d_inplace_lanes.ensure(sizeof(uint32_t) * 3 * (size_t)ng));
+        HIP_TRY(s, hipMemsetAsync(ctl, 0, 4 * sizeof(uint32_t), s->stream));
+    }
     HIP_TRY(s, hipEventRecord(s->ev0, s->stream));
-    HIP_TRY_STATE(s, pe_launch_inplace(&A, s->stream));
+    if (evicting) {
+        uint32_t* lanes = s->d_inplace_lanes.as<uint32_t>();
+        pe::InplaceStopArgs S;
+        S.resume = lanes;
+        S.stopped = lanes + ng;
+        S.n_stopped = ctl;
+        S.own_existing = s->d_own_existing.as<uint32_t>();
+        HIP_TRY_STATE(s, pe_launch_inplace_stop(&A, &S, s->stream));
+        std::memset(&V, 0, sizeof(V));
+        V.I = A;
+        V.P = preempt_args(s, g);
+        V.P.mask_words = words;
+        V.own_existing = S.own_existing;
+        V.resume = S.resume;
+        V.stopped = S.stopped;
+        V.n_stopped = ctl;
+        V.wider = lanes + 2 * (size_t)ng;
+        V.n_wider = ctl + 1;
+        V.app = reinterpret_cast<uint32_t*>(dres + app_off);
+        V.n_app = ctl + 2;
+        V.app_cap = n;
+        V.flags = ctl + 3;
+        HIP_TRY_STATE(s, pe_launch_inplace_evict(&V, words, ng, s->stream));
+    } else {
+        HIP_TRY_STATE(s, pe_launch_inplace(&A, s->stream));
+    }
     HIP_TRY(s, hipEventRecord(s->ev1, s->stream));
     HIP_TRY(s, hipMemcpyAsync(s->h_inplace_out.p, dres, bytes, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));   // the call's one wait
@@ -8448,6 +8568,55 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     HIP_TRY(s, hipEventElapsedTime(&ms, s->ev0, s->ev1));
     s->last_ms = ms;
     s->last_ms_pending = false;
+
+    // The evicting updates' preempted sets (list position, alloc-table rows in
+    // increasing slot of the node's alloc list, as set_preempted lists them),
+    // and one more round per wider eviction width some node needs (none in the
+    // common case): the walk over the groups the last launch left, then the
+    // results again
+    std::vector<std::pair<uint32_t, std::vector<uint32_t>>> evicted;
+    for (uint32_t round = 0; evicting; round++) {
+        const unsigned char* hb = s->h_inplace_out.as<unsigned char>();
+        const uint32_t* hc = reinterpret_cast<const uint32_t*>(hb + ctl_off);
+        const uint32_t n_app = hc[2], flags = hc[3];
+        if (flags & (pe::kEvictUnsup | pe::kSysgOverflow))
+            return s->fail(PE_EINTERNAL, fn + "the eviction walk met a node outside the device path");
+        if (n_app > n) return s->fail(PE_EINTERNAL, fn + "appended records beyond the buffer");
+        const uint32_t* r = reinterpret_cast<const uint32_t*>(hb + app_off);
+        for (uint32_t a = 0; a < n_app; a++, r += 1 + words) {
+            if (r[0] >= n) return s->fail(PE_EINTERNAL, fn + "an appended position out of range");
+            const uint32_t row = s->visit[r[0]];
+            const uint32_t b = s->h_node_alloc_off[row], m = s->h_node_alloc_off[row + 1] - b;
+            std::vector<uint32_t> rows;
+            for (uint32_t w = 0; w < words && 32u * w < m; w++)
+                for (uint32_t bits = r[1 + w]; bits; bits &= bits - 1) {   // increasing slot
+                    const uint32_t i = 32u * w + (uint32_t)__builtin_ctz(bits);
+                    if (i < m) rows.push_back(s->h_palloc_index[b + i]);
+                }
+            evicted.emplace_back(r[0], std::move(rows));
+        }
+        if (!(flags & pe::kEvictWider)) break;
+        words = wider_words(words);
+        if (!words || words > words_max || round >= 2)
+            return s->fail(PE_EINTERNAL, fn + "a node beyond the widest eviction width");
+        // the groups left over become this round's list; its own leftovers go to the other half
+        uint32_t* lanes = s->d_inplace_lanes.as<uint32_t>();
+        const bool from_second = (round & 1u) == 0;   // the first walk wrote the second list
+        V.stopped = from_second ? lanes + 2 * (size_t)ng : lanes + ng;
+        V.n_stopped = from_second ? ctl + 1 : ctl;
+        V.wider = from_second ? lanes + ng : lanes + 2 * (size_t)ng;
+        V.n_wider = from_second ? ctl : ctl + 1;
+        V.P.mask_words = words;
+        HIP_TRY(s, hipMemsetAsync(V.n_wider, 0, sizeof(uint32_t), s->stream));
+        HIP_TRY(s, hipMemsetAsync(ctl + 2, 0, sizeof(uint32_t) * 2, s->stream));
+        HIP_TRY_STATE(s, pe_launch_inplace_evict(&V, words, ng, s->stream));
+        HIP_TRY(s, hipMemcpyAsync(s->h_inplace_out.p, dres, dma_bytes(words), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(s, hipStreamSynchronize(s->stream));
+    }
+    std::sort(evicted.begin(), evicted.end(),
+              [](const std::pair<uint32_t, std::vector<uint32_t>>& x, const std::pair<uint32_t, std::vector<uint32_t>>& y) {
+                  return x.first < y.first;
+              });
 
     // the host mirrors, in list order, as the per-call sequence leaves them
     const unsigned char* h = s->h_inplace_out.as<unsigned char>();
@@ -8467,6 +8636,17 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
             core_hold(s, ai, false);
         }
         plan.emplace_back(g.name, row);      // ... and its AppendAlloc
+    }
+    for (auto& e : evicted) {   // the records' PreemptedAllocs: the whole count, the first rows inline
+        if (status[e.first] != 0) return s->fail(PE_EINTERNAL, fn + "a preempted set without an option");
+        if (!out) continue;
+        pe_ranked_node& o = out[e.first];
+        o.n_preempted = (uint32_t)e.second.size();
+        for (uint32_t k = 0; k < o.n_preempted && k < PE_MAX_PREEMPT; k++) o.preempted[k] = e.second[k];
+    }
+    if (pre_call) {
+        rc = inplace_csr_set(s, evicted);
+        if (rc) return rc;
     }
     if (updated) *updated = up;
     s->offer_row = -1;
@@ -9825,7 +10005,25 @@ int pe_plan_pop_update(pe_stack* s, uint32_t alloc) {
 int pe_inplace_update(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
                       uint8_t* status, uint32_t* updated) {
     PE_FLUSH_RESET(s);
-    return inplace_update_one(s, tgi, allocs, n, out, status, updated);
+    return inplace_update_one(s, tgi, allocs, n, out, status, updated, false);
+}
+
+int pe_inplace_update_preempt(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                              uint8_t* status, uint32_t* updated) {
+    PE_FLUSH_RESET(s);
+    return inplace_update_one(s, tgi, allocs, n, out, status, updated, true);
+}
+
+int pe_inplace_update_preempted(const pe_stack* s, const uint32_t** updates, const uint32_t** off,
+                                const uint32_t** allocs, uint32_t* n_entries) {
+    if (!s || !updates || !off || !allocs || !n_entries) return PE_EINVAL;
+    if (!s->inplace_pre_valid || !s->h_inplace_csr.p) return PE_ESTATE;
+    const uint32_t* w = s->h_inplace_csr.as<uint32_t>();
+    *updates = w;
+    *off = w + s->inplace_pre_entries;
+    *allocs = w + 2 * (size_t)s->inplace_pre_entries + 1;
+    *n_entries = s->inplace_pre_entries;
+    return PE_OK;
 }
 
 int pe_place(pe_stack* s, uint32_t tgi, uint32_t count, pe_ranked_node* out, uint32_t* placed) {

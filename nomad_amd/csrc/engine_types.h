@@ -538,6 +538,33 @@ struct InplaceArgs {
     uint8_t* status;                  // [n] by list position: 0 updated, 1 filtered, 2 exhausted
 };
 
+// pe_inplace_update_preempt: the stopping form of the walk
+// (k_inplace<true>) and the eviction walk over the node groups it stopped
+// (k_inplace_evict).
+struct InplaceStopArgs {
+    uint32_t* resume;                 // [n_groups] the index into upd a group stopped at
+    uint32_t* stopped;                // [n_groups] the groups that stopped, in any order
+    uint32_t* n_stopped;              // [1]
+    uint32_t* own_existing;           // [n rows] PreemptArgs::own_existing: drops with an updated own alloc
+};
+
+struct InplaceEvictArgs {
+    InplaceArgs I;
+    PreemptArgs P;                    // evict_eval's view of the group
+    uint32_t* own_existing;           // [n rows] P.own_existing, written through for the trial
+    uint32_t* resume;                 // [n_groups] read; rewritten for a group the launch's width does not cover
+    const uint32_t* stopped;          // the groups of this launch
+    const uint32_t* n_stopped;
+    uint32_t* wider;                  // the groups left to the next width
+    uint32_t* n_wider;
+    // one record per evicting update: its list position, then the launch's
+    // mask words over the node's CSR slots; at most app_cap records
+    uint32_t* app;
+    uint32_t* n_app;
+    uint32_t app_cap;
+    uint32_t* flags;                  // [1] kEvictUnsup | kEvictWider | kSysgOverflow
+};
+
 // SystemScheduler.computePlacements' loop over (node, task group) in one pass
 // (k_system_groups): one lane per list position walks the listed groups in
 // order on the node's record held in registers. Entry e = pos * n_tg + k.

@@ -4428,7 +4428,19 @@ __global__ void __launch_bounds__(256) k_md_gate(MdNet* md, const uint32_t* coll
 // stop, anything else puts the registers back. One record store per group.
 // Two node images (current and trial) are live across the pipeline: without
 // the hint the allocator takes 130 VGPRs and a fourth wave per SIMD is lost.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_inplace(InplaceArgs A) {
+//
+// kStop (a preempting system stack): at its first update whose
+// plain fit is exhausted the group stops. That update and the later ones stay
+// unwritten, the node's image goes back to HBM as at the end of the walk, the
+// update's index is kept in resume[g] and the group joins the stopped list
+// (one atomic per wave; the groups are independent, the list's order is free).
+// own_existing drops by the own allocs updated so far: evict_eval's
+// placeholders (coll_job - own_existing) stay the job's plan placements.
+__device__ __forceinline__ uint32_t wave_slot(uint32_t* counter);
+
+template <bool kStop>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
+k_inplace(InplaceArgs A, InplaceStopArgs S) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < A.n_groups; g += stride) {
         const uint32_t b = A.group_off[g], e = A.group_off[g + 1];
@@ -4439,6 +4451,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
         if (A.dev_free) in.dev_free = A.dev_free[row];
         uint32_t cj = A.soa.coll_job[row];
         bool dirty = false;
+        uint32_t own_drop = 0;
         for (uint32_t u = b; u < e; u++) {
             const InplaceUpd x = A.upd[u];
             NodeIn t = in;
@@ -4457,6 +4470,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
             if (tj != cj) A.soa.coll_job[row] = tj;   // DistinctHostsIterator reads the column
             ScoreIn si;
             const int st = status_loaded<false>(A.soa, A.tg, A.tg.class_ok, A.ask, 0u, row, t, &si);
+            if (kStop && st == kExhausted) {   // the eviction walk takes the group from here
+                if (tj != cj) A.soa.coll_job[row] = cj;
+                S.resume[g] = u;
+                S.stopped[wave_slot(S.n_stopped)] = g;
+                if (own_drop) S.own_existing[row] -= own_drop;
+                break;
+            }
             A.status[x.pos] = (uint8_t)st;
             if (A.out) {
                 EmitRec& o = A.out[x.pos];
@@ -4509,6 +4529,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
             A.soa.coll_job[row] = cj;
             in = t;
             dirty = true;
+            if (kStop && (x.flags & kInplaceOwnJob)) own_drop++;
             if (x.slot != PE_NONE) {
                 A.preempted[x.slot] = 2;
                 if (A.soa.core_used && A.palloc_cores)   // its reserved cores leave the node's used set
@@ -4538,6 +4559,157 @@ __device__ __forceinline__ uint32_t wave_slot(uint32_t* counter) {
     if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
     base = __shfl(base, (int)leader);
     return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+// The words of a node's image that an in-place update changes, back to HBM.
+__device__ __forceinline__ void inplace_store(const InplaceArgs& A, uint32_t row, const NodeIn& in) {
+    NodeRec& r = A.soa.rec[row];
+    r.used_cpu = in.r.used_cpu;
+    r.used_mem = in.r.used_mem;
+    r.used_disk = in.r.used_disk;
+    r.used_mbits = in.r.used_mbits;
+    r.used_dyn = in.r.used_dyn;
+    A.tg.coll_tg[row] = in.coll_tg;
+}
+
+// The eviction walk of pe_inplace_update_preempt over the node
+// groups k_inplace<true> stopped, one lane per group from its resume index, at
+// eviction width W. Per update the plain Select as k_inplace runs it; where
+// it is exhausted, BinPack with evict (evict_eval). evict_eval reads HBM, so
+// the trial goes there first: the node's record without the old alloc, the
+// stop in `preempted`, coll_job, the group's coll_tg and own_existing. On an
+// option the record takes the eviction's score parts (as k_evict_record), the
+// preempted set goes to the append buffer as [list position, W mask words],
+// and the ask is added as k_inplace does: inplaceUpdate never reads
+// PreemptedAllocs (util.go:759-802), so the evicted allocs stay in the
+// proposed state and nothing joins the plan's preemptions. Otherwise every
+// word the trial wrote is put back. HBM holds the group's current image
+// whenever evict_eval runs or the lane leaves. A node beyond the width
+// commits nothing from that update on: the group keeps its resume index,
+// joins the wider list and raises kEvictWider.
+template <int W>
+__global__ void __launch_bounds__(256) k_inplace_evict(InplaceEvictArgs V) {
+    const InplaceArgs& A = V.I;
+    const uint32_t n = *V.n_stopped;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
+        const uint32_t g = V.stopped[j];
+        const uint32_t e = A.group_off[g + 1];
+        uint32_t u = V.resume[g];
+        if (u >= e) continue;
+        const uint32_t row = A.upd[u].row;
+        NodeIn in;
+        load_node(A.soa, A.tg, row, in);
+        if (A.dev_free) in.dev_free = A.dev_free[row];
+        uint32_t cj = A.soa.coll_job[row];
+        uint32_t oe = V.own_existing[row];
+        EvictWs<W> ws;
+        for (; u < e; u++) {
+            const InplaceUpd x = A.upd[u];
+            NodeIn t = in;
+            uint32_t tj = cj, toe = oe;
+            if (x.slot != PE_NONE) {   // the old alloc leaves ProposedAllocs
+                const PreemptAlloc& p = A.allocs[x.slot];
+                t.r.used_cpu -= p.cpu;
+                t.r.used_mem -= p.mem;
+                t.r.used_disk -= p.disk;
+                t.r.used_mbits -= p.mbits;
+                t.r.used_dyn -= p.dyn;
+                for (int k = 0; k < 4 && k < (int)p.n_dev; k++) t.dev_free += byte_of(p.dev_c, k) << (8 * byte_of(p.dev_g, k));
+            }
+            if (x.flags & kInplaceOwnJob) {
+                tj -= 1u;
+                toe -= 1u;
+            }
+            if (x.flags & kInplaceOwnTg) t.coll_tg -= 1u;
+            if (tj != cj) A.soa.coll_job[row] = tj;   // DistinctHostsIterator reads the column
+            ScoreIn si;
+            int st = status_loaded<false>(A.soa, A.tg, A.tg.class_ok, A.ask, 0u, row, t, &si);
+            double final_score = 0.0, parts[PE_MAX_SCORES];
+            uint32_t ns = 0, exhausted = st == kExhausted;
+            for (int k = 0; k < PE_MAX_SCORES; k++) parts[k] = 0.0;
+            if (st == kOption) {
+                lookup_scores(A.tg, nullptr, nullptr, row, t.r.cls, &si);
+                final_score = score_into<true>(A.ask, A.log10, si, parts, &ns);
+            } else if (st == kExhausted) {
+                // the trial, where evict_eval reads it
+                inplace_store(A, row, t);
+                if (toe != oe) V.own_existing[row] = toe;
+                if (x.slot != PE_NONE) A.preempted[x.slot] = 2;
+                NodeEval ev;
+                AMask<W> mask = AMask<W>::zero();
+                uint32_t offers = 0, unsup = 0;
+                const int es = evict_eval<true, false, W>(V.P, row, &ev, &mask, &offers, &unsup, &ws);
+                if (unsup || es != kOption) {   // every word the trial wrote
+                    inplace_store(A, row, in);
+                    if (toe != oe) V.own_existing[row] = oe;
+                    if (x.slot != PE_NONE) A.preempted[x.slot] = 0;
+                }
+                if (unsup) {
+                    atomicOr(V.flags, unsup);
+                    if (unsup == kEvictWider) {
+                        V.resume[g] = u;
+                        V.wider[wave_slot(V.n_wider)] = g;
+                    }
+                    if (tj != cj) A.soa.coll_job[row] = cj;
+                    break;   // nothing more for this group in this launch
+                }
+                exhausted = es == kExhausted;   // (a skipped eviction Select counts nowhere)
+                if (es == kOption) {
+                    st = kOption;
+                    final_score = ev.score;
+                    ns = ev.nscores;
+                    for (int k = 0; k < PE_MAX_SCORES; k++) parts[k] = k < (int)ev.nscores ? ev.parts[k] : 0.0;
+                    const uint32_t at = wave_slot(V.n_app);
+                    if (at < V.app_cap) {
+                        uint32_t* rec = V.app + (size_t)at * (1u + W);
+                        rec[0] = x.pos;
+                        mask.store(rec + 1);
+                    } else {
+                        atomicOr(V.flags, kSysgOverflow);
+                    }
+                }
+            }
+            A.status[x.pos] = (uint8_t)(st == kOption ? kOption : (st == kFiltered ? kFiltered : kExhausted));
+            if (A.out) {
+                EmitRec& o = A.out[x.pos];
+                o.row = st == kOption ? (int32_t)row : -1;
+                o.n_scores = ns;
+                o.final_score = final_score;
+                for (int k = 0; k < PE_MAX_SCORES; k++) o.scores[k] = parts[k];
+                o.nodes_evaluated = 1;
+                o.nodes_filtered = st == kFiltered;
+                o.nodes_exhausted = st == kOption ? 0u : exhausted;
+                o.new_offset = 0;   // a one-node list: the cursor wraps to its start
+                o.n_device_offers = 0;
+                for (int q = 0; q < kMaxDevReq; q++) o.device_offer_group[q] = 0;
+                o.flags = 0;
+            }
+            if (st != kOption) {
+                if (tj != cj) A.soa.coll_job[row] = cj;
+                continue;
+            }
+            // Plan.AppendAlloc of the updated alloc; the stop stays
+            t.r.used_cpu += A.ask.cpu;
+            t.r.used_mem += A.ask.mem;
+            t.r.used_disk += A.ask.disk;
+            t.r.used_mbits += A.ask.commit_mbits;
+            t.r.used_dyn += A.ask.commit_dyn;
+            t.coll_tg += 1u;
+            cj = tj + 1u;
+            A.soa.coll_job[row] = cj;
+            oe = toe;
+            V.own_existing[row] = oe;
+            in = t;
+            inplace_store(A, row, in);
+            if (A.dev_free) A.dev_free[row] = in.dev_free;
+            if (x.slot != PE_NONE) {
+                A.preempted[x.slot] = 2;
+                if (A.soa.core_used && A.palloc_cores)   // its reserved cores leave the node's used set
+                    for (int w = 0; w < 4; w++) A.soa.core_used[4 * row + w] &= ~A.palloc_cores[4 * (size_t)x.slot + w];
+            }
+        }
+    }
 }
 
 // One plain (node, group) step on a lane's register image: the pipeline every
@@ -5124,7 +5296,18 @@ hipError_t pe_launch_inplace(const pe::InplaceArgs* a, hipStream_t st) {
     if (!a->n_groups) return hipSuccess;
     uint32_t blocks = (a->n_groups + 255) / 256;
     if (blocks > 2048) blocks = 2048;   // grid-stride beyond
-    hipLaunchKernelGGL(pe::k_inplace, dim3(blocks), dim3(256), 0, st, *a);
+    hipLaunchKernelGGL(pe::k_inplace<false>, dim3(blocks), dim3(256), 0, st, *a,
+                       pe::InplaceStopArgs{nullptr, nullptr, nullptr, nullptr});
+    return hipGetLastError();
+}
+
+// The stopping form (a preempting system stack): *s->n_stopped is zero before.
+hipError_t pe_launch_inplace_stop(const pe::InplaceArgs* a, const pe::InplaceStopArgs* s, hipStream_t st) {
+    if (!a->n_groups) return hipSuccess;
+    if (!s->resume || !s->stopped || !s->n_stopped || !s->own_existing) return hipErrorInvalidValue;
+    uint32_t blocks = (a->n_groups + 255) / 256;
+    if (blocks > 2048) blocks = 2048;   // grid-stride beyond
+    hipLaunchKernelGGL(pe::k_inplace<true>, dim3(blocks), dim3(256), 0, st, *a, *s);
     return hipGetLastError();
 }
 
@@ -5217,6 +5400,21 @@ static inline uint32_t evict_blocks(uint32_t n, uint32_t w) {
     const uint32_t cap = w == 1u ? 2048u : w == 8u ? 256u : 32u;
     if (blocks > cap) blocks = cap;
     return blocks ? blocks : 1u;
+}
+
+// The eviction walk of pe_inplace_update_preempt at width `words` over the
+// groups listed in a->stopped (their count is read on the device; at most
+// `max_groups`).
+hipError_t pe_launch_inplace_evict(const pe::InplaceEvictArgs* a, uint32_t words, uint32_t max_groups, hipStream_t st) {
+    if (!max_groups) return hipSuccess;
+    if (!evict_width_ok(words) || !a->own_existing || !a->resume || !a->stopped || !a->n_stopped || !a->wider ||
+        !a->n_wider || !a->app || !a->n_app || !a->flags || !a->I.status || !a->I.preempted || !a->I.allocs)
+        return hipErrorInvalidValue;
+    const uint32_t blocks = evict_blocks(max_groups, words);
+    if (words == 1u) hipLaunchKernelGGL(pe::k_inplace_evict<1>, dim3(blocks), dim3(256), 0, st, *a);
+    else if (words == 8u) hipLaunchKernelGGL(pe::k_inplace_evict<8>, dim3(blocks), dim3(256), 0, st, *a);
+    else hipLaunchKernelGGL(pe::k_inplace_evict<32>, dim3(blocks), dim3(256), 0, st, *a);
+    return hipGetLastError();
 }
 
 hipError_t pe_launch_evict(const pe::PreemptArgs* a, const pe::EvictResolveArgs* r, hipStream_t st) {

@@ -72,6 +72,12 @@ def load_engine():
         lib.pe_inplace_update.restype = C.c_int
         lib.pe_inplace_update.argtypes = [C.c_void_p, C.c_uint32, abi.u32p, C.c_uint32,
                                           C.POINTER(abi.pe_ranked_node), abi.u8p, abi.u32p]
+        if hasattr(lib, "pe_inplace_update_preempt"):
+            lib.pe_inplace_update_preempt.restype = C.c_int
+            lib.pe_inplace_update_preempt.argtypes = lib.pe_inplace_update.argtypes
+            lib.pe_inplace_update_preempted.restype = C.c_int
+            lib.pe_inplace_update_preempted.argtypes = [C.c_void_p, C.POINTER(abi.u32p), C.POINTER(abi.u32p),
+                                                        C.POINTER(abi.u32p), abi.u32p]
         if hasattr(lib, "pe_system_place_groups"):   # present or absent behind one ABI version
             lib.pe_system_place_groups.restype = C.c_int
             lib.pe_system_place_groups.argtypes = [C.c_void_p, abi.u32p, C.c_uint32, abi.f64p, abi.u8p, abi.u32p,
@@ -769,6 +775,15 @@ def preempted_from_csr(entries, off, allocs, n_tg: int) -> Dict:
     return out
 
 
+def inplace_preempted_from_csr(updates, off, allocs) -> Dict:
+    """pe_inplace_update_preempted's CSR as {list position: [alloc-table rows]}:
+    update updates[i] preempted allocs[off[i]:off[i + 1]]."""
+    out = {}
+    for i, u in enumerate(updates):
+        out[int(u)] = [int(a) for a in allocs[int(off[i]):int(off[i + 1])]]
+    return out
+
+
 def system_place_groups_preempt_by_select(stack, tgs):
     """system_place_groups_by_select's loop, which on a stack with preemption
     enabled evicts where the plain fit is exhausted (the Select's record
@@ -1029,6 +1044,48 @@ class SystemStack(_Stack):
     def __init__(self, sysbatch: bool = False, config: SchedulerConfig = None, device: int = 0,
                  devices: Optional[Sequence[int]] = None):
         super().__init__(load_engine(), "pe_", False, config, device, devices)
+
+    def InplaceUpdatePreempt(self, tg, allocs: Sequence[int], fallback: bool = True):
+        """InplaceUpdate on a stack with preemption enabled, in one call
+        (pe_inplace_update_preempt): the Select of an update whose plain fit
+        fails evicts, and its record carries the whole PreemptedAllocs list
+        (pe_inplace_update_preempted; no PE_MAX_PREEMPT cap). The evicted
+        allocs stay in the plan's proposed state, as inplaceUpdate leaves them
+        (util.go:759-802). Returns InplaceUpdate's (records, status); without
+        preemption on the stack it is InplaceUpdate. A job the call refuses
+        (Unsupported) is answered by inplace_update_by_select when `fallback`."""
+        allocs = [int(a) for a in allocs]
+        try:
+            if not hasattr(self._lib, "pe_inplace_update_preempt"):
+                raise Unsupported(abi.PE_EUNSUPPORTED, "no batched in-place update with preemption behind this ABI")
+            n = len(allocs)
+            a = np.ascontiguousarray(np.asarray(allocs or [0], dtype=np.uint32))
+            out = (abi.pe_ranked_node * max(1, n))()
+            status = np.zeros(max(1, n), dtype=np.uint8)
+            updated = C.c_uint32(0)
+            self._check(self._lib.pe_inplace_update_preempt(self._h, self._tg_index(tg), a.ctypes.data_as(abi.u32p), n,
+                                                            out, status.ctypes.data_as(abi.u8p), C.byref(updated)))
+        except Unsupported:
+            if not fallback:
+                raise
+            return inplace_update_by_select(self, tg, allocs)
+        full = self.InplaceUpdatePreempted()
+        records = [RankedNode.from_c(out[i], self.nodes, full.get(i)) if status[i] == 0 else None for i in range(n)]
+        assert updated.value == sum(1 for r in records if r is not None)
+        return records, [int(x) for x in status[:n]]
+
+    def InplaceUpdatePreempted(self) -> Dict:
+        """{list position: [alloc-table rows]} of the last InplaceUpdatePreempt's
+        evicting updates (pe_inplace_update_preempted)."""
+        up, of, al = abi.u32p(), abi.u32p(), abi.u32p()
+        ne = C.c_uint32(0)
+        self._check(self._lib.pe_inplace_update_preempted(self._h, C.byref(up), C.byref(of), C.byref(al), C.byref(ne)))
+        k = ne.value
+        if not k:
+            return {}
+        off = np.ctypeslib.as_array(of, shape=(k + 1,))
+        return inplace_preempted_from_csr(np.ctypeslib.as_array(up, shape=(k,)), off,
+                                          np.ctypeslib.as_array(al, shape=(int(off[k]),)))
 
     def last_kernel_ms(self) -> float:
         return self._lib.pe_last_kernel_ms(self._h)

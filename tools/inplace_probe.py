@@ -5,8 +5,11 @@ one handle and state, timed two ways through the C ABI:
       pe_plan_pop_update and, on an option, pe_plan_stop + pe_commit per alloc
   (b) pe_inplace_update, one call for the whole list
 
-at two shapes: 1000 updates of a job_c2 service on cluster_c2(10000), and an
-updated system job holding one alloc on each of 100k cluster_c4 nodes. Every
+at three shapes: 1000 updates of a job_c2 service on cluster_c2(10000), an
+updated system job holding one alloc on each of 100k cluster_c4 nodes, and
+that system shape on a stack with preemption enabled (the reference's default
+for system jobs), where (a)'s pe_select evicts and (b) is
+pe_inplace_update_preempt. Every
 repetition starts from the snapshot again (pe_reset_plan + pe_set_job, not
 timed); the two paths alternate; both must return the same statuses before a
 time is printed. Where every node is listed once (the system shape) the
@@ -16,7 +19,7 @@ pass takes minutes); its statuses are compared with that prefix of (b)'s.
 Host clock around calls that end in a device synchronise; the kernel time of
 (b) is the engine's HIP events (pe_last_kernel_ms).
 
-    python tools/inplace_probe.py [--reps 5] [--small] [--out probe.json]
+    python tools/inplace_probe.py [--reps 5] [--small] [--shapes service,system,preempt] [--out probe.json]
 """
 import argparse
 import ctypes as C
@@ -29,7 +32,7 @@ import numpy as np
 sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
 from nomad_amd import abi, synth  # noqa: E402
 from nomad_amd.stack import GenericStack, SystemStack  # noqa: E402
-from nomad_amd.structs import Allocation  # noqa: E402
+from nomad_amd.structs import Allocation, SchedulerConfig  # noqa: E402
 
 
 def service_shape(n_nodes, n_upd):
@@ -46,7 +49,7 @@ def service_shape(n_nodes, n_upd):
     return GenericStack(), nodes, allocs, job, upd.astype(np.uint32)
 
 
-def system_shape(n_nodes):
+def system_shape(n_nodes, preempt=False):
     nodes, allocs = synth.cluster_c4(n_nodes, seed=11)
     base = len(allocs)
     for nd in nodes:
@@ -56,7 +59,9 @@ def system_shape(n_nodes):
     job.version = 2
     job.task_groups[0].tasks[0].cpu = 600
     upd = base + np.random.Generator(np.random.PCG64(12)).permutation(n_nodes)
-    return SystemStack(), nodes, allocs, job, upd.astype(np.uint32)
+    # (preempting: the ~5 % pre-filled nodes' filler, priority 50 under the job's 100, is evicted)
+    st = SystemStack(config=SchedulerConfig(preempt_system=True)) if preempt else SystemStack()
+    return st, nodes, allocs, job, upd.astype(np.uint32)
 
 
 def per_call(st, upd, node_row):
@@ -76,15 +81,15 @@ def per_call(st, upd, node_row):
     return status
 
 
-def batched(st, upd, recs, status):
-    """(b): one pe_inplace_update."""
+def batched(st, upd, recs, status, entry="pe_inplace_update"):
+    """(b): one pe_inplace_update (or pe_inplace_update_preempt)."""
     updated = C.c_uint32(0)
-    st._check(st._lib.pe_inplace_update(st._h, 0, upd.ctypes.data_as(abi.u32p), len(upd), recs,
+    st._check(getattr(st._lib, entry)(st._h, 0, upd.ctypes.data_as(abi.u32p), len(upd), recs,
                                         status.ctypes.data_as(abi.u8p), C.byref(updated)))
     return updated.value
 
 
-def measure(name, shape, reps, cap):
+def measure(name, shape, reps, cap, entry="pe_inplace_update"):
     st, nodes, allocs, job, upd = shape
     st.SetState(nodes, allocs)
     st._lib.pe_flush.restype = C.c_int
@@ -109,7 +114,7 @@ def measure(name, shape, reps, cap):
             if path == "a":
                 sa = per_call(st, upd[:na], node_row)
             else:
-                batched(st, upd, recs, sb)
+                batched(st, upd, recs, sb, entry)
             dt = (time.perf_counter() - t0) * 1e6
             if rep:
                 (ta if path == "a" else tb).append(dt)
@@ -119,7 +124,7 @@ def measure(name, shape, reps, cap):
         print("# %s: repetition %d of %d done" % (name, rep, reps), file=sys.stderr, flush=True)
     a, b, k = np.median(ta) * (n / na), np.median(tb), np.median(tk)
     ta = [x * (n / na) for x in ta]   # per-update figures below divide by n
-    res = {"shape": name, "updates": n, "per_call_updates_timed": na, "nodes": len(nodes), "reps": reps,
+    res = {"shape": name, "entry": entry, "updates": n, "per_call_updates_timed": na, "nodes": len(nodes), "reps": reps,
            "status_counts": [int((sb == v).sum()) for v in (0, 1, 2)],
            "per_call_us_per_update": a / n, "per_call_us_min_max": [min(ta) / n, max(ta) / n],
            "batched_us_per_update": b / n, "batched_us_min_max": [min(tb) / n, max(tb) / n],
@@ -135,14 +140,20 @@ def main():
     ap.add_argument("--small", action="store_true", help="toy sizes (a rehearsal of the tool, not a measurement)")
     ap.add_argument("--per-call-cap", type=int, default=2000,
                     help="updates path (a) runs per repetition when every node is listed once (0: all)")
+    ap.add_argument("--shapes", default="service,system,preempt", help="comma-separated: service, system, preempt")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    shapes = [("service: %d updates" % (50 if args.small else 1000),
-               lambda: service_shape(500 if args.small else 10000, 50 if args.small else 1000)),
-              ("system: one alloc per node", lambda: system_shape(2000 if args.small else 100000))]
+    n_sys = 2000 if args.small else 100000
+    shapes = {"service": ("service: %d updates" % (50 if args.small else 1000),
+                          lambda: service_shape(500 if args.small else 10000, 50 if args.small else 1000),
+                          "pe_inplace_update"),
+              "system": ("system: one alloc per node", lambda: system_shape(n_sys), "pe_inplace_update"),
+              "preempt": ("system, preemption enabled: one alloc per node", lambda: system_shape(n_sys, True),
+                          "pe_inplace_update_preempt")}
     results = []
-    for name, make in shapes:
-        r = measure(name, make(), args.reps, args.per_call_cap)
+    for key in args.shapes.split(","):
+        name, make, entry = shapes[key]
+        r = measure(name, make(), args.reps, args.per_call_cap, entry)
         results.append(r)
         print(json.dumps(r), flush=True)
     if args.out:
