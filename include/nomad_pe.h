@@ -450,9 +450,9 @@ int pe_plan_pop_update(pe_stack* s, uint32_t alloc);
  * PE_EINVAL (nothing changed): tg_index or an alloc row out of range, an alloc
  * listed twice. PE_EUNSUPPORTED (nothing changed; the per-call sequence
  * answers): spreads or distinct_property, reserved-cores asks, static ports,
- * multi-device network nodes, a handle over several devices, pe_set_metrics on,
- * a system stack with preemption enabled (pe_inplace_update_preempt below
- * answers that one). */
+ * multi-device network nodes, a handle over several devices, pe_set_metrics on
+ * (pe_inplace_update_metrics below answers that one), a system stack with
+ * preemption enabled (pe_inplace_update_preempt below answers that one). */
 int pe_inplace_update(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n,
                       pe_ranked_node* out, uint8_t* status, uint32_t* updated);
 /* pe_inplace_update for a system stack with preemption enabled, the reference's
@@ -490,6 +490,24 @@ int pe_inplace_update_preempt(pe_stack* s, uint32_t tg_index, const uint32_t* al
  * yet, or a pe_inplace_update since. */
 int pe_inplace_update_preempted(const pe_stack* s, const uint32_t** updates, const uint32_t** off,
                                 const uint32_t** allocs, uint32_t* n_entries);
+/* pe_inplace_update_preempt for a caller that keeps AllocMetric: inplaceUpdate
+ * ends every successful update with newAlloc.Metrics = ctx.Metrics()
+ * (util.go:801), so a faithful caller runs with pe_set_metrics on, which the
+ * two calls above refuse. This one does not, on a generic stack, a system
+ * stack, or a system stack with preemption enabled. Arguments, result layout,
+ * status codes, the node-list rule, PE_EINVAL cases and
+ * pe_inplace_update_preempted are pe_inplace_update_preempt's; PE_EUNSUPPORTED
+ * (checked before anything changes) is its list without the pe_set_metrics
+ * entry. With metrics off the call is pe_inplace_update_preempt. With metrics
+ * on, records, statuses and every later observable state (the class memo that
+ * turns a later node of a failing class into "computed class ineligible"
+ * included) are those of the per-call sequence run with metrics on, and
+ * pe_inplace_metrics returns each update's maps. No further launch and no
+ * further synchronisation than pe_inplace_update_preempt. pe_last_metrics*
+ * answer PE_ESTATE afterwards: there is no "last Select". */
+int pe_inplace_update_metrics(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n,
+                              pe_ranked_node* out, uint8_t* status, uint32_t* updated);
+/* (pe_inplace_metric and pe_inplace_metrics: below, with the AllocMetric types.) */
 /* Fused count loop of GenericScheduler.computePlacements (generic_sched.go:493-649)
  * for `count` fresh placements of one task group (no preferred / penalty nodes):
  * Select -> AppendAlloc repeated on the device; stops at the first nil option
@@ -751,6 +769,26 @@ int pe_last_metrics_bin(const pe_stack* s, const pe_metric_count** counts, uint3
  * PE_EINVAL for an unknown key. Scorer names: pe_scorer_name. */
 int64_t pe_metric_string(const pe_stack* s, uint32_t key, char* buf, size_t cap);
 const char* pe_scorer_name(uint32_t scorer);
+/* What update i's Select left in its AllocMetric maps (pe_last_metrics_bin
+ * after that Select in the per-call sequence). A Select over one node records
+ * at most one key per map, each with count 1, or one ScoreMetaData item. Keys
+ * are pe_metric_count's (pe_metric_string resolves them). */
+typedef struct pe_inplace_metric {
+    uint32_t class_key;   /* ClassFiltered (status 1) / ClassExhausted (status 2) key, or PE_NONE: a node
+                           * without a NodeClass, or no key recorded (below) */
+    uint32_t reason_key;  /* ConstraintFiltered (status 1) / DimensionExhausted (status 2) key, or PE_NONE:
+                           * on a preempting stack, a BinPack with evict that gave the node up without
+                           * ExhaustedNode (a network or device preemption that found nothing) */
+    uint32_t score;       /* status 0: index into scores[]; otherwise PE_NONE */
+} pe_inplace_metric;
+/* The maps of the last pe_inplace_update_metrics that ran with metrics on:
+ * m[n] by list position, scores[n_scores] one item per status-0 update in list
+ * order (the scorers in the order pe_last_metrics_bin lists them; an evicting
+ * update carries the eviction Select's named scores). Page-locked staging,
+ * valid until the next pe_inplace_update* call on the handle. PE_ESTATE: no
+ * such call yet, it ran with metrics off, or a pe_inplace_update* call since. */
+int pe_inplace_metrics(const pe_stack* s, const pe_inplace_metric** m, uint32_t* n,
+                       const pe_metric_score** scores, uint32_t* n_scores);
 /* EvalEligibility (scheduler/context.go:190-356) as the reference chain would
  * hold it after this evaluation's Selects: the job-level and per task group
  * ComputedClassFeasibility entries FeasibilityWrapper.Next writes for every

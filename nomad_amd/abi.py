@@ -236,6 +236,7 @@ ENGINE_SYMBOLS = [
     "pe_system_place_groups_metrics", "pe_system_groups_metrics",
     "pe_chain_wide_stats",
     "pe_inplace_update_preempt", "pe_inplace_update_preempted",
+    "pe_inplace_update_metrics", "pe_inplace_metrics",
 ]
 
 
@@ -267,6 +268,10 @@ class pe_metric_count(C.Structure):   # nomad_pe.h: one AllocMetric map entry
 class pe_metric_score(C.Structure):   # nomad_pe.h: one NodeScoreMeta
     _fields_ = [("row", C.c_int32), ("n_scores", C.c_uint32), ("norm", C.c_double),
                 ("scorer", C.c_uint8 * PE_MAX_SCORES), ("score", C.c_double * PE_MAX_SCORES)]
+
+
+class pe_inplace_metric(C.Structure):   # nomad_pe.h: one update's maps (pe_inplace_metrics)
+    _fields_ = [("class_key", C.c_uint32), ("reason_key", C.c_uint32), ("score", C.c_uint32)]
 
 
 class pe_spec_view(C.Structure):

@@ -956,6 +956,12 @@ struct pe_stack {
     PinnedMem h_inplace_csr;
     uint32_t inplace_pre_entries = 0;
     bool inplace_pre_valid = false;
+    // pe_inplace_update_metrics: the updates' maps [pe_inplace_metric n | pe_metric_score n_scores]
+    // (pe_inplace_metrics)
+    PinnedMem h_inplace_metrics;
+    uint32_t inplace_m_n = 0, inplace_m_scores = 0;
+    size_t inplace_m_scores_off = 0;
+    bool inplace_m_valid = false;
     SysGroupsState sysg;   // pe_system_place_groups*: buffers, and what the accessors read
     bool stopped(uint32_t ai) const { return ai < stop_count.size() && stop_count[ai] > 0; }
 
@@ -5859,9 +5865,11 @@ struct MetricAcc {
 // FeasibilityWrapper half of one Select's maps: the window's rows in visit
 // order against the reference memo shadow (feasible.go:1061-1153); rows that
 // pass go to `rows` for k_trace. `log` (or null) receives the memo changes.
+// `why_out` (or null): the reason key of the k-th visited row where it fails.
 static void metrics_walk(pe_stack* s, TgPlan& g, const std::vector<uint32_t>& order, uint32_t start,
                          uint32_t evaluated, MetricAcc& acc, std::vector<uint32_t>& rows,
-                         std::vector<MemoDelta>* log = nullptr, std::vector<uint8_t>* pass = nullptr) {
+                         std::vector<MemoDelta>* log = nullptr, std::vector<uint8_t>* pass = nullptr,
+                         uint32_t* why_out = nullptr) {
     const size_t m = order.size();
     if (s->ref_job_memo.size() != s->ncls) s->ref_job_memo.assign(s->ncls, -1);
     auto& rt = s->ref_tg_memo[g.name];
@@ -5917,7 +5925,9 @@ static void metrics_walk(pe_stack* s, TgPlan& g, const std::vector<uint32_t>& or
             }
         }
         if (why) {
-            acc.filter(s, row, why == kIneligible ? ineligible : s->mkey_p(why));
+            const uint32_t key = why == kIneligible ? ineligible : s->mkey_p(why);
+            acc.filter(s, row, key);
+            if (why_out) why_out[k] = key;
         } else {
             rows.push_back(row);
             if (pass) (*pass)[p] = 1;
@@ -8340,6 +8350,72 @@ static int inplace_csr_set(pe_stack* s, const std::vector<std::pair<uint32_t, st
     return PE_OK;
 }
 
+// pe_inplace_update_metrics' maps from what the walk left by
+// list position: `code` (k_trace's code space) and `named` (k_trace's six
+// score values) beside the statuses. The FeasibilityWrapper reasons are the
+// host's: one metrics_walk pass over the update list in list order against the
+// reference memo, exactly the per-call sequence's one-node walks one after the
+// other (the first listed node of a failing class gets the checker's reason,
+// later ones "computed class ineligible", escaped constraints are decided per
+// node), which also leaves the memo where that sequence leaves it. A device
+// status that disagrees with the walk is the kTrMismatch guard.
+static int inplace_metrics_finish(pe_stack* s, TgPlan& g, uint32_t n, const uint8_t* status, const uint32_t* code,
+                                  const double* named, bool evicting, const std::string& fn) {
+    std::vector<uint8_t> pass(n, 0);
+    std::vector<uint32_t> why(n, PE_NONE), passed;
+    {
+        MetricAcc walk;
+        metrics_walk(s, g, s->visit, 0, n, walk, passed, nullptr, &pass, why.data());
+    }
+    const pe::Ask a = ask_for(s, g);
+    std::vector<pe_inplace_metric> m(n);
+    std::vector<pe_metric_score> scores;
+    std::vector<pe_metric_count> unused;
+    std::map<int, std::vector<uint32_t>> counts;
+    MetricAcc acc;
+    const auto mismatch = [&]() { return s->fail(PE_EINTERNAL, fn + "device verdict differs from the host walk"); };
+    for (uint32_t i = 0; i < n; i++) {
+        pe_inplace_metric& e = m[i];
+        e.class_key = e.reason_key = e.score = PE_NONE;
+        const uint32_t row = s->visit[i], base = code[i] & 255u;
+        if (!pass[i]) {   // FilterNode(option, reason) of the wrapper
+            if (status[i] != 1 || base != pe::kTrWrapper) return mismatch();
+            e.class_key = MetricAcc::mclass(s, row);
+            e.reason_key = why[i];
+            continue;
+        }
+        if (status[i] == 0) {
+            if (base != pe::kTrOption) return mismatch();
+            acc.reset();
+            const int rc = metrics_outcome(s, g, a, row, code[i], named + (size_t)pe::kInplaceNamed * i, acc, counts);
+            if (rc) return rc;
+            e.score = (uint32_t)scores.size();
+            metrics_bin_into(acc, unused, scores);
+            if (scores.size() != (size_t)e.score + 1) return mismatch();
+            continue;
+        }
+        if (status[i] == 2 && base == pe::kTrOption) {   // BinPack with evict gave the node up without ExhaustedNode
+            if (!evicting) return mismatch();
+            continue;
+        }
+        uint32_t kind, key;
+        if (!trace_key(s, code[i], &kind, &key)) return mismatch();
+        if (kind != (status[i] == 1 ? PE_METRIC_CONSTRAINT_FILTERED : PE_METRIC_DIMENSION_EXHAUSTED)) return mismatch();
+        e.class_key = MetricAcc::mclass(s, row);
+        e.reason_key = key;
+    }
+    const size_t sc_off = (sizeof(pe_inplace_metric) * (size_t)n + 15) & ~(size_t)15;
+    HIP_TRY(s, s->h_inplace_metrics.ensure(sc_off + sizeof(pe_metric_score) * std::max<size_t>(scores.size(), 1)));
+    unsigned char* w = s->h_inplace_metrics.as<unsigned char>();
+    std::memcpy(w, m.data(), sizeof(pe_inplace_metric) * (size_t)n);
+    if (!scores.empty()) std::memcpy(w + sc_off, scores.data(), sizeof(pe_metric_score) * scores.size());
+    s->inplace_m_n = n;
+    s->inplace_m_scores = (uint32_t)scores.size();
+    s->inplace_m_scores_off = sc_off;
+    s->inplace_m_valid = true;
+    return PE_OK;
+}
+
 // inplaceUpdate's loop (util.go:692-806) in one launch: per
 // listed alloc the sequence pe_plan_stop, pe_set_nodes([its node]), pe_select,
 // pe_plan_pop_update and, on an option, pe_plan_stop + pe_commit, with the
@@ -8353,10 +8429,18 @@ static int inplace_csr_set(pe_stack* s, const std::vector<std::pair<uint32_t, st
 // commit stays the plain one: inplaceUpdate never reads PreemptedAllocs
 // (util.go:759-802), so nothing about the evicted allocs enters h_preempted,
 // pcount or the plan; they are kept as a CSR (pe_inplace_update_preempted).
+//
+// `met_call`: pe_inplace_update_metrics, a pre_call that does
+// not refuse AllocMetric. With the maps on, the walks run in their metrics
+// forms: codes and named scores by list position sit behind the statuses in
+// the same result buffer and come back in the same DMA;
+// inplace_metrics_finish turns them into the updates' maps.
 static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
-                              uint8_t* status, uint32_t* updated, bool pre_call) {
+                              uint8_t* status, uint32_t* updated, bool pre_call, bool met_call = false) {
     if (!s) return PE_EINVAL;
-    const std::string fn = pre_call ? "pe_inplace_update_preempt: " : "pe_inplace_update: ";
+    const std::string fn = met_call ? "pe_inplace_update_metrics: "
+                                    : (pre_call ? "pe_inplace_update_preempt: " : "pe_inplace_update: ");
+    const bool metrics = met_call && s->metrics_on;
     if (updated) *updated = 0;
     if (n && (!allocs || !status)) return s->fail(PE_EINVAL, "null alloc list or status array");
     if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
@@ -8372,6 +8456,13 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     }
     if (n == 0) {
         s->inplace_pre_valid = false;
+        s->inplace_m_valid = false;
+        if (metrics) {
+            s->inplace_m_n = s->inplace_m_scores = 0;
+            s->inplace_m_scores_off = 0;
+            HIP_TRY(s, s->h_inplace_metrics.ensure(sizeof(pe_metric_score)));
+            s->inplace_m_valid = true;
+        }
         return pre_call ? inplace_csr_set(s, {}) : PE_OK;
     }
     TgPlan& g = *s->tgs[tgi];
@@ -8379,7 +8470,7 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     // what the batched path does not model: the caller's per-Select loop answers
     const char* why = nullptr;
     if (!s->kids.empty()) why = "a handle over several devices";
-    else if (s->metrics_on) why = "AllocMetric maps are on (pe_set_metrics)";
+    else if (s->metrics_on && !met_call) why = "AllocMetric maps are on (pe_set_metrics)";
     else if (s->cfg.stack_kind != PE_STACK_GENERIC && s->cfg.preempt && !pre_call)
         why = "a system stack with preemption (BinPack evicts)";
     else if (g.ask.cores > 0) why = "a reserved-cores ask";
@@ -8424,6 +8515,7 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     int rc = spec_flush(s);
     if (rc) return rc;
     s->inplace_pre_valid = false;
+    s->inplace_m_valid = false;
     s->gen++;
     s->metrics_valid = false;
     s->pre_overflow.clear();
@@ -8497,7 +8589,11 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     // flags), then the appended records [list position | mask words], at most
     // one per update. The walk starts at the narrowest width that covers all
     // but at most an eighth of the snapshot's nodes, as system_place_groups does
-    const size_t ctl_off = (st_off + n + 15) & ~(size_t)15;
+    // (metrics form: the named scores and the codes come first, by list position)
+    const size_t named_off = (st_off + n + 7) & ~(size_t)7;
+    const size_t code_off = named_off + sizeof(double) * pe::kInplaceNamed * (size_t)n;
+    const size_t res_end = metrics ? code_off + sizeof(uint32_t) * (size_t)n : st_off + n;
+    const size_t ctl_off = (res_end + 15) & ~(size_t)15;
     const size_t app_off = ctl_off + 4 * sizeof(uint32_t);
     uint32_t words = 0;
     if (evicting) {
@@ -8507,7 +8603,7 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
         else if (s->n_beyond_w8 <= nn / 8) words = std::min(words, 8u);
         words_max = std::max(words_max, words);
     }
-    const auto dma_bytes = [&](uint32_t w) { return evicting ? app_off + sizeof(uint32_t) * (1 + (size_t)w) * n : st_off + n; };
+    const auto dma_bytes = [&](uint32_t w) { return evicting ? app_off + sizeof(uint32_t) * (1 + (size_t)w) * n : res_end; };
     const size_t bytes = dma_bytes(words);
     HIP_TRY(s, s->d_inplace_out.ensure(dma_bytes(words_max)));
     HIP_TRY(s, s->h_inplace_out.ensure(dma_bytes(words_max)));
@@ -8527,6 +8623,10 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     A.log10 = s->log10;
     A.out = out ? reinterpret_cast<pe::EmitRec*>(dres) : nullptr;
     A.status = dres + st_off;
+    pe::InplaceMetricsArgs M;
+    M.named = reinterpret_cast<double*>(dres + named_off);
+    M.code = reinterpret_cast<uint32_t*>(dres + code_off);
+    const pe::InplaceMetricsArgs* Mp = metrics ? &M : nullptr;
     pe::InplaceEvictArgs V;
     const uint32_t ng = A.n_groups;
     uint32_t* ctl = reinterpret_cast<uint32_t*>(dres + ctl_off);
@@ -8542,7 +8642,7 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
         S.stopped = lanes + ng;
         S.n_stopped = ctl;
         S.own_existing = s->d_own_existing.as<uint32_t>();
-        HIP_TRY_STATE(s, pe_launch_inplace_stop(&A, &S, s->stream));
+        HIP_TRY_STATE(s, pe_launch_inplace_stop(&A, &S, Mp, s->stream));
         std::memset(&V, 0, sizeof(V));
         V.I = A;
         V.P = preempt_args(s, g);
@@ -8557,9 +8657,9 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
         V.n_app = ctl + 2;
         V.app_cap = n;
         V.flags = ctl + 3;
-        HIP_TRY_STATE(s, pe_launch_inplace_evict(&V, words, ng, s->stream));
+        HIP_TRY_STATE(s, pe_launch_inplace_evict(&V, Mp, words, ng, s->stream));
     } else {
-        HIP_TRY_STATE(s, pe_launch_inplace(&A, s->stream));
+        HIP_TRY_STATE(s, pe_launch_inplace(&A, Mp, s->stream));
     }
     HIP_TRY(s, hipEventRecord(s->ev1, s->stream));
     HIP_TRY(s, hipMemcpyAsync(s->h_inplace_out.p, dres, bytes, hipMemcpyDeviceToHost, s->stream));
@@ -8609,7 +8709,7 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
         V.P.mask_words = words;
         HIP_TRY(s, hipMemsetAsync(V.n_wider, 0, sizeof(uint32_t), s->stream));
         HIP_TRY(s, hipMemsetAsync(ctl + 2, 0, sizeof(uint32_t) * 2, s->stream));
-        HIP_TRY_STATE(s, pe_launch_inplace_evict(&V, words, ng, s->stream));
+        HIP_TRY_STATE(s, pe_launch_inplace_evict(&V, Mp, words, ng, s->stream));
         HIP_TRY(s, hipMemcpyAsync(s->h_inplace_out.p, dres, dma_bytes(words), hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(s, hipStreamSynchronize(s->stream));
     }
@@ -8646,6 +8746,11 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     }
     if (pre_call) {
         rc = inplace_csr_set(s, evicted);
+        if (rc) return rc;
+    }
+    if (metrics) {
+        rc = inplace_metrics_finish(s, g, n, status, reinterpret_cast<const uint32_t*>(h + code_off),
+                                    reinterpret_cast<const double*>(h + named_off), evicting, fn);
         if (rc) return rc;
     }
     if (updated) *updated = up;
@@ -10012,6 +10117,24 @@ int pe_inplace_update_preempt(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
                               uint8_t* status, uint32_t* updated) {
     PE_FLUSH_RESET(s);
     return inplace_update_one(s, tgi, allocs, n, out, status, updated, true);
+}
+
+int pe_inplace_update_metrics(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                              uint8_t* status, uint32_t* updated) {
+    PE_FLUSH_RESET(s);
+    return inplace_update_one(s, tgi, allocs, n, out, status, updated, true, true);
+}
+
+int pe_inplace_metrics(const pe_stack* s, const pe_inplace_metric** m, uint32_t* n, const pe_metric_score** scores,
+                       uint32_t* n_scores) {
+    if (!s || !m || !n || !scores || !n_scores) return PE_EINVAL;
+    if (!s->inplace_m_valid || !s->h_inplace_metrics.p) return PE_ESTATE;
+    const unsigned char* w = s->h_inplace_metrics.as<unsigned char>();
+    *m = reinterpret_cast<const pe_inplace_metric*>(w);
+    *scores = reinterpret_cast<const pe_metric_score*>(w + s->inplace_m_scores_off);
+    *n = s->inplace_m_n;
+    *n_scores = s->inplace_m_scores;
+    return PE_OK;
 }
 
 int pe_inplace_update_preempted(const pe_stack* s, const uint32_t** updates, const uint32_t** off,

@@ -29,6 +29,8 @@ constexpr int kMaxDevGroups = 4;      // device groups per node on device (u8 fr
 // k_trace outcome codes (AllocMetric reasons after the FeasibilityWrapper)
 enum : uint32_t {
     kTrOption = 0, kTrDistinctHosts = 1, kTrDistinctProp = 2,
+    kTrWrapper = 3,             // k_inplace's metrics form only: the folded FeasibilityWrapper verdict
+                                // filtered the node (the reason is the host walk's)
     kTrNoAddr = 10, kTrDynPorts = 11, kTrNoNetworks = 12, kTrBandwidth = 13, kTrTaskDyn = 14,
     kTrStaticPort = 15,         // the reason string is rebuilt on the host (static_port_reason)
     kTrTaskStatic = 16,         // the task network's static ports (task_port_reason)
@@ -546,6 +548,21 @@ struct InplaceStopArgs {
     uint32_t* stopped;                // [n_groups] the groups that stopped, in any order
     uint32_t* n_stopped;              // [1]
     uint32_t* own_existing;           // [n rows] PreemptArgs::own_existing: drops with an updated own alloc
+};
+
+// pe_inplace_update_metrics: what each update's Select would
+// leave in its AllocMetric maps, by list position, written by the metrics forms
+// of the two walks (k_inplace<*, true>, k_inplace_evict<*, true>).
+constexpr uint32_t kInplaceNamed = 6;   // k_trace's score layout
+struct InplaceMetricsArgs {
+    // a k_trace code: kTrOption for an updated alloc; kTrWrapper or
+    // kTrDistinctHosts for a filtered one; for an exhausted one the dimension
+    // (trace_offers, trace_fit on the trial image, or evict_eval's dim_out;
+    // 0: the eviction Select gave the node up without ExhaustedNode)
+    uint32_t* code;                   // [n]
+    // an updated alloc's ScoreNode values as k_trace lays them out: binpack,
+    // devices, job-anti-affinity, node-affinity, allocation-spread, NormScore
+    double* named;                    // [n * kInplaceNamed]
 };
 
 struct InplaceEvictArgs {

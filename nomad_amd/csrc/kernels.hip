@@ -4438,9 +4438,48 @@ __global__ void __launch_bounds__(256) k_md_gate(MdNet* md, const uint32_t* coll
 // placeholders (coll_job - own_existing) stay the job's plan placements.
 __device__ __forceinline__ uint32_t wave_slot(uint32_t* counter);
 
-template <bool kStop>
+// kMetrics (AllocMetric on): the same walk on the same images,
+// so the same outcomes and score bits. Beside them, by list position, what the
+// update's Select leaves in its maps: a k_trace code for an outcome that is not
+// an option (the folded FeasibilityWrapper verdict or distinct_hosts for a
+// filtered node; trace_offers then trace_fit on the trial image for an
+// exhausted one, which is the state that Select saw) and an option's ScoreNode
+// values in k_trace's layout, from the record's own score_into call, whether or
+// not records were asked for. With kStop an exhausted plain fit is not final
+// and records nothing.
+__device__ __forceinline__ uint32_t inplace_filter_code(const TgTables& t, uint32_t row, const NodeIn& in) {
+    bool ok;
+    if (t.node_feas) ok = in.feas != 0;
+    else {
+        ok = t.class_ok[in.r.cls] != 0;
+        if (t.node_ok) ok = ok && t.node_ok[row] != 0;
+    }
+    return ok ? kTrDistinctHosts : kTrWrapper;   // (no property sets on this path)
+}
+
+__device__ __forceinline__ uint32_t inplace_exhaust_code(const NodeSoA& s, const TgTables& t, const Ask& a, uint32_t row,
+                                                         const NodeIn& in) {
+    uint32_t code = trace_offers(t, a, row, in, 0u);
+    if (code == kTrOption) code = trace_fit(s, a, row, in.r, 0u, false);
+    return code == kTrOption ? (uint32_t)kTrMismatch : code;
+}
+
+// score_into's parts (append order) by scorer, as k_trace names them.
+__device__ __forceinline__ void inplace_named(const Ask& a, const ScoreIn& si, const double* parts, double norm,
+                                              double* o) {
+    uint32_t k = 1;
+    o[0] = parts[0];
+    o[1] = a.dev_tw != 0.0 ? parts[k++] : 0.0;
+    o[2] = (a.anti_aff && si.coll > 0) ? parts[k++] : 0.0;
+    if (si.penalty) k++;
+    o[3] = si.aff != 0.0 ? parts[k++] : 0.0;
+    o[4] = si.spread != 0.0 ? parts[k++] : 0.0;
+    o[5] = norm;
+}
+
+template <bool kStop, bool kMetrics>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
-k_inplace(InplaceArgs A, InplaceStopArgs S) {
+k_inplace(InplaceArgs A, InplaceStopArgs S, InplaceMetricsArgs M) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < A.n_groups; g += stride) {
         const uint32_t b = A.group_off[g], e = A.group_off[g + 1];
@@ -4492,11 +4531,28 @@ k_inplace(InplaceArgs A, InplaceStopArgs S) {
                 for (int q = 0; q < kMaxDevReq; q++) o.device_offer_group[q] = 0;
                 o.flags = 0;
             }
+            if (kMetrics)
+                M.code[x.pos] = st == kOption ? (uint32_t)kTrOption
+                                : (st == kFiltered ? inplace_filter_code(A.tg, row, t)
+                                                   : inplace_exhaust_code(A.soa, A.tg, A.ask, row, t));
             if (st != kOption) {
                 if (tj != cj) A.soa.coll_job[row] = cj;
                 continue;
             }
-            if (A.out) {
+            if (kMetrics) {
+                lookup_scores(A.tg, nullptr, nullptr, row, t.r.cls, &si);
+                double parts[PE_MAX_SCORES];
+                for (int k = 0; k < PE_MAX_SCORES; k++) parts[k] = 0.0;
+                uint32_t ns;
+                const double fs = score_into<true>(A.ask, A.log10, si, parts, &ns);
+                inplace_named(A.ask, si, parts, fs, M.named + (size_t)x.pos * kInplaceNamed);
+                if (A.out) {
+                    EmitRec& o = A.out[x.pos];
+                    o.final_score = fs;
+                    o.n_scores = ns;
+                    for (int k = 0; k < PE_MAX_SCORES; k++) o.scores[k] = parts[k];
+                }
+            } else if (A.out) {
                 EmitRec& o = A.out[x.pos];
                 lookup_scores(A.tg, nullptr, nullptr, row, t.r.cls, &si);
                 uint32_t ns;
@@ -4587,8 +4643,14 @@ __device__ __forceinline__ void inplace_store(const InplaceArgs& A, uint32_t row
 // whenever evict_eval runs or the lane leaves. A node beyond the width
 // commits nothing from that update on: the group keeps its resume index,
 // joins the wider list and raises kEvictWider.
-template <int W>
-__global__ void __launch_bounds__(256) k_inplace_evict(InplaceEvictArgs V) {
+//
+// kMetrics: the plain step's codes and named scores as
+// k_inplace's metrics form writes them; evict_eval also returns an option's
+// ScoreNode values and the dimension of an update that stays exhausted (0: it
+// gave the node up without ExhaustedNode). All by list position, so a relaunch
+// at a wider width rewrites the same words.
+template <int W, bool kMetrics>
+__global__ void __launch_bounds__(256) k_inplace_evict(InplaceEvictArgs V, InplaceMetricsArgs M) {
     const InplaceArgs& A = V.I;
     const uint32_t n = *V.n_stopped;
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -4627,10 +4689,14 @@ __global__ void __launch_bounds__(256) k_inplace_evict(InplaceEvictArgs V) {
             int st = status_loaded<false>(A.soa, A.tg, A.tg.class_ok, A.ask, 0u, row, t, &si);
             double final_score = 0.0, parts[PE_MAX_SCORES];
             uint32_t ns = 0, exhausted = st == kExhausted;
+            uint32_t mcode = kTrOption;   // (kMetrics)
             for (int k = 0; k < PE_MAX_SCORES; k++) parts[k] = 0.0;
             if (st == kOption) {
                 lookup_scores(A.tg, nullptr, nullptr, row, t.r.cls, &si);
                 final_score = score_into<true>(A.ask, A.log10, si, parts, &ns);
+                if (kMetrics) inplace_named(A.ask, si, parts, final_score, M.named + (size_t)x.pos * kInplaceNamed);
+            } else if (kMetrics && st == kFiltered) {
+                mcode = inplace_filter_code(A.tg, row, t);
             } else if (st == kExhausted) {
                 // the trial, where evict_eval reads it
                 inplace_store(A, row, t);
@@ -4638,8 +4704,19 @@ __global__ void __launch_bounds__(256) k_inplace_evict(InplaceEvictArgs V) {
                 if (x.slot != PE_NONE) A.preempted[x.slot] = 2;
                 NodeEval ev;
                 AMask<W> mask = AMask<W>::zero();
-                uint32_t offers = 0, unsup = 0;
-                const int es = evict_eval<true, false, W>(V.P, row, &ev, &mask, &offers, &unsup, &ws);
+                uint32_t offers = 0, unsup = 0, nflags = 0, dim = 0;
+                double named[7];   // (kMetrics)
+                const int es = evict_eval<true, false, W>(V.P, row, &ev, &mask, &offers, &unsup, &ws,
+                                                          kMetrics ? named : nullptr, kMetrics ? &nflags : nullptr,
+                                                          kMetrics ? &dim : nullptr);
+                if (kMetrics && !unsup) {
+                    mcode = es == kExhausted ? dim : (uint32_t)kTrOption;   // (a skipped eviction Select: no key)
+                    if (es == kOption) {
+                        double* o = M.named + (size_t)x.pos * kInplaceNamed;
+                        for (int k = 0; k < 5; k++) o[k] = named[k];
+                        o[5] = named[6];
+                    }
+                }
                 if (unsup || es != kOption) {   // every word the trial wrote
                     inplace_store(A, row, in);
                     if (toe != oe) V.own_existing[row] = oe;
@@ -4671,6 +4748,7 @@ __global__ void __launch_bounds__(256) k_inplace_evict(InplaceEvictArgs V) {
                 }
             }
             A.status[x.pos] = (uint8_t)(st == kOption ? kOption : (st == kFiltered ? kFiltered : kExhausted));
+            if (kMetrics) M.code[x.pos] = mcode;
             if (A.out) {
                 EmitRec& o = A.out[x.pos];
                 o.row = st == kOption ? (int32_t)row : -1;
@@ -5292,22 +5370,34 @@ hipError_t pe_launch_system(const pe::SystemArgs* a, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t pe_launch_inplace(const pe::InplaceArgs* a, hipStream_t st) {
+// `m` (or null): the metrics form (pe_inplace_update_metrics with AllocMetric on).
+hipError_t pe_launch_inplace(const pe::InplaceArgs* a, const pe::InplaceMetricsArgs* m, hipStream_t st) {
     if (!a->n_groups) return hipSuccess;
     uint32_t blocks = (a->n_groups + 255) / 256;
     if (blocks > 2048) blocks = 2048;   // grid-stride beyond
-    hipLaunchKernelGGL(pe::k_inplace<false>, dim3(blocks), dim3(256), 0, st, *a,
-                       pe::InplaceStopArgs{nullptr, nullptr, nullptr, nullptr});
+    const pe::InplaceStopArgs none{nullptr, nullptr, nullptr, nullptr};
+    if (m) {
+        if (!m->code || !m->named) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((pe::k_inplace<false, true>), dim3(blocks), dim3(256), 0, st, *a, none, *m);
+    } else {
+        hipLaunchKernelGGL((pe::k_inplace<false, false>), dim3(blocks), dim3(256), 0, st, *a, none,
+                           pe::InplaceMetricsArgs{nullptr, nullptr});
+    }
     return hipGetLastError();
 }
 
 // The stopping form (a preempting system stack): *s->n_stopped is zero before.
-hipError_t pe_launch_inplace_stop(const pe::InplaceArgs* a, const pe::InplaceStopArgs* s, hipStream_t st) {
+hipError_t pe_launch_inplace_stop(const pe::InplaceArgs* a, const pe::InplaceStopArgs* s,
+                                  const pe::InplaceMetricsArgs* m, hipStream_t st) {
     if (!a->n_groups) return hipSuccess;
     if (!s->resume || !s->stopped || !s->n_stopped || !s->own_existing) return hipErrorInvalidValue;
+    if (m && (!m->code || !m->named)) return hipErrorInvalidValue;
     uint32_t blocks = (a->n_groups + 255) / 256;
     if (blocks > 2048) blocks = 2048;   // grid-stride beyond
-    hipLaunchKernelGGL(pe::k_inplace<true>, dim3(blocks), dim3(256), 0, st, *a, *s);
+    if (m) hipLaunchKernelGGL((pe::k_inplace<true, true>), dim3(blocks), dim3(256), 0, st, *a, *s, *m);
+    else
+        hipLaunchKernelGGL((pe::k_inplace<true, false>), dim3(blocks), dim3(256), 0, st, *a, *s,
+                           pe::InplaceMetricsArgs{nullptr, nullptr});
     return hipGetLastError();
 }
 
@@ -5405,15 +5495,24 @@ static inline uint32_t evict_blocks(uint32_t n, uint32_t w) {
 // The eviction walk of pe_inplace_update_preempt at width `words` over the
 // groups listed in a->stopped (their count is read on the device; at most
 // `max_groups`).
-hipError_t pe_launch_inplace_evict(const pe::InplaceEvictArgs* a, uint32_t words, uint32_t max_groups, hipStream_t st) {
+hipError_t pe_launch_inplace_evict(const pe::InplaceEvictArgs* a, const pe::InplaceMetricsArgs* m, uint32_t words,
+                                   uint32_t max_groups, hipStream_t st) {
     if (!max_groups) return hipSuccess;
     if (!evict_width_ok(words) || !a->own_existing || !a->resume || !a->stopped || !a->n_stopped || !a->wider ||
         !a->n_wider || !a->app || !a->n_app || !a->flags || !a->I.status || !a->I.preempted || !a->I.allocs)
         return hipErrorInvalidValue;
+    if (m && (!m->code || !m->named)) return hipErrorInvalidValue;
     const uint32_t blocks = evict_blocks(max_groups, words);
-    if (words == 1u) hipLaunchKernelGGL(pe::k_inplace_evict<1>, dim3(blocks), dim3(256), 0, st, *a);
-    else if (words == 8u) hipLaunchKernelGGL(pe::k_inplace_evict<8>, dim3(blocks), dim3(256), 0, st, *a);
-    else hipLaunchKernelGGL(pe::k_inplace_evict<32>, dim3(blocks), dim3(256), 0, st, *a);
+    const pe::InplaceMetricsArgs none{nullptr, nullptr};
+    if (m) {
+        if (words == 1u) hipLaunchKernelGGL((pe::k_inplace_evict<1, true>), dim3(blocks), dim3(256), 0, st, *a, *m);
+        else if (words == 8u) hipLaunchKernelGGL((pe::k_inplace_evict<8, true>), dim3(blocks), dim3(256), 0, st, *a, *m);
+        else hipLaunchKernelGGL((pe::k_inplace_evict<32, true>), dim3(blocks), dim3(256), 0, st, *a, *m);
+    } else {
+        if (words == 1u) hipLaunchKernelGGL((pe::k_inplace_evict<1, false>), dim3(blocks), dim3(256), 0, st, *a, none);
+        else if (words == 8u) hipLaunchKernelGGL((pe::k_inplace_evict<8, false>), dim3(blocks), dim3(256), 0, st, *a, none);
+        else hipLaunchKernelGGL((pe::k_inplace_evict<32, false>), dim3(blocks), dim3(256), 0, st, *a, none);
+    }
     return hipGetLastError();
 }
 

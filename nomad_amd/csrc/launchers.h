@@ -8,9 +8,11 @@
 size_t pe_place_lds_bytes(bool full, int hash_bits, bool packed, size_t pset_bytes);
 hipError_t pe_launch_place(const pe::BatchArgs* a, uint32_t n_evals, bool full, hipStream_t st);
 hipError_t pe_launch_system(const pe::SystemArgs* a, hipStream_t st);
-hipError_t pe_launch_inplace(const pe::InplaceArgs* a, hipStream_t st);
-hipError_t pe_launch_inplace_stop(const pe::InplaceArgs* a, const pe::InplaceStopArgs* s, hipStream_t st);
-hipError_t pe_launch_inplace_evict(const pe::InplaceEvictArgs* a, uint32_t words, uint32_t max_groups, hipStream_t st);
+hipError_t pe_launch_inplace(const pe::InplaceArgs* a, const pe::InplaceMetricsArgs* m_or_null, hipStream_t st);
+hipError_t pe_launch_inplace_stop(const pe::InplaceArgs* a, const pe::InplaceStopArgs* s,
+                                  const pe::InplaceMetricsArgs* m_or_null, hipStream_t st);
+hipError_t pe_launch_inplace_evict(const pe::InplaceEvictArgs* a, const pe::InplaceMetricsArgs* m_or_null,
+                                   uint32_t words, uint32_t max_groups, hipStream_t st);
 hipError_t pe_launch_system_groups(const pe::SystemGroupsArgs* a, const pe::SysStopArgs* s_or_null,
                                    const pe::SysMetricsArgs* m_or_null, hipStream_t st);
 hipError_t pe_launch_system_groups_evict(const pe::SysEvictArgs* a, uint32_t words, uint32_t max_lanes, bool metrics,

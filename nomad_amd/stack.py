@@ -78,6 +78,12 @@ def load_engine():
             lib.pe_inplace_update_preempted.restype = C.c_int
             lib.pe_inplace_update_preempted.argtypes = [C.c_void_p, C.POINTER(abi.u32p), C.POINTER(abi.u32p),
                                                         C.POINTER(abi.u32p), abi.u32p]
+        if hasattr(lib, "pe_inplace_update_metrics"):
+            lib.pe_inplace_update_metrics.restype = C.c_int
+            lib.pe_inplace_update_metrics.argtypes = lib.pe_inplace_update.argtypes
+            lib.pe_inplace_metrics.restype = C.c_int
+            lib.pe_inplace_metrics.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.pe_inplace_metric)), abi.u32p,
+                                               C.POINTER(C.POINTER(abi.pe_metric_score)), abi.u32p]
         if hasattr(lib, "pe_system_place_groups"):   # present or absent behind one ABI version
             lib.pe_system_place_groups.restype = C.c_int
             lib.pe_system_place_groups.argtypes = [C.c_void_p, abi.u32p, C.c_uint32, abi.f64p, abi.u8p, abi.u32p,
@@ -556,6 +562,78 @@ class _Stack:
         assert updated.value == sum(1 for r in records if r is not None)
         return records, [int(x) for x in status[:n]]
 
+    def InplaceUpdateMetrics(self, tg, allocs: Sequence[int], fallback: bool = True):
+        """InplaceUpdate / InplaceUpdatePreempt for a caller that keeps
+        AllocMetric (pe_inplace_update_metrics): it runs with EnableMetrics on,
+        on a generic stack, a system stack, or a system stack with preemption
+        enabled. Returns (records, status, metrics): the first two are
+        InplaceUpdatePreempt's, metrics[i] is what LastMetrics() gives after
+        update i's Select in the per-call sequence (at most one key per map,
+        or one ScoreMetaData item). With metrics off the call is
+        InplaceUpdatePreempt and `metrics` is None. A job the call refuses
+        (Unsupported) is answered by inplace_update_metrics_by_select when
+        `fallback` (inplace_update_by_select with metrics off)."""
+        allocs = [int(a) for a in allocs]
+        on = getattr(self, "_metrics_on", False)
+        try:
+            if not hasattr(self._lib, self._p + "inplace_update_metrics"):
+                raise Unsupported(abi.PE_EUNSUPPORTED, "no batched in-place update with AllocMetric behind this ABI")
+            n = len(allocs)
+            a = np.ascontiguousarray(np.asarray(allocs or [0], dtype=np.uint32))
+            out = (abi.pe_ranked_node * max(1, n))()
+            status = np.zeros(max(1, n), dtype=np.uint8)
+            updated = C.c_uint32(0)
+            self._check(self._fn("inplace_update_metrics")(self._h, self._tg_index(tg), a.ctypes.data_as(abi.u32p), n,
+                                                           out, status.ctypes.data_as(abi.u8p), C.byref(updated)))
+        except Unsupported:
+            if not fallback:
+                raise
+            if on:
+                return inplace_update_metrics_by_select(self, tg, allocs)
+            return inplace_update_by_select(self, tg, allocs) + (None,)
+        full = SystemStack.InplaceUpdatePreempted(self)
+        records = [RankedNode.from_c(out[i], self.nodes, full.get(i)) if status[i] == 0 else None for i in range(n)]
+        assert updated.value == sum(1 for r in records if r is not None)
+        return records, [int(x) for x in status[:n]], (self.InplaceMetrics(status[:n]) if on else None)
+
+    def InplaceMetrics(self, status=None) -> List[Dict]:
+        """pe_inplace_metrics of the last InplaceUpdateMetrics: per update a
+        dict in LastMetrics' shape. `status` (that call's, or None: taken from
+        the entries, where an entry without any key reads as exhausted) tells
+        the filtered maps from the exhausted ones. EngineError(PE_ESTATE) when
+        that call ran with metrics off or an InplaceUpdate* call came since."""
+        mp, sp = C.POINTER(abi.pe_inplace_metric)(), C.POINTER(abi.pe_metric_score)()
+        n, ns = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.pe_inplace_metrics(self._h, C.byref(mp), C.byref(n), C.byref(sp), C.byref(ns)))
+        cache = getattr(self, "_mkey_cache", None)
+        if cache is None:
+            cache = self._mkey_cache = {}
+
+        def text(key):
+            if key not in cache:
+                cache[key] = self.MetricString(key)
+            return cache[key]
+
+        out = []
+        for i in range(n.value):
+            e = mp[i]
+            m = {v: {} for v in _KIND_NAMES.values()}
+            m["ScoreMetaData"] = []
+            if e.score != abi.PE_NONE:
+                assert e.score < ns.value
+                m["ScoreMetaData"] = decode_metrics(self, None, 0, 0, sp, e.score, e.score + 1)["ScoreMetaData"]
+            else:
+                if status is not None:
+                    filtered = int(status[i]) == 1
+                else:   # the reason keys of the two kinds never coincide: FilterNode's are checker reasons
+                    filtered = e.reason_key != abi.PE_NONE and not _is_dimension(text(e.reason_key))
+                if e.class_key != abi.PE_NONE:
+                    m["ClassFiltered" if filtered else "ClassExhausted"][text(e.class_key)] = 1
+                if e.reason_key != abi.PE_NONE:
+                    m["ConstraintFiltered" if filtered else "DimensionExhausted"][text(e.reason_key)] = 1
+            out.append(m)
+        return out
+
     def Place(self, tg, count: int) -> List[RankedNode]:
         out = (abi.pe_ranked_node * max(1, count))()
         placed = C.c_uint32(0)
@@ -884,6 +962,39 @@ def inplace_update_by_select(stack, tg, allocs: Sequence[int]):
             records.append(None)
             status.append(1 if r.nodes_filtered else 2)
     return records, status
+
+
+def _is_dimension(reason: str) -> bool:
+    """Whether an AllocMetric reason is one ExhaustedNode records
+    (rank.go:255-497: a network or devices message, or AllocsFit's dimension)."""
+    return reason in ("cpu", "memory", "disk", "cores") or reason.startswith(("network: ", "devices: "))
+
+
+def inplace_update_metrics_by_select(stack, tg, allocs: Sequence[int]):
+    """inplace_update_by_select on a stack with EnableMetrics on (the engine's
+    or the oracle's), with LastMetrics() read after each update's Select,
+    before PopUpdate: what inplaceUpdate keeps as newAlloc.Metrics
+    (util.go:801). Returns (records, status, metrics) in InplaceUpdateMetrics'
+    shape; the node list is left on the last alloc's node."""
+    node_row = stack.state.alloc_table.node_row
+    records, status, metrics = [], [], []
+    for ai in allocs:
+        ai = int(ai)
+        row = int(node_row[ai])
+        stack.StopAllocs([ai])
+        stack.SetNodes(np.asarray([row], dtype=np.uint32))
+        r = stack.SelectRaw(tg)
+        metrics.append(stack.LastMetrics())
+        stack.PopUpdate(ai)
+        if r.row >= 0:
+            stack.StopAllocs([ai])        # the in-place alloc replaces the old one (same ID)
+            stack.Commit(tg, r.row)
+            records.append(r)
+            status.append(0)
+        else:
+            records.append(None)
+            status.append(1 if r.nodes_filtered else 2)
+    return records, status, metrics
 
 
 class GenericStack(_Stack):

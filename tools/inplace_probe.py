@@ -19,7 +19,16 @@ pass takes minutes); its statuses are compared with that prefix of (b)'s.
 Host clock around calls that end in a device synchronise; the kernel time of
 (b) is the engine's HIP events (pe_last_kernel_ms).
 
-    python tools/inplace_probe.py [--reps 5] [--small] [--shapes service,system,preempt] [--out probe.json]
+--metrics: pe_inplace_update_metrics with AllocMetric on, on one
+handle, against the same call with the maps off on a second handle of the same
+build, alternating, at the same shapes: the call and its kernels (HIP events),
+and the difference. Beside them the per-call sequence with the maps on over the
+--per-call-cap prefix on the first handle, which is what a caller that keeps
+AllocMetric runs without the call. Statuses are compared before a time is
+printed.
+
+    python tools/inplace_probe.py [--reps 5] [--small] [--shapes service,system,preempt] [--metrics]
+                                  [--out probe.json]
 """
 import argparse
 import ctypes as C
@@ -134,6 +143,71 @@ def measure(name, shape, reps, cap, entry="pe_inplace_update"):
     return res
 
 
+def measure_metrics(name, make, reps, cap):
+    """The metrics leg: the new call with the maps on (handle `on`) and off
+    (handle `off`), alternating; the per-call sequence with the maps on."""
+    on, nodes, allocs, job, upd = make()
+    off = SystemStack(config=SchedulerConfig(preempt_system=bool(on._cfg.preempt))) \
+        if isinstance(on, SystemStack) else GenericStack()
+    for st in (on, off):
+        st.SetState(nodes, allocs)
+        st._lib.pe_flush.restype = C.c_int
+        st._lib.pe_flush.argtypes = [C.c_void_p]
+    on.EnableMetrics(True)
+    node_row = np.ctypeslib.as_array(on.state.alloc_table.node_row, shape=(len(allocs),)).copy()
+    n = len(upd)
+    na = n
+    if cap and n > cap and len(np.unique(node_row[upd])) == n:
+        na = cap
+    recs = (abi.pe_ranked_node * n)()
+    s_on, s_off = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint8)
+    t = {"a": [], "on": [], "off": [], "k_on": [], "k_off": []}
+    n_scores = 0
+    for rep in range(reps + 1):   # the first repetition warms the paths up
+        for path in ("a", "on", "off"):
+            st = off if path == "off" else on
+            st.ResetPlan()
+            st.SetJob(job)
+            st._check(st._lib.pe_flush(st._h))
+            t0 = time.perf_counter()
+            if path == "a":
+                sa = per_call(st, upd[:na], node_row)
+            else:
+                batched(st, upd, recs, s_on if path == "on" else s_off, "pe_inplace_update_metrics")
+            dt = (time.perf_counter() - t0) * 1e6
+            if rep:
+                t[path].append(dt)
+                if path != "a":
+                    t["k_" + path].append(st.last_kernel_ms() * 1e3)
+            if path == "on":
+                mp, sp = C.POINTER(abi.pe_inplace_metric)(), C.POINTER(abi.pe_metric_score)()
+                nm, ns = C.c_uint32(0), C.c_uint32(0)
+                st._check(st._lib.pe_inplace_metrics(st._h, C.byref(mp), C.byref(nm), C.byref(sp), C.byref(ns)))
+                assert nm.value == n
+                n_scores = ns.value
+        assert np.array_equal(s_on, s_off) and np.array_equal(sa, s_on[:na]), "the paths disagree"
+        assert n_scores == int((s_on == 0).sum())
+        print("# %s (metrics): repetition %d of %d done" % (name, rep, reps), file=sys.stderr, flush=True)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    a = med["a"] * (n / na)
+    res = {"shape": name, "entry": "pe_inplace_update_metrics", "updates": n, "per_call_updates_timed": na,
+           "nodes": len(nodes), "reps": reps, "status_counts": [int((s_on == v).sum()) for v in (0, 1, 2)],
+           "score_items": n_scores,
+           "metrics_on_call_us": med["on"], "metrics_on_call_us_min_max": [min(t["on"]), max(t["on"])],
+           "metrics_off_call_us": med["off"], "metrics_off_call_us_min_max": [min(t["off"]), max(t["off"])],
+           "call_us_difference": med["on"] - med["off"],
+           "metrics_on_kernels_us": med["k_on"], "metrics_on_kernels_us_min_max": [min(t["k_on"]), max(t["k_on"])],
+           "metrics_off_kernels_us": med["k_off"], "metrics_off_kernels_us_min_max": [min(t["k_off"]), max(t["k_off"])],
+           "kernels_us_difference": med["k_on"] - med["k_off"],
+           "metrics_on_us_per_update": med["on"] / n,
+           "per_call_metrics_on_us_per_update": a / n,
+           "per_call_metrics_on_us_min_max": [min(t["a"]) / na, max(t["a"]) / na],
+           "ratio_per_call_over_call": a / med["on"]}
+    on.close()
+    off.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -141,6 +215,8 @@ def main():
     ap.add_argument("--per-call-cap", type=int, default=2000,
                     help="updates path (a) runs per repetition when every node is listed once (0: all)")
     ap.add_argument("--shapes", default="service,system,preempt", help="comma-separated: service, system, preempt")
+    ap.add_argument("--metrics", action="store_true",
+                    help="the AllocMetric leg: pe_inplace_update_metrics, maps on against maps off")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     n_sys = 2000 if args.small else 100000
@@ -153,7 +229,10 @@ def main():
     results = []
     for key in args.shapes.split(","):
         name, make, entry = shapes[key]
-        r = measure(name, make(), args.reps, args.per_call_cap, entry)
+        if args.metrics:
+            r = measure_metrics(name, make, args.reps, args.per_call_cap)
+        else:
+            r = measure(name, make(), args.reps, args.per_call_cap, entry)
         results.append(r)
         print(json.dumps(r), flush=True)
     if args.out:
