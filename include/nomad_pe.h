@@ -508,6 +508,31 @@ int pe_inplace_update_preempted(const pe_stack* s, const uint32_t** updates, con
 int pe_inplace_update_metrics(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n,
                               pe_ranked_node* out, uint8_t* status, uint32_t* updated);
 /* (pe_inplace_metric and pe_inplace_metrics: below, with the AllocMetric types.) */
+/* pe_inplace_update_metrics that does not refuse spread stanzas, at job or
+ * group level: the most general of the in-place calls, the one a caller
+ * should use. SpreadIterator never filters (spread.go:110-174), so the walk
+ * decides the statuses without the spread sets; a second stage then adds the
+ * allocation-spread part and the FinalScore built from it in list order, from
+ * the property counts each update's Select sees in the per-call sequence
+ * (the earlier updates' AppendAlloc and stops included). Arguments, result
+ * layout, status codes, the node-list rule, PE_EINVAL cases,
+ * pe_inplace_update_preempted and pe_inplace_metrics (whose ScoreMetaData
+ * item carries allocation-spread) are pe_inplace_update_metrics'. Records,
+ * statuses and every later observable state equal the per-call sequence's bit
+ * for bit. PE_EUNSUPPORTED (checked before anything changes):
+ * pe_inplace_update_metrics' list without "spreads"; distinct_property, alone
+ * or beside a spread, stays on it. On a job without spreads, and on a system
+ * stack (which drops them, stack.go:207-283), the call is
+ * pe_inplace_update_metrics with no further launch; with spreads it adds a
+ * memset and three short launches on the same stream (none when out == NULL
+ * and metrics are off: the statuses are final) and no further copy back or
+ * synchronisation. */
+int pe_inplace_update_spread(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n,
+                             pe_ranked_node* out, uint8_t* status, uint32_t* updated);
+/* HIP-event times of the last pe_inplace_update* call's launches in ms:
+ * ms2[0] the walk(s), ms2[1] pe_inplace_update_spread's second stage (0 when
+ * it did not run). pe_last_kernel_ms gives their sum. */
+int pe_inplace_spread_ms(const pe_stack* s, double* ms2);
 /* Fused count loop of GenericScheduler.computePlacements (generic_sched.go:493-649)
  * for `count` fresh placements of one task group (no preferred / penalty nodes):
  * Select -> AppendAlloc repeated on the device; stops at the first nil option

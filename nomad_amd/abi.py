@@ -237,6 +237,7 @@ ENGINE_SYMBOLS = [
     "pe_chain_wide_stats",
     "pe_inplace_update_preempt", "pe_inplace_update_preempted",
     "pe_inplace_update_metrics", "pe_inplace_metrics",
+    "pe_inplace_update_spread", "pe_inplace_spread_ms",
 ]
 
 

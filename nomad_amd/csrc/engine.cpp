@@ -962,6 +962,11 @@ struct pe_stack {
     uint32_t inplace_m_n = 0, inplace_m_scores = 0;
     size_t inplace_m_scores_off = 0;
     bool inplace_m_valid = false;
+    // pe_inplace_update_spread: the second stage's inputs (the updates' value
+    // indices per set, their own flags, the start columns), the chunks' prefix
+    // rows, and the walk's records when the caller asked for the maps alone
+    DevMem d_inplace_sp_in, d_inplace_sp_pre, d_inplace_sp_rec;
+    double inplace_stage_ms[2] = {0, 0};   // the walk, the spread stage (pe_inplace_spread_ms)
     SysGroupsState sysg;   // pe_system_place_groups*: buffers, and what the accessors read
     bool stopped(uint32_t ai) const { return ai < stop_count.size() && stop_count[ai] > 0; }
 
@@ -8416,6 +8421,65 @@ static int inplace_metrics_finish(pe_stack* s, TgPlan& g, uint32_t n, const uint
     return PE_OK;
 }
 
+// pe_inplace_update_spread's second stage: what build_psets and
+// cleared_counts read at the call's start, per value of every spread set in
+// the pset_cnt_off layout (ep0: the group's existing and plan allocs; craw0:
+// NodeUpdate's allocs of this job, namespace and group, terminal ones
+// included; prop0: a plan alloc of the group has the value), and per update
+// its node's value index per set and whether its old alloc passes
+// cleared_counts' test. The counts each update's Select sees follow from
+// these and the statuses on the device.
+static int inplace_spread_inputs(pe_stack* s, TgPlan& g, const uint32_t* allocs, uint32_t n,
+                                 pe::InplaceSpreadArgs* SP) {
+    SP->tg = tables_of(g);
+    SP->n = n;
+    SP->n_chunks = (n + pe::kInplaceSpreadChunk - 1) / pe::kInplaceSpreadChunk;
+    const uint32_t cols = SP->tg.pset_cnt_total;
+    const int np = SP->tg.n_spread;
+    // one upload: [val: np x n | own: n | ep0 | craw0 | prop0: cols each]
+    std::vector<uint32_t> in((size_t)np * n + n + 3 * (size_t)cols, 0);
+    uint32_t* val = in.data();
+    uint32_t* own = val + (size_t)np * n;
+    uint32_t* base = own + n;
+    const auto mine = [&](const HostAlloc& a) { return a.job == s->job_id && a.ns == s->job_ns && a.tg == g.name; };
+    for (uint32_t i = 0; i < n; i++) own[i] = mine(s->allocs[allocs[i]]) ? 1 : 0;
+    for (int p = 0; p < np; p++) {
+        const PsetDev& ps = *g.psets[p];
+        const auto node_val = [&](uint32_t row) {
+            return ps.per_node ? ps.h_val_node[row] : ps.h_val_class[s->nodes[row].cls];
+        };
+        uint32_t* ep0 = base + SP->tg.pset_cnt_off[p];
+        uint32_t* craw0 = ep0 + cols;
+        uint32_t* prop0 = craw0 + cols;
+        for (uint32_t ai : s->own_allocs())
+            if (const HostAlloc& a = s->allocs[ai]; a.ns == s->job_ns && a.tg == g.name) {
+                const uint32_t v = node_val(a.row);
+                if (v != pe::kMissing) ep0[v]++;
+            }
+        for (auto& e : plan_of(s))
+            if (e.first == g.name) {
+                const uint32_t v = node_val(e.second);
+                if (v != pe::kMissing) { ep0[v]++; prop0[v] = 1; }
+            }
+        for (auto& kv : s->node_update)
+            for (uint32_t ai : kv.second)
+                if (const HostAlloc& a = s->allocs[ai]; mine(a)) {
+                    const uint32_t v = node_val(a.row);
+                    if (v != pe::kMissing) craw0[v]++;
+                }
+        for (uint32_t i = 0; i < n; i++) val[(size_t)p * n + i] = node_val(s->allocs[allocs[i]].row);
+    }
+    HIP_TRY(s, upload_s(s, s->d_inplace_sp_in, in));
+    if (cols) HIP_TRY(s, s->d_inplace_sp_pre.ensure(sizeof(uint32_t) * 2 * (size_t)cols * SP->n_chunks));
+    SP->val = s->d_inplace_sp_in.as<uint32_t>();
+    SP->own = SP->val + (size_t)np * n;
+    SP->ep0 = SP->own + n;
+    SP->craw0 = SP->ep0 + cols;
+    SP->prop0 = SP->craw0 + cols;
+    SP->pre = s->d_inplace_sp_pre.as<uint32_t>();
+    return PE_OK;
+}
+
 // inplaceUpdate's loop (util.go:692-806) in one launch: per
 // listed alloc the sequence pe_plan_stop, pe_set_nodes([its node]), pe_select,
 // pe_plan_pop_update and, on an option, pe_plan_stop + pe_commit, with the
@@ -8436,10 +8500,12 @@ static int inplace_metrics_finish(pe_stack* s, TgPlan& g, uint32_t n, const uint
 // the same result buffer and come back in the same DMA;
 // inplace_metrics_finish turns them into the updates' maps.
 static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
-                              uint8_t* status, uint32_t* updated, bool pre_call, bool met_call = false) {
+                              uint8_t* status, uint32_t* updated, bool pre_call, bool met_call = false,
+                              bool spr_call = false) {
     if (!s) return PE_EINVAL;
-    const std::string fn = met_call ? "pe_inplace_update_metrics: "
-                                    : (pre_call ? "pe_inplace_update_preempt: " : "pe_inplace_update: ");
+    const std::string fn = spr_call ? "pe_inplace_update_spread: "
+                           : met_call ? "pe_inplace_update_metrics: "
+                                      : (pre_call ? "pe_inplace_update_preempt: " : "pe_inplace_update: ");
     const bool metrics = met_call && s->metrics_on;
     if (updated) *updated = 0;
     if (n && (!allocs || !status)) return s->fail(PE_EINVAL, "null alloc list or status array");
@@ -8475,7 +8541,7 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
         why = "a system stack with preemption (BinPack evicts)";
     else if (g.ask.cores > 0) why = "a reserved-cores ask";
     else if (has_static(g)) why = "static ports";
-    else if (!g.spreads.empty() || !s->job_spreads.empty()) why = "spreads";
+    else if (!spr_call && (!g.spreads.empty() || !s->job_spreads.empty())) why = "spreads";
     else if (!g.distinct_props.empty()) why = "distinct_property";
     else if (tg_md(s, g)) why = "a task network on multi-device nodes";
     for (auto& c : s->job_constraints)
@@ -8535,7 +8601,11 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     invalidate_tables(s);
     rc = prepare_tg(s, tgi, s->visit, 0);
     if (rc) return rc;
-    if (!g.psets.empty() || g.md_on) return s->fail(PE_EUNSUPPORTED, fn + "property sets or multi-device nodes");
+    // the spread sets (spr_call): scored by the second stage, the walk runs without them
+    const bool spread = spr_call && !evicting && g.n_spread > 0 && g.n_spread == (int)g.psets.size();
+    if ((!g.psets.empty() && !spread) || g.md_on)
+        return s->fail(PE_EUNSUPPORTED, fn + "property sets or multi-device nodes");
+    const bool stage2 = spread && (out || metrics);   // the statuses do not depend on the spreads
 
     // group by node row (stable: list order within a group), longest groups
     // first so that the lanes of a wave walk groups of similar length
@@ -8583,6 +8653,12 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
 
     HIP_TRY(s, upload_s(s, s->d_inplace_upd, upd));
     HIP_TRY(s, upload_s(s, s->d_inplace_off, group_off));
+    pe::InplaceSpreadArgs SP;
+    std::memset(&SP, 0, sizeof(SP));
+    if (stage2) {
+        rc = inplace_spread_inputs(s, g, allocs, n, &SP);
+        if (rc) return rc;
+    }
     const size_t st_off = out ? sizeof(pe::EmitRec) * (size_t)n : 0;
     // the eviction walk's part of the results, behind the outcomes so that one
     // DMA brings everything: its four control words (stopped, wider, appended,
@@ -8623,6 +8699,11 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     A.log10 = s->log10;
     A.out = out ? reinterpret_cast<pe::EmitRec*>(dres) : nullptr;
     A.status = dres + st_off;
+    if (spread) A.tg.n_psets = A.tg.n_spread = 0;   // the walk's view: no spread sets
+    if (stage2 && !out) {   // the maps alone: the score parts still pass through records
+        HIP_TRY(s, s->d_inplace_sp_rec.ensure(sizeof(pe::EmitRec) * (size_t)n));
+        A.out = s->d_inplace_sp_rec.as<pe::EmitRec>();
+    }
     pe::InplaceMetricsArgs M;
     M.named = reinterpret_cast<double*>(dres + named_off);
     M.code = reinterpret_cast<uint32_t*>(dres + code_off);
@@ -8662,10 +8743,25 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
         HIP_TRY_STATE(s, pe_launch_inplace(&A, Mp, s->stream));
     }
     HIP_TRY(s, hipEventRecord(s->ev1, s->stream));
+    if (stage2) {
+        SP.status = A.status;
+        SP.rec = A.out;
+        SP.named = metrics ? M.named : nullptr;
+        HIP_TRY_STATE(s, pe_launch_inplace_spread(&SP, s->stream));
+        HIP_TRY(s, hipEventRecord(s->ev2, s->stream));
+    }
     HIP_TRY(s, hipMemcpyAsync(s->h_inplace_out.p, dres, bytes, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(s, hipStreamSynchronize(s->stream));   // the call's one wait
     float ms = 0;
     HIP_TRY(s, hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    s->inplace_stage_ms[0] = ms;
+    s->inplace_stage_ms[1] = 0;
+    if (stage2) {
+        float ms2 = 0;
+        HIP_TRY(s, hipEventElapsedTime(&ms2, s->ev1, s->ev2));
+        s->inplace_stage_ms[1] = ms2;
+        ms += ms2;
+    }
     s->last_ms = ms;
     s->last_ms_pending = false;
 
@@ -10123,6 +10219,19 @@ int pe_inplace_update_metrics(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
                               uint8_t* status, uint32_t* updated) {
     PE_FLUSH_RESET(s);
     return inplace_update_one(s, tgi, allocs, n, out, status, updated, true, true);
+}
+
+int pe_inplace_update_spread(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                             uint8_t* status, uint32_t* updated) {
+    PE_FLUSH_RESET(s);
+    return inplace_update_one(s, tgi, allocs, n, out, status, updated, true, true, true);
+}
+
+int pe_inplace_spread_ms(const pe_stack* s, double* ms2) {
+    if (!s || !ms2) return PE_EINVAL;
+    ms2[0] = s->inplace_stage_ms[0];
+    ms2[1] = s->inplace_stage_ms[1];
+    return PE_OK;
 }
 
 int pe_inplace_metrics(const pe_stack* s, const pe_inplace_metric** m, uint32_t* n, const pe_metric_score** scores,

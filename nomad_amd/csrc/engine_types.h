@@ -565,6 +565,31 @@ struct InplaceMetricsArgs {
     double* named;                    // [n * kInplaceNamed]
 };
 
+// pe_inplace_update_spread: the spread score of every updated
+// alloc, in list order, behind a walk (k_inplace) that ran without the spread
+// sets. The list is cut into chunks of kInplaceSpreadChunk positions; per
+// chunk and value two counts of the status-0 updates before the chunk (`pre`,
+// an exclusive scan of the chunks' own histograms): `ks` all of them, `kc`
+// those whose old alloc NodeUpdate counts for this job, namespace and group
+// (`own`). Columns are in the pset_cnt_off layout of the walk's spread sets.
+constexpr uint32_t kInplaceSpreadChunk = 128;
+struct InplaceSpreadArgs {
+    TgTables tg;                      // the spread sets: n_psets == n_spread (pset_counts is not read)
+    uint32_t n;                       // listed updates
+    uint32_t n_chunks;
+    const uint8_t* status;            // [n] the walk's statuses, by list position
+    const uint32_t* val;              // [n_spread][n] value index of the update's node per set, or kMissing
+    const uint32_t* own;              // [n] the update's `own` flag
+    // the call's start, per value: existing + plan allocs of the group, the
+    // NodeUpdate allocs that count, whether a plan alloc of the group has the value
+    const uint32_t* ep0;              // [pset_cnt_total]
+    const uint32_t* craw0;            // [pset_cnt_total]
+    const uint32_t* prop0;            // [pset_cnt_total]
+    uint32_t* pre;                    // [n_chunks][2][pset_cnt_total]: ks then kc
+    EmitRec* rec;                     // [n] the walk's records (parts before the spread), finished in place
+    double* named;                    // [n * kInplaceNamed] or null: entries 4 and 5 are finished
+};
+
 struct InplaceEvictArgs {
     InplaceArgs I;
     PreemptArgs P;                    // evict_eval's view of the group

@@ -4790,6 +4790,212 @@ __global__ void __launch_bounds__(256) k_inplace_evict(InplaceEvictArgs V, Inpla
     }
 }
 
+// ---- pe_inplace_update_spread ---------------------------------
+// SpreadIterator never filters (spread.go:110-174), so the walk's statuses do
+// not depend on the spread sets: k_inplace runs without them and the kernels
+// below add the allocation-spread part in list order.
+
+// GetCombinedUseMap's count of a value (propertyset.go:160-208, 250-273; what
+// build_psets and cleared_counts give the Select of one update): `ks` / `kc`
+// count the status-0 updates listed before it on the value (all / those whose
+// old alloc NodeUpdate counts), `staged` is the update's own stop.
+__device__ __forceinline__ uint32_t inplace_spread_count(uint32_t ep0, uint32_t craw0, uint32_t prop0, uint32_t ks,
+                                                         uint32_t kc, bool staged) {
+    const uint32_t ep = ep0 + ks;
+    const uint32_t craw = craw0 + kc + (staged ? 1u : 0u);
+    const uint32_t cleared = craw - (((prop0 != 0u || ks > 0u) && craw > 1u) ? 1u : 0u);
+    return ep >= cleared ? ep - cleared : 0u;
+}
+
+// build_spread_table's two boosts of one value (the same operations, so the same bits).
+__device__ __forceinline__ double even_boost_of(uint32_t mn, uint32_t mx, uint32_t present, uint32_t cur) {
+    if (present == 0) return 0.0;
+    double delta_boost;
+    if (mn == 0) delta_boost = -1.0;
+    else delta_boost = (double)(int)(mn - cur) / (double)mn;
+    if (cur != mn) return delta_boost;
+    if (mn == mx) return -1.0;
+    if (mn == 0) return 1.0;
+    return (double)(int)(mx - mn) / (double)mn;
+}
+
+__device__ __forceinline__ double target_boost_of(double desired, uint32_t cnt, double weight_frac) {
+    if (desired != desired) return -1.0;   // no target and no implicit "*"
+    const double used = (double)(cnt + 1u);
+    return ((desired - used) / desired) * weight_frac;
+}
+
+// Every chunk's own (ks, kc) histogram into its zeroed row of `pre`.
+__global__ void __launch_bounds__(kInplaceSpreadChunk) k_inplace_spread_hist(InplaceSpreadArgs A) {
+    const uint32_t c = blockIdx.x, i = c * kInplaceSpreadChunk + threadIdx.x;
+    if (c >= A.n_chunks || i >= A.n || A.status[i] != 0) return;
+    const uint32_t cols = A.tg.pset_cnt_total;
+    uint32_t* ks = A.pre + (size_t)c * 2 * cols;
+    uint32_t* kc = ks + cols;
+    const bool own = A.own[i] != 0;
+    for (int p = 0; p < A.tg.n_spread; p++) {
+        const uint32_t v = A.val[(size_t)p * A.n + i];
+        if (v >= (uint32_t)A.tg.pset_nvals[p]) continue;   // kMissing
+        atomicAdd(&ks[A.tg.pset_cnt_off[p] + v], 1u);
+        if (own) atomicAdd(&kc[A.tg.pset_cnt_off[p] + v], 1u);
+    }
+}
+
+// The histograms' exclusive scan over the chunks, one lane per column.
+__global__ void __launch_bounds__(256) k_inplace_spread_scan(InplaceSpreadArgs A) {
+    const uint32_t cols = 2 * A.tg.pset_cnt_total;
+    for (uint32_t j = blockIdx.x * 256 + threadIdx.x; j < cols; j += gridDim.x * 256) {
+        uint32_t acc = 0;
+        for (uint32_t c = 0; c < A.n_chunks; c++) {
+            uint32_t* w = A.pre + (size_t)c * cols + j;
+            const uint32_t t = *w;
+            *w = acc;
+            acc += t;
+        }
+    }
+}
+
+// One workgroup per chunk; lane i < kInplaceSpreadChunk owns the chunk's i-th
+// update and sums its sets' boosts in set order (lookup_scores' sum). A target
+// set needs the update's own value only: the lane counts the chunk's earlier
+// status-0 updates on it (LDS broadcast reads) on top of the chunk prefix. An
+// even set needs min / max / present over all values as that Select saw them:
+// the workgroup walks the chunk's updates in order on the set's columns (LDS
+// while the set fits kLdsPsetValues values, else the chunk's own row of `pre`
+// in HBM), one block reduction per update. Chunks own disjoint list positions:
+// no atomics. The record is finished as score_into does: the parts summed left
+// to right, then the spread part, then the division.
+__global__ void __launch_bounds__(256) k_inplace_spread(InplaceSpreadArgs A) {
+    constexpr uint32_t K = kInplaceSpreadChunk;
+    __shared__ uint32_t s_val[K], s_flag[K];   // flag bit 0: status 0, bit 1: own
+    __shared__ double s_boost[K];
+    __shared__ uint32_t s_col[5][kLdsPsetValues];
+    __shared__ uint32_t s_red[3][4];
+    const uint32_t tid = threadIdx.x, c = blockIdx.x;
+    if (c >= A.n_chunks) return;
+    const uint32_t base = c * K;
+    const uint32_t m = A.n - base < K ? A.n - base : K;
+    const uint32_t cols = A.tg.pset_cnt_total;
+    uint32_t* pre_ks = A.pre + (size_t)c * 2 * cols;
+    uint32_t* pre_kc = pre_ks + cols;
+    const bool lane = tid < m;
+    const uint32_t i = base + tid;
+    uint32_t flag = 0, ns = 0;
+    double sc[PE_MAX_SCORES];
+    for (int k = 0; k < PE_MAX_SCORES; k++) sc[k] = 0.0;
+    if (lane) {   // the walk's record, loaded beside everything else
+        flag = (A.status[i] == 0 ? 1u : 0u) | (A.own[i] ? 2u : 0u);
+        ns = A.rec[i].n_scores;
+        for (int k = 0; k < PE_MAX_SCORES; k++) sc[k] = A.rec[i].scores[k];
+    }
+    if (tid < K) s_flag[tid] = flag;
+    // the chunk positions before this wave's last lane: a wave-uniform loop bound
+    const uint32_t jend = (tid | 63u) < m ? (tid | 63u) : m;
+    double total = 0.0;
+    for (int p = 0; p < A.tg.n_spread; p++) {
+        const uint32_t off = A.tg.pset_cnt_off[p], nv = (uint32_t)A.tg.pset_nvals[p];
+        uint32_t v = kMissing;
+        if (lane) {
+            v = A.val[(size_t)p * A.n + i];
+            if (v >= nv) v = kMissing;
+        }
+        __syncthreads();   // the set before is read to its end
+        if (tid < K) s_val[tid] = v;
+        double b = -1.0;   // a node without a value
+        if (A.tg.pset_even[p]) {
+            const uint32_t *ep0 = A.ep0 + off, *craw0 = A.craw0 + off, *prop0 = A.prop0 + off;
+            uint32_t *ks = pre_ks + off, *kc = pre_kc + off;
+            if (nv <= (uint32_t)kLdsPsetValues) {
+                for (uint32_t u = tid; u < nv; u += 256) {
+                    s_col[0][u] = ep0[u];
+                    s_col[1][u] = craw0[u];
+                    s_col[2][u] = prop0[u];
+                    s_col[3][u] = ks[u];
+                    s_col[4][u] = kc[u];
+                }
+                ep0 = s_col[0];
+                craw0 = s_col[1];
+                prop0 = s_col[2];
+                ks = s_col[3];
+                kc = s_col[4];
+            }
+            __syncthreads();
+            for (uint32_t j = 0; j < m; j++) {
+                const uint32_t fj = s_flag[j], vj = s_val[j];
+                if (!(fj & 1u) || vj == kMissing) continue;   // (uniform)
+                const bool ownj = (fj & 2u) != 0;
+                uint32_t lmn = 0xFFFFFFFFu, lmx = 0, lpr = 0;
+                for (uint32_t u = tid; u < nv; u += 256) {
+                    const uint32_t x = inplace_spread_count(ep0[u], craw0[u], prop0[u], ks[u], kc[u], ownj && u == vj);
+                    if (x == 0) continue;
+                    lpr++;
+                    lmn = x < lmn ? x : lmn;
+                    lmx = x > lmx ? x : lmx;
+                }
+                for (int o = 32; o > 0; o >>= 1) {
+                    lmn = min(lmn, (uint32_t)__shfl_xor((int)lmn, o));
+                    lmx = max(lmx, (uint32_t)__shfl_xor((int)lmx, o));
+                    lpr += (uint32_t)__shfl_xor((int)lpr, o);
+                }
+                if ((tid & 63u) == 0) {
+                    s_red[0][tid >> 6] = lmn;
+                    s_red[1][tid >> 6] = lmx;
+                    s_red[2][tid >> 6] = lpr;
+                }
+                __syncthreads();
+                if (tid == 0) {
+                    uint32_t mn = 0xFFFFFFFFu, mx = 0, present = 0;
+                    for (int w = 0; w < 4; w++) {
+                        mn = min(mn, s_red[0][w]);
+                        mx = max(mx, s_red[1][w]);
+                        present += s_red[2][w];
+                    }
+                    if (present == 0) mn = 0;   // no used value: min = max = 0
+                    const uint32_t cur = inplace_spread_count(ep0[vj], craw0[vj], prop0[vj], ks[vj], kc[vj], ownj);
+                    s_boost[j] = even_boost_of(mn, mx, present, cur);
+                    ks[vj] += 1u;   // the update's AppendAlloc, and its stop that stays
+                    if (ownj) kc[vj] += 1u;
+                }
+                __syncthreads();
+            }
+            if ((flag & 1u) && v != kMissing) b = s_boost[tid];
+        } else {
+            __syncthreads();
+            uint32_t ksl = 0, kcl = 0;
+#pragma unroll 8
+            for (uint32_t j = 0; j < jend; j++) {
+                const uint32_t fj = s_flag[j];
+                const bool hit = j < tid && (fj & 1u) && s_val[j] == v;
+                ksl += hit ? 1u : 0u;
+                kcl += hit ? (fj >> 1) & 1u : 0u;
+            }
+            if ((flag & 1u) && v != kMissing) {
+                const uint32_t cnt = inplace_spread_count(A.ep0[off + v], A.craw0[off + v], A.prop0[off + v],
+                                                          pre_ks[off + v] + ksl, pre_kc[off + v] + kcl, (flag & 2u) != 0);
+                b = target_boost_of(A.tg.pset_desired[p][v], cnt, A.tg.pset_weight_frac[p]);
+            }
+        }
+        total += b;
+    }
+    if (!(flag & 1u) || total == 0.0) return;   // without a spread part the walk's record is final
+    EmitRec& o = A.rec[i];
+    if (ns == 0 || ns >= (uint32_t)PE_MAX_SCORES) return;
+    double sum = sc[0];
+#pragma unroll
+    for (uint32_t k = 1; k < (uint32_t)PE_MAX_SCORES; k++)
+        if (k < ns) sum += sc[k];
+    sum += total;   // SpreadIterator (spread.go:110-174)
+    o.scores[ns] = total;
+    ns++;
+    const double fs = sum / (double)ns;   // ScoreNormalizationIterator (rank.go:762-767)
+    o.n_scores = ns;
+    o.final_score = fs;
+    if (A.named) {
+        A.named[(size_t)i * kInplaceNamed + 4] = total;
+        A.named[(size_t)i * kInplaceNamed + 5] = fs;
+    }
+}
+
 // One plain (node, group) step on a lane's register image: the pipeline every
 // other path runs (the same status_loaded / score_into, so the same bits). With
 // kNamed (the AllocMetric forms) an option's ScoreNode values
@@ -5398,6 +5604,26 @@ hipError_t pe_launch_inplace_stop(const pe::InplaceArgs* a, const pe::InplaceSto
     else
         hipLaunchKernelGGL((pe::k_inplace<true, false>), dim3(blocks), dim3(256), 0, st, *a, *s,
                            pe::InplaceMetricsArgs{nullptr, nullptr});
+    return hipGetLastError();
+}
+
+// pe_inplace_update_spread's second stage behind pe_launch_inplace on the same
+// stream: the chunks' histograms, their scan, then the spread parts.
+hipError_t pe_launch_inplace_spread(const pe::InplaceSpreadArgs* a, hipStream_t st) {
+    if (!a->n || a->tg.n_spread <= 0) return hipSuccess;
+    const uint32_t cols = a->tg.pset_cnt_total;
+    if (a->tg.n_psets != a->tg.n_spread || a->n_chunks != (a->n + pe::kInplaceSpreadChunk - 1) / pe::kInplaceSpreadChunk ||
+        !a->status || !a->val || !a->own || !a->rec || (cols && (!a->ep0 || !a->craw0 || !a->prop0 || !a->pre)))
+        return hipErrorInvalidValue;
+    if (cols) {
+        const hipError_t e = hipMemsetAsync(a->pre, 0, sizeof(uint32_t) * 2 * (size_t)cols * a->n_chunks, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(pe::k_inplace_spread_hist, dim3(a->n_chunks), dim3(pe::kInplaceSpreadChunk), 0, st, *a);
+        uint32_t blocks = (2 * cols + 255) / 256;
+        if (blocks > 1024) blocks = 1024;   // grid-stride beyond
+        hipLaunchKernelGGL(pe::k_inplace_spread_scan, dim3(blocks), dim3(256), 0, st, *a);
+    }
+    hipLaunchKernelGGL(pe::k_inplace_spread, dim3(a->n_chunks), dim3(256), 0, st, *a);
     return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@ hipError_t pe_launch_system(const pe::SystemArgs* a, hipStream_t st);
 hipError_t pe_launch_inplace(const pe::InplaceArgs* a, const pe::InplaceMetricsArgs* m_or_null, hipStream_t st);
 hipError_t pe_launch_inplace_stop(const pe::InplaceArgs* a, const pe::InplaceStopArgs* s,
                                   const pe::InplaceMetricsArgs* m_or_null, hipStream_t st);
+hipError_t pe_launch_inplace_spread(const pe::InplaceSpreadArgs* a, hipStream_t st);
 hipError_t pe_launch_inplace_evict(const pe::InplaceEvictArgs* a, const pe::InplaceMetricsArgs* m_or_null,
                                    uint32_t words, uint32_t max_groups, hipStream_t st);
 hipError_t pe_launch_system_groups(const pe::SystemGroupsArgs* a, const pe::SysStopArgs* s_or_null,

@@ -84,6 +84,11 @@ def load_engine():
             lib.pe_inplace_metrics.restype = C.c_int
             lib.pe_inplace_metrics.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.pe_inplace_metric)), abi.u32p,
                                                C.POINTER(C.POINTER(abi.pe_metric_score)), abi.u32p]
+        if hasattr(lib, "pe_inplace_update_spread"):
+            lib.pe_inplace_update_spread.restype = C.c_int
+            lib.pe_inplace_update_spread.argtypes = lib.pe_inplace_update.argtypes
+            lib.pe_inplace_spread_ms.restype = C.c_int
+            lib.pe_inplace_spread_ms.argtypes = [C.c_void_p, abi.f64p]
         if hasattr(lib, "pe_system_place_groups"):   # present or absent behind one ABI version
             lib.pe_system_place_groups.restype = C.c_int
             lib.pe_system_place_groups.argtypes = [C.c_void_p, abi.u32p, C.c_uint32, abi.f64p, abi.u8p, abi.u32p,
@@ -595,6 +600,47 @@ class _Stack:
         records = [RankedNode.from_c(out[i], self.nodes, full.get(i)) if status[i] == 0 else None for i in range(n)]
         assert updated.value == sum(1 for r in records if r is not None)
         return records, [int(x) for x in status[:n]], (self.InplaceMetrics(status[:n]) if on else None)
+
+    def InplaceUpdateSpread(self, tg, allocs: Sequence[int], fallback: bool = True):
+        """InplaceUpdateMetrics for a job that may carry spread stanzas, at job
+        or group level (pe_inplace_update_spread): the most general in-place
+        call. Returns (records, status, metrics) in InplaceUpdateMetrics'
+        shape; the records' scores and the maps' ScoreMetaData carry the
+        allocation-spread part as each update's Select computes it in the
+        per-call sequence. On a job without spreads the call is
+        InplaceUpdateMetrics. A job the call refuses (Unsupported:
+        distinct_property, reserved cores, static ports, ...) is answered by
+        inplace_update_metrics_by_select when `fallback`
+        (inplace_update_by_select with metrics off)."""
+        allocs = [int(a) for a in allocs]
+        on = getattr(self, "_metrics_on", False)
+        try:
+            if not hasattr(self._lib, self._p + "inplace_update_spread"):
+                raise Unsupported(abi.PE_EUNSUPPORTED, "no batched in-place update with spreads behind this ABI")
+            n = len(allocs)
+            a = np.ascontiguousarray(np.asarray(allocs or [0], dtype=np.uint32))
+            out = (abi.pe_ranked_node * max(1, n))()
+            status = np.zeros(max(1, n), dtype=np.uint8)
+            updated = C.c_uint32(0)
+            self._check(self._fn("inplace_update_spread")(self._h, self._tg_index(tg), a.ctypes.data_as(abi.u32p), n,
+                                                          out, status.ctypes.data_as(abi.u8p), C.byref(updated)))
+        except Unsupported:
+            if not fallback:
+                raise
+            if on:
+                return inplace_update_metrics_by_select(self, tg, allocs)
+            return inplace_update_by_select(self, tg, allocs) + (None,)
+        full = SystemStack.InplaceUpdatePreempted(self)
+        records = [RankedNode.from_c(out[i], self.nodes, full.get(i)) if status[i] == 0 else None for i in range(n)]
+        assert updated.value == sum(1 for r in records if r is not None)
+        return records, [int(x) for x in status[:n]], (self.InplaceMetrics(status[:n]) if on else None)
+
+    def inplace_stage_ms(self):
+        """HIP-event times (ms) of the last InplaceUpdate* call: (the walk, the
+        spread stage; 0.0 when it did not run)."""
+        buf = (C.c_double * 2)()
+        self._check(self._lib.pe_inplace_spread_ms(self._h, C.cast(buf, abi.f64p)))
+        return buf[0], buf[1]
 
     def InplaceMetrics(self, status=None) -> List[Dict]:
         """pe_inplace_metrics of the last InplaceUpdateMetrics: per update a

@@ -27,10 +27,18 @@ and the difference. Beside them the per-call sequence with the maps on over the
 AllocMetric runs without the call. Statuses are compared before a time is
 printed.
 
-    python tools/inplace_probe.py [--reps 5] [--small] [--shapes service,system,preempt] [--metrics]
+--spread: the service shape with a target spread on
+${node.class}, three paths alternating on one handle: the per-call sequence
+(the only answer the other in-place calls leave such a job),
+pe_inplace_update_spread with records, and pe_inplace_update on the same job
+without the spread, which shows what the second stage costs; beside them the
+HIP-event times of the walk and of the second stage (pe_inplace_spread_ms).
+
+    python tools/inplace_probe.py [--reps 5] [--small] [--shapes service,system,preempt] [--metrics | --spread]
                                   [--out probe.json]
 """
 import argparse
+import copy
 import ctypes as C
 import json
 import sys
@@ -41,7 +49,7 @@ import numpy as np
 sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
 from nomad_amd import abi, synth  # noqa: E402
 from nomad_amd.stack import GenericStack, SystemStack  # noqa: E402
-from nomad_amd.structs import Allocation, SchedulerConfig  # noqa: E402
+from nomad_amd.structs import Allocation, SchedulerConfig, Spread, SpreadTarget  # noqa: E402
 
 
 def service_shape(n_nodes, n_upd):
@@ -208,6 +216,66 @@ def measure_metrics(name, make, reps, cap):
     return res
 
 
+def measure_spread(n_nodes, n_upd, reps):
+    """The spread leg: the service shape with a target spread on
+    ${node.class}, three paths alternating on one handle: (a) the per-call
+    sequence, (b) pe_inplace_update_spread with records, (c) pe_inplace_update
+    on the same job without the spread. Statuses do not depend on the spread:
+    all three must agree on every repetition."""
+    st, nodes, allocs, job, upd = service_shape(n_nodes, n_upd)
+    plain = copy.deepcopy(job)
+    job.task_groups[0].spreads = [Spread("${node.class}", 60, [SpreadTarget("class-1", 40), SpreadTarget("class-2", 30)])]
+    st.SetState(nodes, allocs)
+    st._lib.pe_flush.restype = C.c_int
+    st._lib.pe_flush.argtypes = [C.c_void_p]
+    node_row = np.ctypeslib.as_array(st.state.alloc_table.node_row, shape=(len(allocs),)).copy()
+    n = len(upd)
+    recs = (abi.pe_ranked_node * n)()
+    s = {"b": np.empty(n, dtype=np.uint8), "c": np.empty(n, dtype=np.uint8)}
+    t = {"a": [], "b": [], "c": [], "stage1": [], "stage2": [], "k_c": []}
+    with_part = 0
+    for rep in range(reps + 1):   # the first repetition warms the paths up
+        for path in ("a", "b", "c"):
+            st.ResetPlan()
+            st.SetJob(plain if path == "c" else job)
+            st._check(st._lib.pe_flush(st._h))
+            t0 = time.perf_counter()
+            if path == "a":
+                sa = per_call(st, upd, node_row)
+            else:
+                batched(st, upd, recs, s[path], "pe_inplace_update_spread" if path == "b" else "pe_inplace_update")
+            dt = (time.perf_counter() - t0) * 1e6
+            if path == "b":
+                with_part = sum(1 for i in range(n) if s["b"][i] == 0 and recs[i].n_scores >= 2)
+            if rep:
+                t[path].append(dt)
+                if path == "b":
+                    ms = st.inplace_stage_ms()
+                    t["stage1"].append(ms[0] * 1e3)
+                    t["stage2"].append(ms[1] * 1e3)
+                elif path == "c":
+                    t["k_c"].append(st.last_kernel_ms() * 1e3)
+        assert np.array_equal(sa, s["b"]) and np.array_equal(s["b"], s["c"]), "the paths disagree"
+        print("# spread: repetition %d of %d done" % (rep, reps), file=sys.stderr, flush=True)
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    res = {"shape": "service with a target spread: %d updates" % n, "entry": "pe_inplace_update_spread", "updates": n,
+           "nodes": len(nodes), "reps": reps, "status_counts": [int((s["b"] == v).sum()) for v in (0, 1, 2)],
+           "records_with_a_spread_part": with_part}
+    for k, label in (("a", "per_call"), ("b", "spread_call"), ("c", "plain_call_without_spread")):
+        res[label + "_us"] = med[k]
+        res[label + "_us_min_max"] = [min(t[k]), max(t[k])]
+        res[label + "_us_per_update"] = med[k] / n
+    res["ratio_per_call_over_spread_call"] = med["a"] / med["b"]
+    res["spread_call_minus_plain_call_us"] = med["b"] - med["c"]
+    res["stage1_us"] = med["stage1"]
+    res["stage1_us_min_max"] = [min(t["stage1"]), max(t["stage1"])]
+    res["stage2_us"] = med["stage2"]
+    res["stage2_us_min_max"] = [min(t["stage2"]), max(t["stage2"])]
+    res["plain_call_kernel_us"] = med["k_c"]
+    st.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -217,6 +285,8 @@ def main():
     ap.add_argument("--shapes", default="service,system,preempt", help="comma-separated: service, system, preempt")
     ap.add_argument("--metrics", action="store_true",
                     help="the AllocMetric leg: pe_inplace_update_metrics, maps on against maps off")
+    ap.add_argument("--spread", action="store_true",
+                    help="the spread leg: pe_inplace_update_spread on the service shape with a target spread")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     n_sys = 2000 if args.small else 100000
@@ -227,7 +297,11 @@ def main():
               "preempt": ("system, preemption enabled: one alloc per node", lambda: system_shape(n_sys, True),
                           "pe_inplace_update_preempt")}
     results = []
-    for key in args.shapes.split(","):
+    if args.spread:
+        r = measure_spread(500 if args.small else 10000, 50 if args.small else 1000, args.reps)
+        results.append(r)
+        print(json.dumps(r), flush=True)
+    for key in ([] if args.spread else args.shapes.split(",")):
         name, make, entry = shapes[key]
         if args.metrics:
             r = measure_metrics(name, make, args.reps, args.per_call_cap)
