@@ -403,6 +403,14 @@ int pe_speculation_stats(const pe_stack* s, uint64_t* out4);
 /* Counters of the chain's wide phase launches (PE_CHAIN_WIDE): out[0] phases
  * they resolved, [1] phases they declined (left to k_chain). */
 int pe_chain_wide_stats(const pe_stack* s, uint64_t* out2);
+/* Chain launches with wide phases, by kind: out[0] with two k_phase launches,
+ * [1] with both phases in one k_phases launch (PE_CHAIN_WIDE_ONE=0: never). */
+int pe_chain_wide_launches(const pe_stack* s, uint64_t* out2);
+/* The one-launch gate for a list of n_visit positions, a launch of `count`
+ * Selects and a limit: out[0] the dynamic LDS bytes the launch needs, [1] what
+ * a workgroup of the current device may hold. Returns 1 if k_phases takes the
+ * launch, 0 if the two k_phase launches do, a negative PE_E* on an error. */
+int pe_chain_wide_one_lds(uint32_t n_visit, uint32_t count, uint32_t limit, uint64_t* out2);
 /* Plan.AppendAlloc plus Plan.AppendPreemptedAlloc of each preempted alloc
  * (handlePreemptions, generic_sched.go:794-816): `preempted` are alloc-table
  * rows, as returned in pe_ranked_node.preempted by a Select with Preempt. */

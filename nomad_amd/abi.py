@@ -234,7 +234,7 @@ ENGINE_SYMBOLS = [
     "pe_system_place_groups", "pe_system_groups_results",
     "pe_system_place_groups_preempt", "pe_system_groups_preempted",
     "pe_system_place_groups_metrics", "pe_system_groups_metrics",
-    "pe_chain_wide_stats",
+    "pe_chain_wide_stats", "pe_chain_wide_launches", "pe_chain_wide_one_lds",
     "pe_inplace_update_preempt", "pe_inplace_update_preempted",
     "pe_inplace_update_metrics", "pe_inplace_metrics",
     "pe_inplace_update_spread", "pe_inplace_spread_ms",

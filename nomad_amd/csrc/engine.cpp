@@ -489,6 +489,7 @@ struct Tunables {
     bool counts_defer_ok = true;       // PE_COUNTS_DEFER=0: SetJob launches its counts at once
     bool kernel_split = false;         // PE_KERNEL_SPLIT=1 (or pe_set_kernel_split): per-kernel chain events
     bool chain_wide = true;            // PE_CHAIN_WIDE=0: no wide phase launches before k_chain
+    bool chain_wide_one = true;        // PE_CHAIN_WIDE_ONE=0: two k_phase launches, never one k_phases launch
     // profiling, printed to stderr
     bool api_prof = false;             // PE_API_PROF=1
     bool place_prof = false;           // PE_PLACE_PROF set
@@ -518,6 +519,7 @@ static Tunables read_tunables() {
     flag("PE_COUNTS_DEFER", &t.counts_defer_ok);
     flag("PE_KERNEL_SPLIT", &t.kernel_split);
     flag("PE_CHAIN_WIDE", &t.chain_wide);
+    flag("PE_CHAIN_WIDE_ONE", &t.chain_wide_one);
     flag("PE_API_PROF", &t.api_prof);
     t.place_prof = is_set("PE_PLACE_PROF");
     t.chain_prof = is_set("PE_CHAIN_PROF");
@@ -928,6 +930,7 @@ struct pe_stack {
     std::vector<uint32_t> sys_log;     // its log
     uint32_t sys_taken = 0;            // log entries taken over
     uint64_t spec_stats[4] = {0, 0, 0, 0};   // runs, Selects served, rollbacks, records computed
+    uint64_t wide_launches[2] = {0, 0};      // armed chain launches: with the k_phase pair, with one k_phases
     DevMem ck_rec, ck_coll_job, ck_coll_tg, ck_dev_free, ck_pset[pe::kMaxPsets];
     DevMem d_commit_rows, d_commit_offers;
 
@@ -4829,6 +4832,7 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
         A.count = c;
         A.offset0 = *new_offset;
         A.wide.phases = (uint64_t)c * A.limit > (uint64_t)n ? 2u : 1u;
+        const bool wide_one = A.wide.bits && s->tun.chain_wide_one && pe_chain_one_fits((uint32_t)n, c, A.limit);
         const double t0 = hprof ? now_us() : 0.0;
         if (spin) {
             A.done_seq = ++s->place_seq;
@@ -4845,12 +4849,13 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
                     split = s->ev_split;
                 }
                 HIP_TRY_STATE(s, hipSuccess);   // whatever is still pending launches first
-                const hipError_t le = pe_launch_chain(&A, 1, 1, s->tun.chain_items, s->stream, split);
+                const hipError_t le = pe_launch_chain(&A, 1, 1, s->tun.chain_items, s->stream, split, wide_one);
                 if (le != hipSuccess && done == 0) {
                     if (fold_taken) { s->pending_fold = fold_saved; s->fold_pending = true; }
                     if (counts_taken) { s->pending_counts = counts_saved; s->counts_pending = true; }
                 }
                 HIP_TRY(s, le);
+                if (A.wide.bits) s->wide_launches[wide_one ? 1 : 0]++;
                 s->split_valid = split != nullptr;
                 s->split_rounds = 0;
             } else {
@@ -9074,6 +9079,21 @@ int pe_chain_wide_stats(const pe_stack* cs, uint64_t* out2) {
     out2[0] = v[0];
     out2[1] = v[1];
     return PE_OK;
+}
+
+int pe_chain_wide_launches(const pe_stack* cs, uint64_t* out2) {
+    if (!cs || !out2) return PE_EINVAL;
+    view_take(const_cast<pe_stack*>(cs));
+    out2[0] = cs->wide_launches[0];
+    out2[1] = cs->wide_launches[1];
+    return PE_OK;
+}
+
+int pe_chain_wide_one_lds(uint32_t n_visit, uint32_t count, uint32_t limit, uint64_t* out2) {
+    if (!out2) return PE_EINVAL;
+    out2[0] = pe_chain_one_lds_bytes(n_visit, count, limit);
+    out2[1] = pe_chain_one_max_dyn();
+    return pe_chain_one_fits(n_visit, count, limit) ? 1 : 0;
 }
 
 int pe_stage_orders(pe_stack* s, const uint32_t* orders, uint32_t n_evals, uint32_t n) {

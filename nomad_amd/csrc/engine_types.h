@@ -210,6 +210,7 @@ struct ChainWide {
     // base1) x predicate (option, filtered, non-positive option)
     uint32_t* bits;
     uint32_t* won;                // 2 x words: positions whose row won in phase 0 / in phase 1
+                                  // (k_phase's; k_phases keeps phase 0's in LDS and stores neither)
     uint32_t* slot;               // [n_visit]: the emit_ov slot of a phase 0 winner's position
     ChainSeed* seed;              // [2]
     uint32_t* err;                // a bounds guard of k_phase tripped

@@ -3083,6 +3083,233 @@ __global__ void __launch_bounds__(kWideBlock) k_phase(BatchArgs A, uint32_t phas
     }
 }
 
+// ---- both wide phases in one launch, options compacted by rank -------------------
+//
+// k_phases is k_phase(0) and k_phase(1) in one workgroup: phase 1 follows phase
+// 0 behind the workgroup's own barrier, so there is one dispatch, one prologue
+// per phase and no launch-to-launch state but the last seed. Instead of a rank
+// select per Select (a binary search over the word prefixes and a walk over set
+// bits), one pass over the visit positions writes the inverse map once: an
+// option's absolute rank is prefix[word] + popc(bits below), its rank relative
+// to the cursor k = rank - c_opt (wrapped by the options' total), and the
+// option of relative rank k belongs to Select k / L. So position and value (a
+// coalesced load of base / base1) go to LDS entry k, and Select s reads the L
+// consecutive entries [s L, (s + 1) L). Everything stored (ChainEmit, emit_ov,
+// slot, seed, stats, err) is what the k_phase pair stores, except `won`, which
+// only phase 1 reads and which therefore stays in LDS.
+// LDS: the static words below plus pe_chain_one_lds_bytes() of entries; a
+// launch that needs more than a workgroup may hold keeps the k_phase pair.
+constexpr int kOneBlock = 1024;
+static_assert(kWideMaxWords <= (uint32_t)kOneBlock, "k_phases: one bitmap word per lane");
+static_assert(kChainMaxN <= (1u << 16), "k_phases: positions in 16 bits, word prefixes of two bitmaps in one word");
+
+// compact entries of a launch: one per option the two phases can return
+__host__ __device__ inline uint32_t one_entries(uint32_t n_visit, uint32_t count, uint32_t limit) {
+    const unsigned long long cl = (unsigned long long)count * limit;
+    return cl < n_visit ? (uint32_t)cl : n_visit;
+}
+// the values (8 B each), then the positions (2 B each)
+__host__ __device__ inline size_t one_lds_bytes(uint32_t entries) {
+    return (size_t)entries * sizeof(double) + (((size_t)entries * sizeof(uint16_t) + 15u) & ~(size_t)15u);
+}
+
+__global__ void __launch_bounds__(kOneBlock) k_phases(BatchArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char one_smem[];
+    __shared__ uint32_t s_opt[kWideMaxWords], s_fil[kWideMaxWords], s_won[kWideMaxWords];
+    __shared__ uint32_t s_pre[kWideMaxWords + 1];   // exclusive word prefixes: options | filtered << 16
+    __shared__ uint32_t s_wave[kOneBlock / 64], s_neg;
+    const ChainWide& Wd = A.wide;
+    const uint32_t tid = threadIdx.x, n = A.n_visit, L = A.limit, nw = Wd.words;
+    const bool args_ok = n != 0 && nw == (n + 31u) / 32u && nw <= kWideMaxWords && L != 0 && L <= kMaxChainLimit;
+    const uint32_t cap = one_entries(n, A.count, L);
+    double* e_val = reinterpret_cast<double*>(one_smem);
+    uint16_t* e_pos = reinterpret_cast<uint16_t*>(e_val + cap);
+    // one round of loads: the lane's word of all six bitmaps, for both phases
+    uint32_t t_o[2] = {0u, 0u}, t_f[2] = {0u, 0u}, t_n[2] = {0u, 0u};
+    if (args_ok && tid < nw) {
+        const uint32_t* b = Wd.bits + tid;
+#pragma unroll
+        for (uint32_t t = 0; t < 2; t++) {
+            t_o[t] = b[t * nw];
+            t_f[t] = b[(2 + t) * nw];
+            t_n[t] = b[(4 + t) * nw];
+        }
+    }
+    if (tid < kWideMaxWords) s_won[tid] = 0u;
+    ChainSeed in;
+    in.status = kSeedOk;
+    in.placed = 0;
+    in.cur = wrap_pos(A.offset0, n ? n : 1u);
+    in.pos_used = 0;
+    const uint32_t phases = Wd.phases < 2u ? Wd.phases : 2u;   // a row holds at most one placement per phase
+    // (every test that leaves or declines a phase is uniform over the workgroup)
+    for (uint32_t phase = 0; phase < phases; phase++) {
+        if (in.status != kSeedOk || in.placed >= A.count) {
+            if (tid == 0) Wd.seed[phase] = in;
+            continue;
+        }
+        const uint32_t cur = in.cur;
+        bool ok = args_ok && cur < n;
+        uint32_t tot_o = 0, tot_f = 0, ns = 0;
+        if (ok) {
+            if (tid == 0) s_neg = 0u;
+            __syncthreads();   // phase 0's winners are in s_won; its readers of the entries are done
+            // the phase's bitmaps: table 1 where the row won in phase 0
+            uint32_t o = 0, f = 0, neg = 0;
+            if (tid < nw) {
+                const uint32_t w = phase ? s_won[tid] : 0u;
+                o = (t_o[0] & ~w) | (t_o[1] & w);
+                f = (t_f[0] & ~w) | (t_f[1] & w);
+                neg = (t_n[0] & ~w) | (t_n[1] & w);
+                if (tid == nw - 1u && (n & 31u) && ((o | f) >> (n & 31u))) {   // bits past the list's end
+                    wide_fail(Wd);
+                    o &= (1u << (n & 31u)) - 1u;
+                    f &= (1u << (n & 31u)) - 1u;
+                }
+                s_opt[tid] = o;
+                s_fil[tid] = f;
+                if (neg) atomicOr(&s_neg, 1u);
+            }
+            // word prefixes of both bitmaps: a scan per wave, then the waves' totals
+            const uint32_t pk = (uint32_t)__popc(o) | ((uint32_t)__popc(f) << 16);
+            uint32_t inc = pk;
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t x = (uint32_t)__shfl_up((int)inc, off);
+                if ((int)(tid & 63u) >= off) inc += x;
+            }
+            if ((tid & 63u) == 63u) s_wave[tid >> 6] = inc;
+            __syncthreads();
+            uint32_t before = 0;
+            for (uint32_t v = 0; v < (tid >> 6); v++) before += s_wave[v];
+            if (tid < nw) s_pre[tid] = before + inc - pk;
+            if (tid == nw - 1u) s_pre[nw] = before + inc;
+            __syncthreads();
+            tot_o = s_pre[nw] & 0xFFFFu;
+            tot_f = s_pre[nw] >> 16;
+            ns = min(A.count - in.placed, tot_o / L);
+            // non-positive options (the Selects set them aside), or no whole Select
+            // in the window (k_chain's Retry / Stall / Exhausted modes): k_chain's
+            if (s_neg != 0u || ns == 0) ok = false;
+        }
+        if (!ok) {
+            if (tid == 0) {
+                in.status = kSeedDeclined;
+                Wd.seed[phase] = in;
+                Wd.stats[1] += 1ull;
+            }
+            in.status = kSeedDeclined;
+            continue;
+        }
+        // set bits at absolute positions [0, p), p in [0, n]: options | filtered << 16
+        auto prefix = [&](uint32_t p) {
+            const uint32_t w = p >> 5;
+            if (w >= nw) return s_pre[nw];
+            const uint32_t below = (1u << (p & 31u)) - 1u;
+            return s_pre[w] + ((uint32_t)__popc(s_opt[w] & below) | ((uint32_t)__popc(s_fil[w] & below) << 16));
+        };
+        const uint32_t c_pk = prefix(cur), c_opt = c_pk & 0xFFFFu, c_fil = c_pk >> 16;
+        // filtered positions among the relative positions [0, x), x in [0, n]
+        auto fil_before = [&](uint32_t x) {
+            const uint32_t a = cur + x;
+            if (a <= n) return (prefix(a) >> 16) - c_fil;
+            return tot_f - c_fil + (prefix(a - n) >> 16);
+        };
+        auto rel_of = [&](uint32_t p) { return p >= cur ? p - cur : p + n - cur; };
+        // ns <= count - placed and ns L <= tot_o <= n: the entries fit (guarded all the same)
+        uint32_t need = ns * L;
+        if (need > cap) {
+            if (tid == 0) wide_fail(Wd);
+            need = cap;
+            ns = need / L;
+        }
+        // compaction: every option of relative rank below ns L into its entry
+#pragma unroll 4
+        for (uint32_t p = tid; p < n; p += kOneBlock) {
+            const uint32_t w = p >> 5, bit = p & 31u, word = s_opt[w];
+            if (!((word >> bit) & 1u)) continue;
+            const uint32_t r = (s_pre[w] & 0xFFFFu) + (uint32_t)__popc(word & ((1u << bit) - 1u));
+            const uint32_t k = r >= c_opt ? r - c_opt : r + tot_o - c_opt;
+            if (k >= need) continue;
+            const bool had = phase && ((s_won[w] >> bit) & 1u);
+            e_val[k] = (had ? A.base1 : A.base)[p];
+            e_pos[k] = (uint16_t)p;
+        }
+        __syncthreads();
+        for (uint32_t s = tid; s < ns; s += kOneBlock) {
+            // first strict maximum in visit order (chain_walk's rule without set-aside options)
+            const uint32_t e0 = s * L;
+            double best = e_val[e0];
+            uint32_t bk = 0;
+            for (uint32_t k = 1; k < L; k++) {
+                const double v = e_val[e0 + k];
+                if (v > best) { best = v; bk = k; }
+            }
+            const uint32_t bp = e_pos[e0 + bk], stop = e_pos[e0 + L - 1u];
+            // the previous Select's stop (its last option), for the span's start
+            const uint32_t start = s ? rel_of(e_pos[e0 - 1u]) + 1u : 0u;
+            const uint32_t it = in.placed + s;
+            if (bp >= n || stop >= n || it >= A.count) {
+                wide_fail(Wd);
+                continue;
+            }
+            const uint32_t stop_rel = rel_of(stop);
+            const uint32_t consumed = stop_rel + 1u - start;
+            const uint32_t nf = fil_before(stop_rel + 1u) - fil_before(start);
+            if (stop_rel >= n || stop_rel < start || consumed < L + nf) {
+                wide_fail(Wd);
+                continue;
+            }
+            // the winner's row and (on a phase 0 winner) its writeback slot, one round of loads
+            const uint32_t dk = phase ? (s_won[bp >> 5] >> (bp & 31u)) & 1u : 0u;
+            const uint32_t row = A.perms[bp];
+            const uint32_t sl = dk ? Wd.slot[bp] : ~0u;   // stored in phase 0, before the workgroup's barrier
+            if (dk && sl >= A.count) {
+                wide_fail(Wd);
+                continue;
+            }
+            ChainEmit& m = A.emit[it];
+            m.row = (int32_t)row;
+            m.dk = dk;
+            m.consumed = consumed;
+            m.filtered = nf;
+            m.exhausted = consumed - L - nf;
+            m.new_offset = wrap_pos(cur + stop_rel + 1u, n);
+            m.pos = bp;
+            m.score = best;
+            // the writeback's entry: one per row
+            if (dk) {
+                A.emit_ov[sl] = make_uint2(row, 2u);
+                A.emit_ov[it] = make_uint2(row, 0u);
+            } else {
+                A.emit_ov[it] = make_uint2(row, 1u);
+                if (phase == 0) {
+                    Wd.slot[bp] = it;
+                    atomicOr(&s_won[bp >> 5], 1u << (bp & 31u));
+                }
+            }
+        }
+        // the seed after the phase, in every lane (phase 1 starts from it)
+        const uint32_t last = e_pos[ns * L - 1u];
+        if (last >= n) {
+            if (tid == 0) {
+                wide_fail(Wd);
+                in.status = kSeedDeclined;
+                Wd.seed[phase] = in;
+            }
+            in.status = kSeedDeclined;
+            continue;
+        }
+        const uint32_t used = rel_of(last) + 1u;
+        in.placed += ns;
+        in.cur = wrap_pos(cur + used, n);
+        in.pos_used += used;
+        if (tid == 0) {
+            Wd.seed[phase] = in;
+            Wd.stats[0] += 1ull;
+        }
+    }
+}
+
 // The placed count of a 256-lane workgroup, one atomic per workgroup into one
 // of kPlacedSlots counters (the host sums them): same-address atomics from
 // every wave serialise at one L2 channel (32k of them at 6.4M rows cost more
@@ -5459,10 +5686,48 @@ uint32_t pe_chain_fused_max_n() { return pe::kChainBlock * 4u; }
 uint32_t pe_chain_fused_max_count() { return 256u; }
 uint32_t pe_chain_fused_max_classes() { return pe::kFusedMaxClasses; }
 
+// k_phases: dynamic LDS of a launch (its compact entries), and what a
+// workgroup of the current device may add to the kernel's static LDS (0: no
+// device); a launch past that keeps the two k_phase launches
+static int lds_per_workgroup(int dev);
+
+size_t pe_chain_one_lds_bytes(uint32_t n_visit, uint32_t count, uint32_t limit) {
+    return pe::one_lds_bytes(pe::one_entries(n_visit, count, limit));
+}
+
+size_t pe_chain_one_max_dyn() {
+    constexpr int kDevs = 64;
+    static int v[kDevs];
+    static bool init[kDevs];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kDevs) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (!init[dev]) {
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&pe::k_phases)) != hipSuccess) {
+            (void)hipGetLastError();
+            return 0;
+        }
+        const int d = lds_per_workgroup(dev) - (int)fa.sharedSizeBytes;
+        v[dev] = d > 0 ? d : 0;
+        init[dev] = true;
+    }
+    return (size_t)v[dev];
+}
+
+bool pe_chain_one_fits(uint32_t n_visit, uint32_t count, uint32_t limit) {
+    return n_visit != 0 && n_visit <= pe::kChainMaxN && count != 0 && limit != 0 && limit <= pe::kMaxChainLimit &&
+           pe_chain_one_lds_bytes(n_visit, count, limit) <= pe_chain_one_max_dyn();
+}
+
 // split (or null): five events recorded before k_base and after k_base,
-// k_chain, k_emit and k_emit_writeback (per-kernel device time, PE_KERNEL_SPLIT)
+// k_chain, k_emit and k_emit_writeback (per-kernel device time, PE_KERNEL_SPLIT);
+// wide_one: an armed launch resolves both wide phases in one k_phases launch
+// (the caller checked pe_chain_one_fits)
 hipError_t pe_launch_chain(const pe::BatchArgs* a, uint32_t n_evals, uint32_t max_blocks, int forced_items,
-                           hipStream_t st, hipEvent_t* split) {
+                           hipStream_t st, hipEvent_t* split, bool wide_one) {
     if (!a->base || !a->chain_vs || (a->n_visit > pe::kChainMaxN && n_evals != 1) || a->class_ok_stride ||
         a->limit > pe::kMaxChainLimit || a->count >= (1u << 18))   // redo entries pack count | position << 18
         return hipErrorInvalidValue;
@@ -5512,7 +5777,22 @@ hipError_t pe_launch_chain(const pe::BatchArgs* a, uint32_t n_evals, uint32_t ma
         hipLaunchKernelGGL(pe::k_base<false>, dim3(blocks), dim3(pe::kBaseBlock), 0, st, *a);
     }
     if (split) (void)hipEventRecord(split[1], st);
-    if (wd.bits) {
+    if (wd.bits && wide_one) {
+        // both rotations in one workgroup, the options compacted by rank in LDS
+        if (!pe_chain_one_fits(a->n_visit, a->count, a->limit)) return hipErrorInvalidValue;
+        static bool attr[64];   // per device: the attribute is set on the current device's function
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+        if (!attr[dev]) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pe::k_phases),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     (int)pe_chain_one_max_dyn());
+            if (e != hipSuccess) return e;
+            attr[dev] = true;
+        }
+        hipLaunchKernelGGL(pe::k_phases, dim3(1), dim3(pe::kOneBlock),
+                           pe_chain_one_lds_bytes(a->n_visit, a->count, a->limit), st, *a);
+    } else if (wd.bits) {
         // one Select per lane; the second rotation only when the count reaches it
         const uint32_t wg = (a->count + pe::kWideBlock - 1) / pe::kWideBlock;
         for (uint32_t ph = 0; ph < wd.phases; ph++)

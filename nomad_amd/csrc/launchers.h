@@ -90,8 +90,11 @@ uint32_t pe_emit_grid(uint32_t count);
 uint32_t pe_chain_max_limit();
 size_t pe_chain_lds_bytes(int hash_bits, bool packed, uint32_t n);
 int pe_chain_blocks_per_cu(size_t lds);
+size_t pe_chain_one_lds_bytes(uint32_t n_visit, uint32_t count, uint32_t limit);
+size_t pe_chain_one_max_dyn();
+bool pe_chain_one_fits(uint32_t n_visit, uint32_t count, uint32_t limit);
 hipError_t pe_launch_chain(const pe::BatchArgs* a, uint32_t n_evals, uint32_t max_blocks, int forced_items,
-                           hipStream_t st, hipEvent_t* split = nullptr);
+                           hipStream_t st, hipEvent_t* split = nullptr, bool wide_one = false);
 hipError_t pe_launch_sweep_step(const pe::SweepArgs* a, uint32_t blocks, const uint32_t* visit, uint32_t n,
                                 uint32_t offset, pe_ranked_node* out, uint32_t* state, hipStream_t st);
 hipError_t pe_launch_trace(const pe::NodeSoA* s, const pe::TgTables* t, const pe::Ask* a, const uint32_t* rows,

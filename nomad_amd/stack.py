@@ -115,6 +115,11 @@ def load_engine():
         lib.pe_speculation_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.pe_chain_wide_stats.restype = C.c_int
         lib.pe_chain_wide_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        if hasattr(lib, "pe_chain_wide_launches"):
+            lib.pe_chain_wide_launches.restype = C.c_int
+            lib.pe_chain_wide_launches.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+            lib.pe_chain_wide_one_lds.restype = C.c_int
+            lib.pe_chain_wide_one_lds.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
         lib.pe_comm_unique_id.restype = C.c_int
         lib.pe_comm_unique_id.argtypes = [abi.u8p, C.c_size_t]
         lib.pe_comm_init.restype = C.c_int
@@ -1159,6 +1164,23 @@ class GenericStack(_Stack):
         buf = (C.c_uint64 * 2)()
         self._check(self._lib.pe_chain_wide_stats(self._h, buf))
         return tuple(int(x) for x in buf)
+
+    def ChainWideLaunches(self):
+        """Chain launches with wide phases, by kind: (with two k_phase launches,
+        with both phases in one k_phases launch) (pe_chain_wide_launches)."""
+        buf = (C.c_uint64 * 2)()
+        self._check(self._lib.pe_chain_wide_launches(self._h, buf))
+        return tuple(int(x) for x in buf)
+
+    def ChainWideOneLds(self, n_visit, count, limit):
+        """(takes, need, cap): whether one k_phases launch takes a chain launch
+        of `count` Selects on `n_visit` positions, the dynamic LDS bytes it
+        needs and what a workgroup of this device may hold (pe_chain_wide_one_lds)."""
+        buf = (C.c_uint64 * 2)()
+        rc = self._lib.pe_chain_wide_one_lds(int(n_visit), int(count), int(limit), buf)
+        if rc < 0:
+            self._check(rc)
+        return bool(rc), int(buf[0]), int(buf[1])
 
     def last_phase_ms(self):
         """[host prep, kernel, D2H copy, total] of the last PlaceBatch, ms."""
