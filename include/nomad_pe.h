@@ -980,6 +980,71 @@ typedef struct pe_system_view {
 } pe_system_view;
 pe_system_view* pe_system_view_get(pe_stack* s);
 int pe_set_cursor(pe_stack* s, uint32_t tg_index, uint32_t offset, uint32_t limit);
+/* ---- CSI volumes (CSIVolumeChecker, feasible.go:209-337) ----------------------
+ * The CSI state of the snapshot, flattened by the caller. Every string field
+ * is an id of the snapshot's table (`strs` extends it, as in pe_set_job).
+ *   per node (CSR, off[n_nodes + 1]): Node.CSINodePlugins: the plugin id (the
+ *     map key), Healthy, NodeInfo.MaxVolumes;
+ *   per volume: ID, Namespace, PluginID, ReadSchedulable(), WriteSchedulable(),
+ *     WriteFreeClaims(), and (CSR, claim_off[n_volumes + 1]) the allocs of
+ *     WriteAllocs as (Namespace, JobID) of state.AllocByID, both PE_NONE for an
+ *     alloc the state no longer has;
+ *   per node (CSR): the indices into the volume table of the volumes
+ *     state.CSIVolumesByNodeID yields (state_store.go:2240-2280).
+ * n_nodes must equal the snapshot's node count. The table belongs to the
+ * snapshot: pe_set_state, pe_update_nodes and pe_update_allocs drop it;
+ * pe_reset_plan keeps it. table == NULL drops it. */
+typedef struct pe_csi_table {
+    uint32_t n_nodes;
+    uint32_t n_volumes;
+    const uint32_t* plug_off; const uint32_t* plug_id; const uint8_t* plug_healthy;
+    const int64_t* plug_max_volumes;
+    const uint32_t* vol_id; const uint32_t* vol_ns; const uint32_t* vol_plugin;
+    const uint8_t* vol_read_ok; const uint8_t* vol_write_ok; const uint8_t* vol_write_free;
+    const uint32_t* claim_off; const uint32_t* claim_ns; const uint32_t* claim_job;
+    const uint32_t* node_vol_off; const uint32_t* node_vol_index;
+} pe_csi_table;
+int pe_set_csi(pe_stack* s, const pe_strtab* strs, const pe_csi_table* table);
+/* The CSI volume requests of task group tg_index (TaskGroup.Volumes of type
+ * csi), after pe_set_job. The reference ranges over a Go map; the list order
+ * given here replaces it: the first failing request, in this order, names the
+ * reason. At most PE_MAX_CSI_REQ. A group with has_csi_volumes set and no
+ * table or no requests is refused (PE_EUNSUPPORTED "CSI volumes"). With both,
+ * pe_select (plain: no preferred nodes, no Preempt, pe_set_metrics off) and
+ * pe_system_place place it; every other placing call refuses it before
+ * anything changes. On a generic stack pe_select may itself return
+ * PE_EUNSUPPORTED with the cursor, the memo and the plan untouched: the
+ * reference would resume its walk past an unavailable node of a class already
+ * memoised eligible (select.go:59-67), or a full pass (a group with affinities
+ * or spreads) ends at such a node; the engine leaves both to the chain. */
+#define PE_MAX_CSI_REQ 16
+typedef struct pe_csi_request {
+    uint32_t source;      /* VolumeRequest.Source (str id) */
+    uint32_t read_only;   /* VolumeRequest.ReadOnly */
+    uint32_t per_alloc;   /* VolumeRequest.PerAlloc: the source takes the "[idx]" suffix */
+} pe_csi_request;
+int pe_set_csi_requests(pe_stack* s, uint32_t tg_index, const pe_csi_request* reqs, uint32_t n);
+/* AllocSuffix of the alloc name the next Selects of the group place
+ * (funcs.go:402): per_alloc sources become source + "[idx]". 0 after
+ * pe_set_csi_requests. */
+int pe_csi_alloc_index(pe_stack* s, uint32_t tg_index, uint32_t idx);
+/* The engine's availability column of the group, one code per snapshot row:
+ * 0 available, else request_index << 3 | reason with the reason numbered as
+ * isFeasible's checks run (feasible.go:293-333): 1 volume not found, 2 the
+ * node lacks the volume's plugin, 3 plugin unhealthy, 4 MaxVolumes reached,
+ * 5 no read claims, 6 no write claims, 7 volume in use by another job. */
+#define PE_CSI_NOT_FOUND 1u
+#define PE_CSI_NO_PLUGIN 2u
+#define PE_CSI_UNHEALTHY 3u
+#define PE_CSI_MAX_VOLUMES 4u
+#define PE_CSI_NO_READ 5u
+#define PE_CSI_NO_WRITE 6u
+#define PE_CSI_IN_USE 7u
+int pe_csi_check(pe_stack* s, uint32_t tg_index, uint16_t* codes);
+/* Measurement aid: device time of the last k_csi_avail launch in ms, by HIP
+ * events that are recorded only with PE_CSI_TIME=1 in the environment at
+ * pe_stack_create; 0 otherwise. */
+double pe_csi_last_ms(pe_stack* s);
 /* Host-side constraint semantics used for pre-resolution (checkConstraint,
  * feasible.go:785-820), exposed for known-answer tests; needs no device.
  * l_state / r_state: 0 nil (unknown ${...} target), 1 found, 2 missing ("", false). */

@@ -195,6 +195,43 @@ class pe_class_feas(C.Structure):
     _fields_ = [("task_group", C.c_uint32), ("computed_class", C.c_uint32), ("status", C.c_uint32)]
 
 
+# ---- CSI volumes (pe_set_csi, pe_set_csi_requests, pe_csi_check) -----------------
+PE_MAX_CSI_REQ = 16
+PE_CSI_NOT_FOUND, PE_CSI_NO_PLUGIN, PE_CSI_UNHEALTHY, PE_CSI_MAX_VOLUMES = 1, 2, 3, 4
+PE_CSI_NO_READ, PE_CSI_NO_WRITE, PE_CSI_IN_USE = 5, 6, 7
+
+
+class pe_csi_table(C.Structure):
+    _fields_ = [
+        ("n_nodes", C.c_uint32), ("n_volumes", C.c_uint32),
+        ("plug_off", u32p), ("plug_id", u32p), ("plug_healthy", u8p), ("plug_max_volumes", i64p),
+        ("vol_id", u32p), ("vol_ns", u32p), ("vol_plugin", u32p),
+        ("vol_read_ok", u8p), ("vol_write_ok", u8p), ("vol_write_free", u8p),
+        ("claim_off", u32p), ("claim_ns", u32p), ("claim_job", u32p),
+        ("node_vol_off", u32p), ("node_vol_index", u32p),
+    ]
+
+
+class pe_csi_request(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("read_only", C.c_uint32), ("per_alloc", C.c_uint32)]
+
+
+def bind_csi(lib):
+    """Attach restype/argtypes for the CSI entry points on a loaded engine."""
+    H = C.c_void_p
+    lib.pe_set_csi.restype = C.c_int
+    lib.pe_set_csi.argtypes = [H, C.POINTER(pe_strtab), C.POINTER(pe_csi_table)]
+    lib.pe_set_csi_requests.restype = C.c_int
+    lib.pe_set_csi_requests.argtypes = [H, C.c_uint32, C.POINTER(pe_csi_request), C.c_uint32]
+    lib.pe_csi_alloc_index.restype = C.c_int
+    lib.pe_csi_alloc_index.argtypes = [H, C.c_uint32, C.c_uint32]
+    lib.pe_csi_check.restype = C.c_int
+    lib.pe_csi_check.argtypes = [H, C.c_uint32, u16p]
+    lib.pe_csi_last_ms.restype = C.c_double
+    lib.pe_csi_last_ms.argtypes = [H]
+    return lib
+
+
 # Entry points declared in include/nomad_pe.h: (name, restype, argtypes)
 def _sigs(prefix, handle):
     H = C.c_void_p

@@ -456,7 +456,23 @@ struct TgPlan {
     std::vector<double> h_aff_class, h_aff_node;
     DevMem node_aux, aff_vals, aff_idx;
     bool aux_valid = false, aux_ok = false;
+    // CSI volume requests (pe_set_csi_requests) in the caller's order, the
+    // alloc index per_alloc sources take, and k_csi_avail's columns: the code
+    // per node with its page-locked host copy, and the per-node verdict
+    // without CSI that the kernel folds the availability into
+    bool has_csi = false;
+    std::string unsupported_else;      // the refusal has_csi_volumes replaced
+    std::vector<pe_csi_request> csi_reqs;
+    uint32_t csi_idx = 0;
+    bool csi_dirty = true;             // requests, index, table or the group's tables changed
+    DevMem csi_base_ok;
+    PinnedMem csi_codes;               // mapped: the kernel stores the codes where the host reads them
 };
+
+// A group with has_csi_volumes is refused with this text until it has both a
+// CSI table and its requests; csi_active: it has them and is placed with them.
+static const char* const kCsiRefused = "CSI volumes";
+static inline bool csi_active(const TgPlan& g) { return g.has_csi && !g.csi_reqs.empty() && g.unsupported.empty(); }
 
 static inline bool has_static(const TgPlan& g) { return !g.rports.empty() || !g.trports.empty(); }
 
@@ -488,6 +504,7 @@ struct Tunables {
     bool spin_wait = true;             // PE_SPIN_WAIT=0: chain launches wait with a stream sync
     bool counts_defer_ok = true;       // PE_COUNTS_DEFER=0: SetJob launches its counts at once
     bool kernel_split = false;         // PE_KERNEL_SPLIT=1 (or pe_set_kernel_split): per-kernel chain events
+    bool csi_time = false;             // PE_CSI_TIME=1: HIP events around k_csi_avail (pe_csi_last_ms)
     bool chain_wide = true;            // PE_CHAIN_WIDE=0: no wide phase launches before k_chain
     bool chain_wide_one = true;        // PE_CHAIN_WIDE_ONE=0: two k_phase launches, never one k_phases launch
     // profiling, printed to stderr
@@ -518,6 +535,7 @@ static Tunables read_tunables() {
     flag("PE_SPIN_WAIT", &t.spin_wait);
     flag("PE_COUNTS_DEFER", &t.counts_defer_ok);
     flag("PE_KERNEL_SPLIT", &t.kernel_split);
+    flag("PE_CSI_TIME", &t.csi_time);
     flag("PE_CHAIN_WIDE", &t.chain_wide);
     flag("PE_CHAIN_WIDE_ONE", &t.chain_wide_one);
     flag("PE_API_PROF", &t.api_prof);
@@ -830,6 +848,20 @@ struct pe_stack {
     std::vector<uint32_t> cls_str;                       // dense class -> ComputedClass str id
     bool elig_mute = false;                              // place_impl inside pe_place / spec_start
 
+    // CSI state of the snapshot (pe_set_csi): the host mirror the request
+    // records are resolved against, and the per-node CSRs k_csi_avail walks
+    struct Csi {
+        bool valid = false;
+        std::vector<uint32_t> vol_plugin;
+        std::vector<uint8_t> vol_read_ok, vol_write_ok, vol_write_free;
+        std::vector<uint32_t> claim_off, claim_ns, claim_job;
+        std::map<std::pair<uint32_t, uint32_t>, uint32_t> by_id;   // (namespace, volume id) -> volume
+        DevMem plug_off, plug_id, plug_healthy, plug_max, nvol_off, nvol_plugin;
+    } csi;
+    bool csi_scope = false;            // inside pe_select / pe_system_place: the calls that place a CSI group
+    hipEvent_t ev_csi0 = nullptr, ev_csi1 = nullptr;   // around the last k_csi_avail
+    bool csi_timed = false;
+
     // The unchanged SystemScheduler caller (scheduler_system.go:289-302):
     // SetNodes([node]) then Select for every node. From the third single-node
     // Select of a task group on, one k_system pass over every snapshot row
@@ -1093,6 +1125,7 @@ static void kid_log(pe_stack* s, uint8_t kind, uint32_t tgi, int32_t row, const 
 }
 
 static void elig_resolve(pe_stack* s);   // the served system-Select view replays it
+static void csi_drop(pe_stack* s);      // a new snapshot: the CSI table goes with the old one
 namespace {
 
 constexpr uint32_t kFullLdsMaxN = 32768;          // k_fullpass_lds tried up to this list length
@@ -3891,6 +3924,13 @@ int build_tables(pe_stack* s, TgPlan& g, const std::vector<uint32_t>& order, uin
         }
         if (s->job_escaped) node_ok = g.job_ok_node;
     }
+    if (csi_active(g)) {
+        // k_csi_avail folds the availability into node_ok: the column always
+        // exists for such a group, and the verdict without CSI is kept beside it
+        if (node_ok.empty()) node_ok.assign(n, 1);
+        HIP_TRY(s, upload_s(s, g.csi_base_ok, node_ok));
+        g.csi_dirty = true;
+    }
     g.node_ok_used = !node_ok.empty();
     if (g.node_ok_used) HIP_TRY(s, upload_s(s, g.node_ok, node_ok));
     {
@@ -4088,6 +4128,74 @@ size_t pset_lds_bytes(const pe::TgTables& t) {
     return b <= kPsetLdsBudget ? b : 0u;
 }
 
+// The request records of a CSI group against the snapshot's volumes, and one
+// k_csi_avail launch: the code column, stored straight into mapped page-locked
+// memory (no copy back, no wait here), and the group's node_ok / node_feas with
+// the availability folded in. Runs after the group's tables are built and again
+// when the requests, the alloc index or the table change.
+int csi_refresh(pe_stack* s, TgPlan& g) {
+    const uint32_t n = (uint32_t)s->nodes.size();
+    g.csi_dirty = false;
+    if (!n) return PE_OK;
+    pe::CsiArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.n = n;
+    A.n_req = (uint32_t)g.csi_reqs.size();
+    for (uint32_t q = 0; q < A.n_req; q++) {
+        const pe_csi_request& r = g.csi_reqs[q];
+        pe::CsiReq& d = A.req[q];
+        // SetVolumes (feasible.go:230-249): a per_alloc source takes AllocSuffix(allocName)
+        const uint32_t src = r.per_alloc ? s->lookup(s->S(r.source) + "[" + std::to_string(g.csi_idx) + "]") : r.source;
+        const auto it = src == PE_NONE ? s->csi.by_id.end() : s->csi.by_id.find({s->job_ns, src});
+        if (it == s->csi.by_id.end()) continue;   // found = 0
+        const uint32_t v = it->second;
+        d.found = 1;
+        d.plugin = s->csi.vol_plugin[v];
+        if (r.read_only) {
+            if (!s->csi.vol_read_ok[v]) d.vol_reason = PE_CSI_NO_READ;
+        } else if (!s->csi.vol_write_ok[v]) {
+            d.vol_reason = PE_CSI_NO_WRITE;
+        } else if (!s->csi.vol_write_free[v]) {
+            // the blocking allocs must all be this job's (feasible.go:322-331)
+            for (uint32_t k = s->csi.claim_off[v]; k < s->csi.claim_off[v + 1]; k++)
+                if (s->csi.claim_ns[k] == PE_NONE || s->csi.claim_ns[k] != s->job_ns || s->csi.claim_job[k] != s->job_id)
+                    d.vol_reason = PE_CSI_IN_USE;
+        }
+    }
+    {
+        const int rc = flush_fold(s);   // the class table reaches the device with the group's fold
+        if (rc) return rc;
+    }
+    HIP_TRY(s, g.csi_codes.ensure(sizeof(uint16_t) * (size_t)n));
+    A.plug_off = s->csi.plug_off.as<uint32_t>();
+    A.plug_id = s->csi.plug_id.as<uint32_t>();
+    A.plug_healthy = s->csi.plug_healthy.as<uint8_t>();
+    A.plug_max = s->csi.plug_max.as<int64_t>();
+    A.nvol_off = s->csi.nvol_off.as<uint32_t>();
+    A.nvol_plugin = s->csi.nvol_plugin.as<uint32_t>();
+    A.rec = soa_of(s).rec;
+    A.class_ok = g.class_ok.as<uint8_t>();
+    A.base_ok = g.csi_base_ok.as<uint8_t>();
+    A.codes = g.csi_codes.dev<uint16_t>();
+    if (!A.codes) return s->fail(PE_EHIP, "mapped code column unavailable");
+    A.node_ok = g.node_ok.as<uint8_t>();
+    A.node_feas = g.node_feas.as<uint8_t>();
+    if (s->tun.csi_time) {   // measurement aid: events around the launch (pe_csi_last_ms)
+        if (!s->ev_csi0) {
+            HIP_TRY(s, hipEventCreate(&s->ev_csi0));
+            HIP_TRY(s, hipEventCreate(&s->ev_csi1));
+        }
+        HIP_TRY(s, hipEventRecord(s->ev_csi0, s->stream));
+    }
+    HIP_TRY_STATE(s, pe_launch_csi_avail(&A, s->stream));
+    if (s->tun.csi_time) {
+        HIP_TRY(s, hipEventRecord(s->ev_csi1, s->stream));
+        s->csi_timed = true;
+    }
+    g.aux_valid = false;   // the sweep's per-node word carries the verdict bit
+    return PE_OK;
+}
+
 int prepare_tg(pe_stack* s, uint32_t tgi, const std::vector<uint32_t>& order, uint32_t start) {
     ApiScope prof_(s, "prepare_tg");
     if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
@@ -4095,6 +4203,8 @@ int prepare_tg(pe_stack* s, uint32_t tgi, const std::vector<uint32_t>& order, ui
     if (tgi >= s->tgs.size()) return s->fail(PE_EINVAL, "task group index out of range");
     TgPlan& g = *s->tgs[tgi];
     if (!g.unsupported.empty()) return s->fail(PE_EUNSUPPORTED, g.unsupported);
+    if (csi_active(g) && (!s->csi_scope || !s->kids.empty()))
+        return s->fail(PE_EUNSUPPORTED, "CSI volumes: pe_select and pe_system_place on one device place such a group");
     if (!s->cores_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->cores_unsupported);
     if (g.ask.cores > 0 && !s->cores_tg_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->cores_tg_unsupported);
     if (!g.psets_built) {
@@ -4113,6 +4223,7 @@ int prepare_tg(pe_stack* s, uint32_t tgi, const std::vector<uint32_t>& order, ui
         int rc = build_tables(s, g, order, start);
         if (rc) return rc;
     }
+    if (csi_active(g) && g.csi_dirty) return csi_refresh(s, g);
     return PE_OK;
 }
 
@@ -4633,9 +4744,20 @@ static inline void widen_rec(const pe::EmitRec& e, pe_ranked_node* o) {
 // One evaluation on the stack's plan (pe_select / pe_place): the fused count
 // loop in launches of at most H/2 placements, each merging its overlay back
 // into the HBM SoA so the plan persists.
+// `cut` (csi_select's run B, one windowed Select): the list was cut short at a
+// node that ended the stream. The windowed kernel walks it whatever its length
+// and reports in *cut->aside how many options its LimitIterator had set aside
+// at the end; sub_len > 0: the list is positions [sub_begin, sub_begin +
+// sub_len) of `order`, which must be the SetNodes list (its device copy is
+// entered at sub_begin, no upload).
+struct PlaceCut {
+    uint32_t sub_begin = 0, sub_len = 0;
+    uint32_t* aside = nullptr;
+};
+
 int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::vector<uint32_t>& order,
               uint32_t offset, const pe_select_options* opts, pe_ranked_node* out, uint32_t* placed,
-              uint32_t* new_offset) {
+              uint32_t* new_offset, const PlaceCut* cut = nullptr) {
     TgPlan& g = *s->tgs[tgi];
     *placed = 0;
     *new_offset = offset;
@@ -4644,8 +4766,14 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
         *new_offset = 0;
         return PE_OK;
     }
-    const uint32_t n = (uint32_t)order.size();
-    const bool full = full_scan_kernel(s, g, n);
+    if (cut && (count != 1 || !g.psets.empty() || !g.affinities.empty() || s->limit >= 0x7FFFFFFFu ||
+                (cut->sub_len && (&order != &s->visit || (size_t)cut->sub_begin + cut->sub_len > order.size()))))
+        return s->fail(PE_EINTERNAL, "run_place: a cut list needs one windowed Select");
+    const bool sub = cut && cut->sub_len;
+    const uint32_t n = sub ? cut->sub_len : (uint32_t)order.size();
+    // a cut list: the windowed kernel walks it (its closed form holds for any
+    // list length) rather than the full pass a list within the limit would take
+    const bool full = !cut && full_scan_kernel(s, g, n);
     std::vector<pe::EmitRec>* sink = s->emit_sink;
     pe::BatchArgs A = batch_args(s, g);
     if (opts && opts->penalty_count > 0) {
@@ -4714,7 +4842,7 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
             HIP_TRY(s, upload_visit(s, order));
         }
     }
-    A.perms = s->d_visit.as<uint32_t>();
+    A.perms = s->d_visit.as<uint32_t>() + (sub ? cut->sub_begin : 0u);
     A.n_visit = n;
     const uint32_t chunk = std::max<uint32_t>(1, (1u << A.hash_bits) / 2);
     // records and status land in mapped page-locked memory: the kernel writes
@@ -4726,6 +4854,10 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
     A.full_out = s->h_place_out.dev<pe_ranked_node>();
     A.eval_status = s->h_place_status.dev<uint32_t>();
     if (!A.full_out || !A.eval_status) return s->fail(PE_EHIP, "mapped result buffers unavailable");
+    if (cut) {   // (count == 1: never the chain)
+        s->h_place_status.as<uint32_t>()[2] = 0;
+        A.aside_out = A.eval_status + 2;
+    }
     // the table build's pending fold: carried by the chain's first launch
     // (k_base pulls the class table into LDS per workgroup while that stays
     // small on the bus, the fused k_chain for short lists), else its own launch
@@ -4896,6 +5028,7 @@ int run_place(pe_stack* s, uint32_t tgi, uint32_t count, int commit, const std::
         const double t2 = hprof ? now_us() : 0.0;
         uint32_t st[2];
         std::memcpy(st, const_cast<const uint32_t*>(s->h_place_status.as<uint32_t>()), sizeof(st));
+        if (cut && cut->aside) *cut->aside = const_cast<const uint32_t*>(s->h_place_status.as<uint32_t>())[2];
         const uint32_t got = std::min(c, st[0] + 1);   // placed + the failing Select
         if (chain) {
             const pe::EmitRec* er = s->h_emit_out.as<pe::EmitRec>();
@@ -5095,6 +5228,8 @@ void pe_stack_destroy(pe_stack* s) {
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     if (s->ev2) (void)hipEventDestroy(s->ev2);
+    if (s->ev_csi0) (void)hipEventDestroy(s->ev_csi0);
+    if (s->ev_csi1) (void)hipEventDestroy(s->ev_csi1);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -5277,6 +5412,7 @@ static int set_state_one(pe_stack* s, const pe_strtab* strs, const pe_node_table
     s->stop_count.clear();
     s->gen++;
     HIP_TRY(s, hipSetDevice(s->device));
+    csi_drop(s);
     s->strs.clear();
     s->sid.clear();
     s->add_strings(strs);
@@ -5313,6 +5449,7 @@ static int update_allocs_one(pe_stack* s, const pe_strtab* strs, const pe_alloc_
     s->stop_count.clear();
     s->gen++;
     HIP_TRY(s, hipSetDevice(s->device));
+    csi_drop(s);   // claims and in-use volumes follow the allocs
     s->add_strings(strs);
     const size_t before = s->allocs.size();
     int rc = append_allocs(s, allocs, index);
@@ -5357,6 +5494,7 @@ static int update_nodes_one(pe_stack* s, const pe_strtab* strs, const pe_node_ta
     s->stop_count.clear();
     s->gen++;
     HIP_TRY(s, hipSetDevice(s->device));
+    csi_drop(s);   // per-node CSRs of the old rows
     s->add_strings(strs);
     const uint32_t n_old = (uint32_t)s->nodes.size();
     std::vector<uint32_t> target(nodes->n);
@@ -5540,7 +5678,11 @@ static int set_job_one(pe_stack* s, const pe_strtab* strs, const pe_job* j) {
         for (auto& c : g->constraints) g->escaped = g->escaped || c.escapes;
         for (uint32_t k = 0; k < t.volume_count; k++)
             g->volumes.emplace_back(j->volume_source[t.volume_off + k], j->volume_read_only[t.volume_off + k] != 0);
-        if (t.has_csi_volumes) g->unsupported = "CSI volumes";
+        if (t.has_csi_volumes) {   // refused until pe_set_csi_requests finds a table (csi_gate)
+            g->has_csi = true;
+            g->unsupported_else = g->unsupported;
+            g->unsupported = kCsiRefused;
+        }
         g->has_network = t.has_network != 0;
         g->net_mode = t.has_network ? t.net_mode : s->lookup("host");
         g->net_host = t.net_host_network;
@@ -6815,8 +6957,9 @@ static int sys_flush(pe_stack* s) {
 // an escaped group), and the result record the cache holds complete (no
 // device offers, reserved cores or static ports to return).
 static bool sys_cacheable(pe_stack* s, TgPlan& g) {
+    // (a CSI group's verdict moves with the alloc index: every Select asks the column)
     return g.unsupported.empty() && g.psets.empty() && g.dev_reqs.empty() && g.ask.cores == 0 && !has_static(g) &&
-           (g.escaped || g.nonuniform.empty()) && s->visit_unique;
+           (g.escaped || g.nonuniform.empty()) && s->visit_unique && !csi_active(g);
 }
 
 // The served system-Select view's per-row AllocMetric entries (nomad_pe.h,
@@ -7014,9 +7157,17 @@ static bool sys_serve(pe_stack* s, uint32_t tgi, const pe_select_options* opts, 
     return true;
 }
 
+// The calls that place a CSI group hold this while they run (prepare_tg).
+struct CsiScope {
+    pe_stack* s;
+    explicit CsiScope(pe_stack* st) : s(st) { if (s) s->csi_scope = true; }
+    ~CsiScope() { if (s) s->csi_scope = false; }
+};
+
 int pe_select(pe_stack* s, uint32_t tgi, const pe_select_options* opts, pe_ranked_node* out) {
     PE_FLUSH_RESET(s);
     if (!s || !out) return PE_EINVAL;
+    CsiScope csi_scope_(s);
     s->pre_overflow.clear();
     int rc = PE_OK;
     if (s->cfg.stack_kind == PE_STACK_SYSTEM && !s->tun.test_fallback_every && sys_serve(s, tgi, opts, out, &rc))
@@ -7041,9 +7192,127 @@ int pe_select(pe_stack* s, uint32_t tgi, const pe_select_options* opts, pe_ranke
     return rc;
 }
 
+// ---- Selects of a group with CSI volume requests ------------------------------
+// The CSI checker is an availability checker (stack.go:248, 381): a node it
+// fails is skipped while its class's task-group status is unknown or escaped
+// (feasible.go:1145-1149), but ends the stream for this Select when the class
+// is already memoised eligible (:1112-1119).
+
+// What a placing call refuses for a CSI group, before anything changes.
+static int csi_refuse(pe_stack* s, const pe_select_options* opts) {
+    if (s->metrics_on) return s->fail(PE_EUNSUPPORTED, "CSI volumes with pe_set_metrics on");
+    if (!s->kids.empty()) return s->fail(PE_EUNSUPPORTED, "CSI volumes on a handle over several devices");
+    if (s->cfg.stack_kind == PE_STACK_GENERIC && opts && (opts->preferred_count || opts->preempt))
+        return s->fail(PE_EUNSUPPORTED, "CSI volumes in a Select with preferred nodes or Preempt");
+    return PE_OK;
+}
+
+// The first position of the window [start, start + len) of the SetNodes list
+// at which FeasibilityWrapper.Next returns nil: an unavailable node that passed
+// the job checks and whose class was memoised eligible, at Select start (the
+// memo shadow) or by an earlier node of the window that ran the task group's
+// checks and passed. -1: every unavailable node of the window is a skip.
+static int csi_window_stop(pe_stack* s, TgPlan& g, uint32_t start, uint32_t len) {
+    if (g.escaped) return -1;   // no memo entry for the group: always the slow path
+    const size_t m = s->visit.size(), n = s->nodes.size();
+    const uint16_t* codes = g.csi_codes.as<uint16_t>();
+    pe::ConstraintEvaluator ev;
+    if (s->job_memo.size() != s->ncls) s->job_memo.assign(s->ncls, -1);
+    if (g.sig_tg.size() != s->sig_rep.size()) {
+        g.sig_tg.clear();
+        classify_classes(s, g, ev);
+    }
+    std::vector<int8_t> st = elig_tg(s, g.name).st;   // -1 unknown / 0 ineligible / 1 eligible
+    len = (uint32_t)std::min<uint64_t>(len, m);
+    for (uint32_t k = 0; k < len; k++) {
+        const uint32_t row = s->visit[(start + k) % m];
+        const HostNode& nd = s->nodes[row];
+        const uint32_t c = nd.cls;
+        bool jr;
+        if (s->job_escaped) {
+            jr = g.job_ok_node.size() == n ? g.job_ok_node[row] != 0 : job_feasible(s, ev, s->view(row));
+        } else {
+            if (s->job_memo[c] == -1) s->job_memo[c] = job_feasible(s, ev, s->view(row)) ? 1 : 0;
+            jr = s->job_memo[c] == 1;
+        }
+        if (!jr || st[c] == 0) continue;
+        if (st[c] == 1) {
+            if (codes[row]) return (int)k;
+            continue;
+        }
+        st[c] = g.sig_tg[nd.sig] ? 1 : 0;   // this node decides the class; unavailable: a skip
+    }
+    return -1;
+}
+
+static int csi_select(pe_stack* s, uint32_t tgi, const pe_select_options* opts, pe_ranked_node* out,
+                      uint32_t limit_before) {
+    TgPlan& g = *s->tgs[tgi];
+    if (!g.escaped && !g.nonuniform.empty()) {
+        s->limit = limit_before;
+        return s->fail(PE_EUNSUPPORTED, "CSI volumes with computed classes whose nodes differ in the group's checks");
+    }
+    elig_resolve(s);   // the memo as the earlier Selects left it
+    const uint32_t start = s->offset, m = (uint32_t)s->visit.size();
+    uint32_t placed, no;
+    // run A: the Select with the unavailable nodes filtered
+    pe_ranked_node a;
+    int rc = run_place(s, tgi, 1, 0, s->visit, start, opts, &a, &placed, &no);
+    if (rc) return rc;
+    HIP_TRY(s, hipStreamSynchronize(s->stream));   // (run A waited already: the codes were stored before it ran)
+    const int p = m ? csi_window_stop(s, g, start, a.nodes_evaluated) : -1;
+    if (p < 0) {
+        *out = a;
+        s->offset = no;
+        elig_log_span(s, tgi, start, out->nodes_evaluated);
+        return PE_OK;
+    }
+    // run B: the stream ended at position p; the options pulled before it decide
+    pe_ranked_node b;
+    std::memset(&b, 0, sizeof(b));
+    b.row = -1;
+    uint32_t aside = 0;
+    if (p > 0) {
+        if (!g.psets.empty() || !g.affinities.empty() || s->limit >= 0x7FFFFFFFu) {
+            // a full pass: its kernel does not report the set-aside options
+            s->limit = limit_before;
+            return s->fail(PE_EUNSUPPORTED, "CSI volumes: a full-pass Select that ends at an unavailable node");
+        }
+        PlaceCut cut;
+        cut.aside = &aside;
+        if (start + (uint32_t)p <= m) {   // no wrap: a stretch of the list already on the device
+            cut.sub_begin = start;
+            cut.sub_len = (uint32_t)p;
+            rc = run_place(s, tgi, 1, 0, s->visit, 0, opts, &b, &placed, &no, &cut);
+        } else {
+            std::vector<uint32_t> rows((size_t)p);
+            for (int i = 0; i < p; i++) rows[i] = s->visit[(start + (uint32_t)i) % m];
+            rc = run_place(s, tgi, 1, 0, rows, 0, opts, &b, &placed, &no, &cut);
+        }
+        if (rc) return rc;
+    }
+    if (aside > 0) {
+        // LimitIterator holds skipped options: it asks the source again, and
+        // the walk resumes past the node (select.go:44-67)
+        s->limit = limit_before;
+        return s->fail(PE_EUNSUPPORTED, "CSI volumes: the chain resumes past an unavailable node (skipped options pending)");
+    }
+    b.nodes_evaluated = (uint32_t)p + 1u;
+    b.nodes_filtered += 1u;
+    b.new_offset = (start + (uint32_t)p + 1u) % m;
+    *out = b;
+    s->offset = b.new_offset;
+    elig_log_span(s, tgi, start, (uint32_t)p + 1u);
+    return PE_OK;
+}
+
 // `rec`: the record's index in the call's output (PreemptedAllocs overflow).
 static int select_impl(pe_stack* s, uint32_t tgi, const pe_select_options* opts, pe_ranked_node* out, uint32_t rec) {
     if (!s || !out) return PE_EINVAL;
+    if (s->have_job && tgi < s->tgs.size() && csi_active(*s->tgs[tgi])) {
+        const int crc = csi_refuse(s, opts);
+        if (crc) return crc;
+    }
     s->gen++;
     s->metrics_valid = false;
     HIP_TRY(s, hipSetDevice(s->device));
@@ -7099,7 +7368,9 @@ static int select_impl(pe_stack* s, uint32_t tgi, const pe_select_options* opts,
     int rc = prepare_tg(s, tgi, s->visit, s->offset);
     if (rc) return rc;
     TgPlan& g = *s->tgs[tgi];
+    const uint32_t limit_before = s->limit;
     if (tg_full_scan(s, g)) s->limit = 0x7FFFFFFF;   // never reset until SetNodes (stack.go:165-167)
+    if (csi_active(g)) return csi_select(s, tgi, opts, out, limit_before);
     if (opts && opts->preempt) {
         uint32_t no;
         const uint32_t start0 = s->offset;
@@ -7814,6 +8085,7 @@ static bool spec_eligible(pe_stack* s, uint32_t tgi, const pe_select_options* op
     if (opts && (opts->penalty_count || opts->preferred_count || opts->preempt)) return false;
     if (!s->have_state || !s->have_job || tgi >= s->tgs.size()) return false;
     if (s->tgs[tgi]->ask.cores > 0) return false;   // the rollback kernel does not return reserved cores
+    if (csi_active(*s->tgs[tgi])) return false;     // every Select checks its window for a stop (csi_select)
     for (size_t k = 0; k < s->tgs.size(); k++)   // commits would rebuild a sibling's collision counts
         if (k != tgi && s->tgs[k]->name == s->tgs[tgi]->name) return false;
     // with AllocMetric on, the records' maps come from the batched trace
@@ -8553,6 +8825,7 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
         if (!why && c.op == "distinct_property") why = "distinct_property";
     if (why) return s->fail(PE_EUNSUPPORTED, fn + why);
     if (!g.unsupported.empty()) return s->fail(PE_EUNSUPPORTED, g.unsupported);
+    if (csi_active(g)) return s->fail(PE_EUNSUPPORTED, fn + "CSI volumes");
     if (!s->cores_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->cores_unsupported);
     // the eviction walk: what evict_eval would flag kEvictUnsup for (a device
     // ask: PreemptForDevice, and the old alloc's instances stay with it,
@@ -9136,6 +9409,7 @@ int prepare_batch(pe_stack* s, uint32_t tgi, uint32_t count) {
     const uint32_t E = s->staged_evals, n = s->staged_n;
     TgPlan& g = *s->tgs[tgi];
     if (!g.unsupported.empty()) return s->fail(PE_EUNSUPPORTED, g.unsupported);
+    if (csi_active(g)) return s->fail(PE_EUNSUPPORTED, "pe_place_batch: CSI volumes");
     if (!g.psets_built) {
         int rc = build_psets(s, g);
         if (rc) return rc;
@@ -9396,6 +9670,10 @@ static int system_place_impl(pe_stack* s, uint32_t tgi, double* out_score, uint8
         if (frc) return frc;
     }
     if (s->cfg.stack_kind != PE_STACK_SYSTEM) return s->fail(PE_ESTATE, "pe_system_place needs a system stack");
+    if (s->have_job && tgi < s->tgs.size() && csi_active(*s->tgs[tgi])) {
+        const int crc = csi_refuse(s, nullptr);
+        if (crc) return crc;
+    }
     s->sysg.pre_valid = false;   // (pe_system_groups_preempted: until the next pe_system_place* call)
     s->sysg.met_valid = false;   // (pe_system_groups_metrics likewise)
     s->gen++;
@@ -9835,6 +10113,151 @@ int pe_flush(pe_stack* s) {
     PE_FLUSH_RESET(s);
     if (!s) return PE_EINVAL;
     return spec_flush(s);
+}
+
+// ---- CSI volumes: the snapshot's table and a group's requests -------------------
+
+// A group with has_csi_volumes is placed once it has a table and requests.
+static void csi_gate(pe_stack* s, TgPlan& g) {
+    if (!g.has_csi) return;
+    const bool ok = s->csi.valid && !g.csi_reqs.empty();
+    if (ok && g.unsupported == kCsiRefused) g.unsupported = g.unsupported_else;
+    else if (!ok && g.unsupported.empty()) g.unsupported = kCsiRefused;
+    g.csi_dirty = true;
+}
+
+static void csi_drop(pe_stack* s) {
+    s->csi.valid = false;
+    s->csi.by_id.clear();
+    for (auto& g : s->tgs) csi_gate(s, *g);
+}
+
+static bool csr_ok(const uint32_t* off, uint32_t n) {
+    if (!off || off[0] != 0) return false;
+    for (uint32_t i = 0; i < n; i++)
+        if (off[i + 1] < off[i]) return false;
+    return true;
+}
+
+int pe_set_csi(pe_stack* s, const pe_strtab* strs, const pe_csi_table* t) {
+    PE_FLUSH_RESET(s);
+    if (!s) return PE_EINVAL;
+    if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
+    {
+        const int rc = spec_flush(s);
+        if (rc) return rc;
+    }
+    s->gen++;
+    if (!t) { csi_drop(s); return PE_OK; }
+    const uint32_t n = t->n_nodes, nv = t->n_volumes;
+    if (n != s->nodes.size()) return s->fail(PE_EINVAL, "pe_csi_table.n_nodes differs from the snapshot");
+    if (!csr_ok(t->plug_off, n) || !csr_ok(t->node_vol_off, n) || !csr_ok(t->claim_off, nv))
+        return s->fail(PE_EINVAL, "pe_csi_table: a CSR offset array is missing or not monotone from 0");
+    const uint32_t np = t->plug_off[n], nu = t->node_vol_off[n], nc = t->claim_off[nv];
+    if ((np && (!t->plug_id || !t->plug_healthy || !t->plug_max_volumes)) || (nu && !t->node_vol_index) ||
+        (nc && (!t->claim_ns || !t->claim_job)) ||
+        (nv && (!t->vol_id || !t->vol_ns || !t->vol_plugin || !t->vol_read_ok || !t->vol_write_ok || !t->vol_write_free)))
+        return s->fail(PE_EINVAL, "pe_csi_table: a column is missing");
+    for (uint32_t k = 0; k < nu; k++)
+        if (t->node_vol_index[k] >= nv) return s->fail(PE_EINVAL, "pe_csi_table.node_vol_index out of range");
+    HIP_TRY(s, hipSetDevice(s->device));
+    s->add_strings(strs);
+    pe_stack::Csi& c = s->csi;
+    c.valid = false;
+    c.vol_plugin.assign(t->vol_plugin, t->vol_plugin + nv);
+    c.vol_read_ok.assign(t->vol_read_ok, t->vol_read_ok + nv);
+    c.vol_write_ok.assign(t->vol_write_ok, t->vol_write_ok + nv);
+    c.vol_write_free.assign(t->vol_write_free, t->vol_write_free + nv);
+    c.claim_off.assign(t->claim_off, t->claim_off + nv + 1);
+    c.claim_ns.assign(t->claim_ns, t->claim_ns + nc);
+    c.claim_job.assign(t->claim_job, t->claim_job + nc);
+    c.by_id.clear();
+    for (uint32_t v = 0; v < nv; v++) c.by_id.emplace(std::make_pair(t->vol_ns[v], t->vol_id[v]), v);
+    // the device walks each node's volumes as their plugin ids (one gather less per lane);
+    // every array holds one spare element, so an empty CSR still has a column
+    std::vector<uint32_t> plug_off(t->plug_off, t->plug_off + n + 1), nvol_off(t->node_vol_off, t->node_vol_off + n + 1);
+    std::vector<uint32_t> plug_id(np + 1, PE_NONE), nvol_plugin(nu + 1, PE_NONE);
+    std::vector<uint8_t> healthy(np + 1, 0);
+    std::vector<int64_t> maxv(np + 1, 0);
+    for (uint32_t k = 0; k < np; k++) {
+        plug_id[k] = t->plug_id[k];
+        healthy[k] = t->plug_healthy[k] ? 1 : 0;
+        maxv[k] = t->plug_max_volumes[k];
+    }
+    for (uint32_t k = 0; k < nu; k++) nvol_plugin[k] = t->vol_plugin[t->node_vol_index[k]];
+    HIP_TRY(s, upload_s(s, c.plug_off, plug_off));
+    HIP_TRY(s, upload_s(s, c.plug_id, plug_id));
+    HIP_TRY(s, upload_s(s, c.plug_healthy, healthy));
+    HIP_TRY(s, upload_s(s, c.plug_max, maxv));
+    HIP_TRY(s, upload_s(s, c.nvol_off, nvol_off));
+    HIP_TRY(s, upload_s(s, c.nvol_plugin, nvol_plugin));
+    c.valid = true;
+    for (auto& g : s->tgs) csi_gate(s, *g);
+    return PE_OK;
+}
+
+int pe_set_csi_requests(pe_stack* s, uint32_t tgi, const pe_csi_request* reqs, uint32_t n) {
+    PE_FLUSH_RESET(s);
+    if (!s || (!reqs && n)) return PE_EINVAL;
+    if (!s->have_job) return s->fail(PE_ESTATE, "pe_set_job not called");
+    if (tgi >= s->tgs.size()) return s->fail(PE_EINVAL, "task group index out of range");
+    if (n > PE_MAX_CSI_REQ) return s->fail(PE_EUNSUPPORTED, "more than 16 CSI volume requests");
+    TgPlan& g = *s->tgs[tgi];
+    if (!g.has_csi) return s->fail(PE_EINVAL, "pe_set_csi_requests: the task group has no has_csi_volumes");
+    for (uint32_t i = 0; i < n; i++)
+        if (reqs[i].source >= s->strs.size()) return s->fail(PE_EINVAL, "pe_csi_request.source is not a string id");
+    {
+        const int rc = spec_flush(s);
+        if (rc) return rc;
+    }
+    s->gen++;
+    g.csi_reqs.assign(reqs, reqs + n);
+    g.csi_idx = 0;
+    csi_gate(s, g);
+    g.tables_valid = false;   // node_ok exists for a group that is placed with its requests
+    return PE_OK;
+}
+
+int pe_csi_alloc_index(pe_stack* s, uint32_t tgi, uint32_t idx) {
+    if (!s) return PE_EINVAL;
+    if (!s->have_job || tgi >= s->tgs.size()) return s->fail(PE_EINVAL, "task group index out of range");
+    TgPlan& g = *s->tgs[tgi];
+    if (g.csi_idx == idx) return PE_OK;
+    g.csi_idx = idx;
+    for (const pe_csi_request& r : g.csi_reqs)
+        if (r.per_alloc) g.csi_dirty = true;   // the next Select's prepare_tg launches k_csi_avail again
+    return PE_OK;
+}
+
+int pe_csi_check(pe_stack* s, uint32_t tgi, uint16_t* codes) {
+    PE_FLUSH_RESET(s);
+    if (!s || !codes) return PE_EINVAL;
+    if (!s->have_job || tgi >= s->tgs.size()) return s->fail(PE_EINVAL, "task group index out of range");
+    if (!csi_active(*s->tgs[tgi])) {
+        const std::string& why = s->tgs[tgi]->unsupported;
+        return why.empty() ? s->fail(PE_ESTATE, "pe_csi_check: the task group has no CSI requests")
+                           : s->fail(PE_EUNSUPPORTED, why);
+    }
+    {
+        const int rc = spec_flush(s);
+        if (rc) return rc;
+    }
+    HIP_TRY(s, hipSetDevice(s->device));
+    CsiScope scope(s);
+    const int rc = prepare_tg(s, tgi, s->visit, s->offset);
+    if (rc) return rc;
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    const size_t n = s->nodes.size();
+    if (n) std::memcpy(codes, s->tgs[tgi]->csi_codes.p, sizeof(uint16_t) * n);
+    return PE_OK;
+}
+
+double pe_csi_last_ms(pe_stack* s) {
+    if (!s || !s->csi_timed) return 0.0;
+    float ms = 0;
+    if (hipEventSynchronize(s->ev_csi1) != hipSuccess || hipEventElapsedTime(&ms, s->ev_csi0, s->ev_csi1) != hipSuccess)
+        return 0.0;
+    return ms;
 }
 
 int pe_system_spec_stats(const pe_stack* s, uint64_t* out2) {
@@ -10316,6 +10739,7 @@ int pe_preempted_of(const pe_stack* s, uint32_t record, uint32_t* out, uint32_t 
 int pe_system_place(pe_stack* s, uint32_t tgi, double* out_score, uint8_t* out_status, uint32_t* placed) {
     PE_FLUSH_RESET(s);
     if (!s || (!out_score) != (!out_status)) return PE_EINVAL;
+    CsiScope csi_scope_(s);
     s->pre_overflow.clear();
     if (!s->kids.empty() && s->kids_valid && out_score) {   // (the staged-results form runs on the root)
         int rc = spec_flush(s);
@@ -10401,6 +10825,8 @@ static int sysg_check(pe_stack* s, const SysGroupsCall& c, const double* out_sco
     if (why) return s->fail(PE_EUNSUPPORTED, fn + ": " + why);
     for (uint32_t k = 0; k < n_tg; k++)
         if (!s->tgs[tgs[k]]->unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->tgs[tgs[k]]->unsupported);
+    for (uint32_t k = 0; k < n_tg; k++)
+        if (csi_active(*s->tgs[tgs[k]])) return s->fail(PE_EUNSUPPORTED, fn + ": CSI volumes in a listed group");
     if (!s->cores_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->cores_unsupported);
     plan_settle(s);   // (the deferred entries written out: nothing a caller can observe)
     if (c.evicting) {

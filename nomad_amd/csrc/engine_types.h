@@ -348,6 +348,42 @@ struct BatchArgs {
     EmitRec* emit_out;            // k_emit's records (single-evaluation chain), or null
     pe_placement* out;            // [n_evals][count] compact records, or null
     uint32_t* eval_status;        // [n_evals][2]: placed, final cursor
+    // one evaluation of k_window, or null: the options the last Select's
+    // LimitIterator had set aside when its pull ended (a source that ended
+    // early would be asked again while any is pending, select.go:59-67).
+    // k_place does not report it.
+    uint32_t* aside_out;
+};
+
+// k_csi_avail: CSIVolumeChecker.isFeasible (feasible.go:261-337) per node.
+// The host resolves what does not depend on the node into one record per
+// request (after the per_alloc suffix): the volume's plugin, and the first of
+// the volume-level failures (not found, read / write claims, claim holders of
+// another job); the lane adds the node's part (plugin present, healthy,
+// MaxVolumes against the node's volumes of that plugin).
+constexpr int kMaxCsiReq = 16;
+struct CsiReq {
+    uint32_t plugin;       // the volume's PluginID (str id); unused when not found
+    uint32_t found;        // CSIVolumeByID returned a volume
+    uint32_t vol_reason;   // 0, or PE_CSI_NO_READ / NO_WRITE / IN_USE
+    uint32_t _pad;
+};
+struct CsiArgs {
+    uint32_t n;                    // snapshot rows
+    uint32_t n_req;                // <= kMaxCsiReq
+    const uint32_t* plug_off;      // [n + 1] Node.CSINodePlugins (CSR)
+    const uint32_t* plug_id;
+    const uint8_t* plug_healthy;
+    const int64_t* plug_max;       // NodeInfo.MaxVolumes
+    const uint32_t* nvol_off;      // [n + 1] CSIVolumesByNodeID (CSR) ...
+    const uint32_t* nvol_plugin;   // ... as each volume's PluginID
+    const NodeRec* rec;            // the class of each row
+    const uint8_t* class_ok;       // the group's class verdicts
+    const uint8_t* base_ok;        // [n] or null: the per-node verdict without CSI
+    uint16_t* codes;               // [n] out: 0 or request << 3 | reason
+    uint8_t* node_ok;              // [n] out: base_ok && available
+    uint8_t* node_feas;            // [n] out: class_ok[cls] && node_ok
+    CsiReq req[kMaxCsiReq];
 };
 
 // Full-scan Select reduction record (one per workgroup, and per GPU shard).

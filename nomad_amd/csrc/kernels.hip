@@ -1512,6 +1512,7 @@ __global__ void __launch_bounds__(64) k_window(BatchArgs A) {
             if (A.full_out)
                 emit_placement(A, class_ok, ov, nullptr, e, it, win_row, best_score, consumed, n_filtered,
                                n_exhausted, no);
+            if (A.aside_out) *A.aside_out = a;
             pe_placement& o = stage[it & 63u];
             o.row = win_row;
             o.nodes_evaluated = consumed;
@@ -4601,6 +4602,50 @@ __global__ void __launch_bounds__(256) k_fold_feas_staged(NodeSoA s, const uint8
     }
 }
 
+// CSIVolumeChecker.isFeasible per node (CsiArgs, engine_types.h), one lane per
+// snapshot row. The request records are staged once per workgroup. A lane
+// looks the request's plugin up among its node's plugins (a handful) and, only
+// when the node runs it healthy, counts the node's volumes of that plugin
+// against MaxVolumes; the volume-level reasons come resolved in the record.
+// The first failing request in list order gives the code. The verdict is
+// folded into node_ok / node_feas, the per-node bytes every walk kernel reads,
+// so an unavailable node is one filtered node to all of them.
+__global__ void __launch_bounds__(256) k_csi_avail(CsiArgs A) {
+    __shared__ CsiReq req[kMaxCsiReq];
+    const uint32_t nr = min(A.n_req, (uint32_t)kMaxCsiReq);
+    if (threadIdx.x < nr) req[threadIdx.x] = A.req[threadIdx.x];
+    __syncthreads();
+    for (uint32_t row = blockIdx.x * 256 + threadIdx.x; row < A.n; row += gridDim.x * 256) {
+        const uint32_t pb = A.plug_off[row], pz = A.plug_off[row + 1];
+        const uint32_t vb = A.nvol_off[row], ve = A.nvol_off[row + 1];
+        uint32_t code = 0;
+        for (uint32_t q = 0; q < nr && !code; q++) {
+            const CsiReq r = req[q];
+            uint32_t reason;
+            if (!r.found) {
+                reason = PE_CSI_NOT_FOUND;
+            } else {
+                uint32_t k = pb;
+                while (k < pz && A.plug_id[k] != r.plugin) k++;
+                if (k == pz) {
+                    reason = PE_CSI_NO_PLUGIN;
+                } else if (!A.plug_healthy[k]) {
+                    reason = PE_CSI_UNHEALTHY;
+                } else {
+                    int64_t in_use = 0;   // pluginCount[vol.PluginID]
+                    for (uint32_t v = vb; v < ve; v++) in_use += A.nvol_plugin[v] == r.plugin;
+                    reason = in_use >= A.plug_max[k] ? PE_CSI_MAX_VOLUMES : r.vol_reason;
+                }
+            }
+            if (reason) code = q << 3 | reason;
+        }
+        A.codes[row] = (uint16_t)code;
+        const bool ok = code == 0 && (!A.base_ok || A.base_ok[row] != 0);
+        A.node_ok[row] = ok ? 1 : 0;
+        A.node_feas[row] = (ok && A.class_ok[A.rec[row].cls] != 0) ? 1 : 0;
+    }
+}
+
 // node_aux[row] (SweepArgs): verdict bit, affinity index (per class, or per
 // node when the affinities escape the class), spread values of the first
 // kAuxPsets properties. Built once per (job, task group) tables.
@@ -6195,6 +6240,17 @@ hipError_t pe_launch_fold_feas(const pe::NodeSoA* s, const uint8_t* class_ok, co
     if (blocks > 4096) blocks = 4096;
     if (blocks == 0) blocks = 1;
     hipLaunchKernelGGL(pe::k_fold_feas, dim3(blocks), dim3(256), 0, st, *s, class_ok, node_ok, feas);
+    return hipGetLastError();
+}
+
+hipError_t pe_launch_csi_avail(const pe::CsiArgs* a, hipStream_t st) {
+    if (a->n_req > (uint32_t)pe::kMaxCsiReq || !a->plug_off || !a->nvol_off || !a->rec || !a->class_ok || !a->codes ||
+        !a->node_ok || !a->node_feas)
+        return hipErrorInvalidValue;
+    uint32_t blocks = (a->n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (blocks == 0) blocks = 1;
+    hipLaunchKernelGGL(pe::k_csi_avail, dim3(blocks), dim3(256), 0, st, *a);
     return hipGetLastError();
 }
 

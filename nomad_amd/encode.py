@@ -13,7 +13,7 @@ from typing import Dict, List, Sequence
 import numpy as np
 
 from . import abi
-from .structs import Allocation, Job, Node
+from .structs import Allocation, CSINodePlugin, CSIVolume, CSIVolumeRequest, Job, Node
 
 MIN_DYN, MAX_DYN = 20000, 32000
 
@@ -265,6 +265,84 @@ class EncodedState:
         return t
 
 
+class EncodedCSI:
+    """pe_csi_table over a state's Interner: the nodes' CSINodePlugins, the
+    volumes, and per node the volumes CSIVolumesByNodeID yields
+    (`node_volumes`: node id -> volume ids or (namespace, id) pairs)."""
+
+    def __init__(self, nodes: Sequence[Node], volumes: Sequence[CSIVolume], node_volumes, interner: Interner):
+        I = interner.intern
+        n = len(nodes)
+        self.interner = interner
+        index = {}
+        for v, vol in enumerate(volumes):
+            index[(vol.namespace, vol.id)] = v
+            index.setdefault(vol.id, v)
+        plug_off, nvol_off, claim_off = [0], [0], [0]
+        plug_id, healthy, maxv, nvol = [], [], [], []
+        for nd in nodes:
+            for pid, p in nd.csi_node_plugins.items():
+                plug_id.append(I(pid))
+                healthy.append(int(p.healthy))
+                maxv.append(p.max_volumes)
+            plug_off.append(len(plug_id))
+            nvol.extend(index[v] for v in (node_volumes or {}).get(nd.id, ()))
+            nvol_off.append(len(nvol))
+        claim_ns, claim_job = [], []
+        for vol in volumes:
+            for h in vol.write_allocs:
+                claim_ns.append(abi.PE_NONE if h is None else I(h[0]))
+                claim_job.append(abi.PE_NONE if h is None else I(h[1]))
+            claim_off.append(len(claim_ns))
+        self.cols = {
+            "plug_off": _u32(plug_off), "plug_id": _u32(plug_id or [0]), "plug_healthy": _u8(healthy or [0]),
+            "plug_max_volumes": _i64(maxv or [0]),
+            "vol_id": _u32([I(v.id) for v in volumes] or [0]), "vol_ns": _u32([I(v.namespace) for v in volumes] or [0]),
+            "vol_plugin": _u32([I(v.plugin_id) for v in volumes] or [0]),
+            "vol_read_ok": _u8([int(v.read_schedulable) for v in volumes] or [0]),
+            "vol_write_ok": _u8([int(v.write_schedulable) for v in volumes] or [0]),
+            "vol_write_free": _u8([int(v.write_free_claims) for v in volumes] or [0]),
+            "claim_off": _u32(claim_off), "claim_ns": _u32(claim_ns or [0]), "claim_job": _u32(claim_job or [0]),
+            "node_vol_off": _u32(nvol_off), "node_vol_index": _u32(nvol or [0]),
+        }
+        t = abi.pe_csi_table()
+        t.n_nodes, t.n_volumes = n, len(volumes)
+        for name, a in self.cols.items():
+            setattr(t, name, _ptr(a, dict(abi.pe_csi_table._fields_)[name]))
+        self.table = t
+
+    def strtab(self):
+        t, k = self.interner.table()
+        self._strtab_keep = k
+        return t
+
+    def decode(self):
+        """The flattened table back as (plugins per node, volumes, volume indices
+        per node): what the engine reads, for round-trip checks."""
+        c, S = self.cols, self.interner.strs
+        n, nv = self.table.n_nodes, self.table.n_volumes
+        plugins = [{S[c["plug_id"][k]]: CSINodePlugin(bool(c["plug_healthy"][k]), int(c["plug_max_volumes"][k]))
+                    for k in range(c["plug_off"][i], c["plug_off"][i + 1])} for i in range(n)]
+        volumes = []
+        for v in range(nv):
+            holders = [None if c["claim_ns"][k] == abi.PE_NONE else (S[c["claim_ns"][k]], S[c["claim_job"][k]])
+                       for k in range(c["claim_off"][v], c["claim_off"][v + 1])]
+            volumes.append(CSIVolume(S[c["vol_id"][v]], S[c["vol_ns"][v]], S[c["vol_plugin"][v]],
+                                     bool(c["vol_read_ok"][v]), bool(c["vol_write_ok"][v]),
+                                     bool(c["vol_write_free"][v]), holders))
+        node_vols = [[int(x) for x in c["node_vol_index"][c["node_vol_off"][i]:c["node_vol_off"][i + 1]]]
+                     for i in range(n)]
+        return plugins, volumes, node_vols
+
+
+def encode_csi_requests(reqs: Sequence[CSIVolumeRequest], interner: Interner):
+    """pe_csi_request array of a task group's CSI volume requests, in list order."""
+    arr = (abi.pe_csi_request * max(1, len(reqs)))()
+    for k, r in enumerate(reqs):
+        arr[k].source, arr[k].read_only, arr[k].per_alloc = interner.intern(r.source), int(r.read_only), int(r.per_alloc)
+    return arr
+
+
 def _cidr_single(cidr: str, intern) -> int:
     """The only address of a CIDR block, interned (PE_NONE when the CIDR does
     not parse or holds more than one address)."""
@@ -384,6 +462,9 @@ class EncodedJob:
                 vol_src.append(I(src))
                 vol_ro.append(int(ro))
             g.volume_count = len(tg.host_volumes)
+            g.has_csi_volumes = int(bool(tg.csi_volumes))
+            for r in tg.csi_volumes:   # pe_set_csi_requests names them by id
+                I(r.source)
             tgs.append(g)
         pj.tg_count = len(tgs)
 

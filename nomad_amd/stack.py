@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import abi
-from .encode import EncodedJob, EncodedState, Interner
+from .encode import EncodedCSI, EncodedJob, EncodedState, Interner, encode_csi_requests
 from .structs import Allocation, Job, Node, SchedulerConfig
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -111,6 +111,8 @@ def load_engine():
             lib.pe_system_groups_metrics.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.pe_sysg_failure)),
                                                      C.POINTER(C.c_int32), C.POINTER(abi.f64p), C.POINTER(abi.f64p),
                                                      abi.u32p]
+        if hasattr(lib, "pe_set_csi"):
+            abi.bind_csi(lib)
         lib.pe_speculation_stats.restype = C.c_int
         lib.pe_speculation_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.pe_chain_wide_stats.restype = C.c_int
@@ -200,6 +202,8 @@ class SelectOptions:
     preferred_nodes: Sequence[str] = ()
     preempt: bool = False
     alloc_name: str = ""
+    # AllocSuffix of the alloc being placed: per_alloc CSI sources take "[alloc_index]"
+    alloc_index: Optional[int] = None
 
 
 def _core_ids(mask) -> List[int]:
@@ -278,6 +282,7 @@ class _Stack:
         self.job: Optional[EncodedJob] = None
         self.nodes: List[Node] = []
         self.limit = None
+        self.csi: Optional[EncodedCSI] = None
 
     def close(self):
         if self._h:
@@ -412,11 +417,40 @@ class _Stack:
     # -- scheduler.State snapshot -------------------------------------------
     def SetState(self, nodes: Sequence[Node], allocs: Sequence[Allocation] = ()):
         self.nodes = list(nodes)
+        self.csi = None   # the table goes with the snapshot
         self.state = EncodedState(nodes, allocs, Interner())
         t = self.state.strtab()
         self._check(self._fn("set_state")(self._h, C.byref(t), C.byref(self.state.node_table),
                                           C.byref(self.state.alloc_table)))
         return self.state
+
+    # -- CSI volumes (CSIVolumeChecker, feasible.go:209-337) ---------------------
+    def SetCSI(self, volumes, node_volumes=None):
+        """The snapshot's CSI state (pe_set_csi): `volumes` CSIVolume objects,
+        `node_volumes` node id -> ids of the volumes CSIVolumesByNodeID yields;
+        the plugins come from Node.csi_node_plugins. None drops the table.
+        SetState, UpdateNodes and UpdateAllocs drop it too."""
+        if volumes is None:
+            self._check(self._lib.pe_set_csi(self._h, None, None))
+            self.csi = None
+            return None
+        self.csi = EncodedCSI(self.state.nodes, list(volumes), node_volumes, self.state.interner)
+        t = self.csi.strtab()
+        self._check(self._lib.pe_set_csi(self._h, C.byref(t), C.byref(self.csi.table)))
+        return self.csi
+
+    def CSICheck(self, tg) -> np.ndarray:
+        """pe_csi_check: the availability code of every snapshot row for `tg`
+        (0, or request index << 3 | reason)."""
+        out = np.zeros(max(1, len(self.state.nodes)), dtype=np.uint16)
+        self._check(self._lib.pe_csi_check(self._h, self._tg_index(tg), out.ctypes.data_as(abi.u16p)))
+        return out[:len(self.state.nodes)]
+
+    def CSIAllocIndex(self, tg, idx: int):
+        self._check(self._lib.pe_csi_alloc_index(self._h, self._tg_index(tg), int(idx)))
+
+    def csi_last_ms(self) -> float:
+        return float(self._lib.pe_csi_last_ms(self._h))
 
     def SetStateColumnar(self, cs):
         """Snapshot from a synth_columnar.ColumnarState (no per-node Python objects)."""
@@ -466,6 +500,11 @@ class _Stack:
         self._job = job
         t = self.job.strtab()
         self._check(self._fn("set_job")(self._h, C.byref(t), C.byref(self.job.job)))
+        if self._p == "pe_":   # the groups' CSI requests follow the job (pe_set_csi_requests)
+            for i, g in enumerate(job.task_groups):
+                if g.csi_volumes:
+                    reqs = encode_csi_requests(g.csi_volumes, self.state.interner)   # (sources interned with the job)
+                    self._check(self._lib.pe_set_csi_requests(self._h, i, reqs, len(g.csi_volumes)))
 
     def SetNodes(self, nodes_in_visit_order) -> int:
         """`nodes_in_visit_order`: Node objects / IDs / rows, already shuffled."""
@@ -501,6 +540,8 @@ class _Stack:
                 keep.append(pref)
                 opts.preferred_rows, opts.preferred_count = pref.ctypes.data_as(abi.u32p), len(pref)
             opts.preempt = int(options.preempt)
+        if options is not None and options.alloc_index is not None and self._p == "pe_":
+            self._check(self._lib.pe_csi_alloc_index(self._h, self._tg_index(tg), int(options.alloc_index)))
         out = abi.pe_ranked_node()
         self._check(self._fn("select")(self._h, self._tg_index(tg), C.byref(opts), C.byref(out)))
         r = RankedNode.from_c(out, self.nodes, self._full_preempted(0, out))

@@ -51,6 +51,13 @@ class DeviceGroup:
 
 
 @dataclass
+class CSINodePlugin:
+    """Node.CSINodePlugins[plugin id] (structs.CSIInfo): Healthy and NodeInfo.MaxVolumes."""
+    healthy: bool = True
+    max_volumes: int = (1 << 63) - 1
+
+
+@dataclass
 class Node:
     id: str
     name: str = "foobar"
@@ -80,6 +87,8 @@ class Node:
     drain: bool = False
     eligible: bool = True
     computed_class: str = ""
+    # CSINodePlugins by plugin id; not part of the computed class (node_class.go:43-50)
+    csi_node_plugins: Dict[str, CSINodePlugin] = field(default_factory=dict)
 
     def node_addresses(self) -> List[Tuple[str, str, str]]:
         """NodeNetworks addresses (alias, address, ReservedPorts spec) in node order."""
@@ -154,6 +163,28 @@ class Allocation:
 
 
 @dataclass
+class CSIVolume:
+    """structs.CSIVolume as CSIVolumeChecker reads it (feasible.go:261-337): the
+    three schedulability predicates evaluated by the caller, and the holders of
+    WriteAllocs as (namespace, job id), None for an alloc the state no longer has."""
+    id: str
+    namespace: str = "default"
+    plugin_id: str = ""
+    read_schedulable: bool = True
+    write_schedulable: bool = True
+    write_free_claims: bool = True
+    write_allocs: List[Optional[Tuple[str, str]]] = field(default_factory=list)
+
+
+@dataclass
+class CSIVolumeRequest:
+    """A VolumeRequest of type csi (structs.VolumeRequest)."""
+    source: str
+    read_only: bool = False
+    per_alloc: bool = False
+
+
+@dataclass
 class Constraint:
     ltarget: str = ""
     rtarget: str = ""
@@ -220,6 +251,8 @@ class TaskGroup:
     tasks: List[Task] = field(default_factory=list)
     network: Optional[NetworkResource] = None
     host_volumes: List[tuple] = field(default_factory=list)   # (source, read_only)
+    # CSI volume requests, in the order that stands in for the reference's map order
+    csi_volumes: List[CSIVolumeRequest] = field(default_factory=list)
 
 
 @dataclass

@@ -1,0 +1,139 @@
+"""CSI probe: what task groups with CSI volumes cost on the
+device path, at 10k nodes (cluster_c2) and 100k nodes (cluster_c4) with three
+requests, one of them per_alloc.
+
+  (a) k_csi_avail alone, by the engine's HIP events (pe_csi_last_ms, recorded
+      with PE_CSI_TIME=1, which the probe sets on the handle it times): every
+      repetition changes the alloc index, so pe_csi_check launches the kernel
+      again and waits for the code column;
+  (b) per-Select time, host clock around pe_select (which ends in a device
+      synchronise), on three handles of one build that alternate: the job
+      without CSI, the job with CSI and a fixed alloc index (no k_csi_avail
+      launch per Select), and the job with CSI and a new alloc index per
+      Select (one launch per placement). Every Select is followed by its
+      Commit (not timed). All three run the non-speculative path: the probe
+      sets PE_SPECULATE=0 before it creates a handle.
+
+Each node runs each of the three plugins with probability 0.97, healthy with
+probability 0.97, so about one node in six is unavailable, most windows hold
+unavailable nodes and some Selects take the second run of the stop rule; Selects that the
+engine hands back (PE_EUNSUPPORTED, the resume corner) are counted, not timed.
+
+    python tools/csi_probe.py [--reps 20] [--selects 200] [--small] [--out profiles/csi/probe.json]
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+os.environ["PE_SPECULATE"] = "0"
+sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
+from nomad_amd import synth  # noqa: E402
+from nomad_amd.stack import GenericStack, SelectOptions, Unsupported  # noqa: E402
+from nomad_amd.structs import CSINodePlugin, CSIVolume, CSIVolumeRequest  # noqa: E402
+
+REQS = [CSIVolumeRequest("data"), CSIVolumeRequest("scratch", per_alloc=True), CSIVolumeRequest("conf", read_only=True)]
+
+
+def csi_state(nodes, n_alloc_names, seed):
+    rng = np.random.Generator(np.random.PCG64(seed))
+    volumes = [CSIVolume("data", "default", "p0"), CSIVolume("conf", "default", "p2")]
+    volumes += [CSIVolume("scratch[%d]" % i, "default", "p1") for i in range(n_alloc_names)]
+    volumes += [CSIVolume("other-%d" % i, "default", "p%d" % (i % 3)) for i in range(6)]
+    node_volumes = {}
+    for nd in nodes:
+        for p in range(3):
+            if rng.random() < 0.97:
+                nd.csi_node_plugins["p%d" % p] = CSINodePlugin(bool(rng.random() < 0.97), 8)
+        k = int(rng.integers(0, 3))
+        if k:
+            node_volumes[nd.id] = ["other-%d" % int(i) for i in rng.integers(0, 6, k)]
+    return volumes, node_volumes
+
+
+def handle(nodes, allocs, job, perm, volumes=None, node_volumes=None):
+    st = GenericStack()
+    st.SetState(nodes, allocs)
+    if volumes is not None:
+        st.SetCSI(volumes, node_volumes)
+    st.SetJob(job)
+    st.SetNodes(perm)
+    return st
+
+
+def measure(name, nodes, allocs, job, reps, selects):
+    perm = synth.shuffle(len(nodes), 5)
+    volumes, node_volumes = csi_state(nodes, max(selects, reps) + 1, seed=6)
+    csi = copy.deepcopy(job)
+    csi.task_groups[0].csi_volumes = list(REQS)
+    st_plain = handle(nodes, allocs, job, perm)
+    os.environ["PE_CSI_TIME"] = "1"     # read at create: only st_time records the events
+    st_time = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    del os.environ["PE_CSI_TIME"]
+    st_fixed = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    st_alloc = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+
+    kernel_ms = []
+    for r in range(reps + 2):
+        st_time.CSIAllocIndex(0, r + 1)
+        codes = st_time.CSICheck(0)
+        if r >= 2:
+            kernel_ms.append(st_time.csi_last_ms())
+    st_time.close()
+    unavailable = float(np.count_nonzero(codes)) / len(nodes)
+
+    times = {"plain": [], "csi": [], "csi_per_alloc": []}
+    handed_back = {"csi": 0, "csi_per_alloc": 0}
+    for k in range(selects):
+        for key, st, opts in (("plain", st_plain, None), ("csi", st_fixed, None),
+                              ("csi_per_alloc", st_alloc, SelectOptions(alloc_index=k))):
+            t0 = time.perf_counter()
+            try:
+                r = st.Select(0, opts)
+            except Unsupported:
+                handed_back[key] += 1
+                st.SetCursor((st.GetCursor()[0] + 1) % len(nodes), st.GetCursor()[1])
+                continue
+            dt = time.perf_counter() - t0
+            if k >= 5:
+                times[key].append(dt * 1e6)
+            if r is not None:
+                st.Commit(0, r.row)
+
+    def stats(v):
+        a = np.asarray(v)
+        return {"n": int(a.size), "median_us": float(np.median(a)), "p10_us": float(np.percentile(a, 10)),
+                "p90_us": float(np.percentile(a, 90))} if a.size else {"n": 0}
+    out = {"nodes": len(nodes), "requests": len(REQS), "unavailable_fraction": unavailable,
+           "k_csi_avail_ms": {"reps": len(kernel_ms), "median": float(np.median(kernel_ms)),
+                              "min": float(np.min(kernel_ms)), "max": float(np.max(kernel_ms))},
+           "select_us": {k: stats(v) for k, v in times.items()}, "handed_back": handed_back}
+    print(name, json.dumps(out))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--selects", type=int, default=200)
+    ap.add_argument("--small", action="store_true", help="1/10 of the node counts (rehearsal)")
+    ap.add_argument("--out", default="profiles/csi/probe.json")
+    a = ap.parse_args()
+    scale = 10 if a.small else 1
+    res = {"tool": "tools/csi_probe.py", "speculate": 0}
+    nodes, allocs = synth.cluster_c2(10000 // scale, seed=42)
+    res["cluster_c2"] = measure("cluster_c2", nodes, allocs, synth.job_c2(a.selects), a.reps, a.selects)
+    nodes, allocs = synth.cluster_c4(100000 // scale, seed=11)
+    res["cluster_c4"] = measure("cluster_c4", nodes, allocs, synth.job_c2(a.selects), a.reps, a.selects)
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
