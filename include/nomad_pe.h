@@ -1011,12 +1011,14 @@ int pe_set_csi(pe_stack* s, const pe_strtab* strs, const pe_csi_table* table);
  * reason. At most PE_MAX_CSI_REQ. A group with has_csi_volumes set and no
  * table or no requests is refused (PE_EUNSUPPORTED "CSI volumes"). With both,
  * pe_select (plain: no preferred nodes, no Preempt, pe_set_metrics off) and
- * pe_system_place place it; every other placing call refuses it before
+ * pe_system_place place it, and so does pe_place_csi (below), the count loop
+ * for such a group; every other placing call refuses it before
  * anything changes. On a generic stack pe_select may itself return
  * PE_EUNSUPPORTED with the cursor, the memo and the plan untouched: the
  * reference would resume its walk past an unavailable node of a class already
  * memoised eligible (select.go:59-67), or a full pass (a group with affinities
- * or spreads) ends at such a node; the engine leaves both to the chain. */
+ * or spreads) ends at such a node; the engine leaves both to the chain
+ * (pe_place_csi answers the first of the two). */
 #define PE_MAX_CSI_REQ 16
 typedef struct pe_csi_request {
     uint32_t source;      /* VolumeRequest.Source (str id) */
@@ -1045,6 +1047,43 @@ int pe_csi_check(pe_stack* s, uint32_t tg_index, uint16_t* codes);
  * events that are recorded only with PE_CSI_TIME=1 in the environment at
  * pe_stack_create; 0 otherwise. */
 double pe_csi_last_ms(pe_stack* s);
+/* computePlacements' loop for `count` fresh placements of a task group with CSI
+ * requests: for i in [0, count): SetVolumes(alloc name with index alloc_idx[i]),
+ * Select, AppendAlloc; ends at the first nil option, as pe_place does.
+ * alloc_idx == NULL: every placement takes the index that pe_csi_alloc_index holds.
+ * Afterwards the cursor, the memo (pe_get_eligibility), the plan and the records
+ * out[0..*placed] (the failed Select's too, if any) are what the per-placement
+ * sequence pe_csi_alloc_index / pe_select / pe_commit would leave if the
+ * reference chain answered the Selects that pe_select hands back: a stop while
+ * LimitIterator holds skipped options resumes past the node here
+ * (select.go:35-67). One launch of the loop kernel and one synchronisation per
+ * call; one k_csi_avail launch per distinct set of resolved request records
+ * among the call's alloc indices, at most PE_MAX_CSI_SETS.
+ * On a group without CSI requests the call is pe_place. PE_EUNSUPPORTED, with
+ * the cursor, the limit, the memo and the plan untouched: pe_set_metrics on, a
+ * handle over several devices, a system stack, a preempting stack, computed
+ * classes whose nodes differ in the group's checks, a group that runs full
+ * passes (affinities, spreads, distinct_property, a latched limit), whatever
+ * pe_place refuses, more than PE_MAX_CSI_SETS distinct record sets, and a
+ * count beyond the overlay of one launch. */
+#define PE_MAX_CSI_SETS 8
+int pe_place_csi(pe_stack* s, uint32_t tg_index, uint32_t count, const uint32_t* alloc_idx, pe_ranked_node* out,
+                 uint32_t* placed);
+/* k_csi_avail launches of the handle so far (pe_select's and pe_place_csi's). */
+uint64_t pe_csi_avail_launches(const pe_stack* s);
+/* Measurement aid: device time in ms of the last pe_place_csi's k_csi_first
+ * (ms2[0]) and k_csi_loop (ms2[1]), recorded only with PE_CSI_TIME=1;
+ * PE_ESTATE otherwise. */
+int pe_csi_place_ms(pe_stack* s, double* ms2);
+/* LimitIterator + MaxScoreIterator (select.go:35-116) over a source with
+ * transient nils, the fold pe_place_csi's kernel steps, exposed for tests;
+ * needs no device. Item i of the stream is an option scoring scores[i]
+ * (kind[i] == 0) or a nil after which the source goes on (kind[i] == 1); past
+ * item n - 1 the source returns nil for ever. Outputs: the winner's item index
+ * (-1 none), LimitIterator.seen, the items pulled, and whether the Select ended
+ * at a nil Next rather than at seen == limit. */
+int pe_csi_limit_fold(const double* scores, const uint8_t* kind, uint32_t n, uint32_t limit, int32_t* winner,
+                      uint32_t* seen, uint32_t* consumed, uint32_t* ended_nil);
 /* Host-side constraint semantics used for pre-resolution (checkConstraint,
  * feasible.go:785-820), exposed for known-answer tests; needs no device.
  * l_state / r_state: 0 nil (unknown ${...} target), 1 found, 2 missing ("", false). */

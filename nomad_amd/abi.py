@@ -229,6 +229,25 @@ def bind_csi(lib):
     lib.pe_csi_check.argtypes = [H, C.c_uint32, u16p]
     lib.pe_csi_last_ms.restype = C.c_double
     lib.pe_csi_last_ms.argtypes = [H]
+    if not hasattr(lib, "pe_place_csi"):   # present or absent behind one ABI version (an A/B library)
+        return lib
+    lib.pe_place_csi.restype = C.c_int
+    lib.pe_place_csi.argtypes = [H, C.c_uint32, C.c_uint32, u32p, C.POINTER(pe_ranked_node), u32p]
+    lib.pe_csi_avail_launches.restype = C.c_uint64
+    lib.pe_csi_avail_launches.argtypes = [H]
+    lib.pe_csi_place_ms.restype = C.c_int
+    lib.pe_csi_place_ms.argtypes = [H, f64p]
+    bind_csi_limit_fold(lib)
+    return lib
+
+
+PE_MAX_CSI_SETS = 8
+
+
+def bind_csi_limit_fold(lib):
+    """pe_csi_limit_fold: stateless, needs no device (any loaded libnomadpe.so)."""
+    lib.pe_csi_limit_fold.restype = C.c_int
+    lib.pe_csi_limit_fold.argtypes = [f64p, u8p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), u32p, u32p, u32p]
     return lib
 
 
@@ -275,6 +294,7 @@ ENGINE_SYMBOLS = [
     "pe_inplace_update_preempt", "pe_inplace_update_preempted",
     "pe_inplace_update_metrics", "pe_inplace_metrics",
     "pe_inplace_update_spread", "pe_inplace_spread_ms",
+    "pe_place_csi", "pe_csi_avail_launches", "pe_csi_place_ms", "pe_csi_limit_fold",
 ]
 
 

@@ -41,6 +41,7 @@
 #include "gomath_dev.h"
 #include "gosort.h"
 #include "launchers.h"
+#include "csi_limit.h"
 
 // ---- RCCL, bound at run time ------------------------------------------------
 // The engine's collectives (pe_comm_init / pe_place_sharded, the one-handle
@@ -467,6 +468,10 @@ struct TgPlan {
     bool csi_dirty = true;             // requests, index, table or the group's tables changed
     DevMem csi_base_ok;
     PinnedMem csi_codes;               // mapped: the kernel stores the codes where the host reads them
+    // pe_place_csi: one code column per distinct record set of the call (device
+    // memory, nothing copied back), the column of each placement, the class
+    // states of the stop rule and F[c]
+    DevMem csi_cols, csi_set_of, csi_cls_state, csi_first;
 };
 
 // A group with has_csi_volumes is refused with this text until it has both a
@@ -861,6 +866,9 @@ struct pe_stack {
     bool csi_scope = false;            // inside pe_select / pe_system_place: the calls that place a CSI group
     hipEvent_t ev_csi0 = nullptr, ev_csi1 = nullptr;   // around the last k_csi_avail
     bool csi_timed = false;
+    uint64_t csi_avail_launches = 0;   // k_csi_avail launches of the handle (pe_csi_avail_launches)
+    hipEvent_t ev_csip[3] = {nullptr, nullptr, nullptr};   // PE_CSI_TIME: before k_csi_first, between, after k_csi_loop
+    bool csip_timed = false;
 
     // The unchanged SystemScheduler caller (scheduler_system.go:289-302):
     // SetNodes([node]) then Select for every node. From the third single-node
@@ -4128,24 +4136,15 @@ size_t pset_lds_bytes(const pe::TgTables& t) {
     return b <= kPsetLdsBudget ? b : 0u;
 }
 
-// The request records of a CSI group against the snapshot's volumes, and one
-// k_csi_avail launch: the code column, stored straight into mapped page-locked
-// memory (no copy back, no wait here), and the group's node_ok / node_feas with
-// the availability folded in. Runs after the group's tables are built and again
-// when the requests, the alloc index or the table change.
-int csi_refresh(pe_stack* s, TgPlan& g) {
-    const uint32_t n = (uint32_t)s->nodes.size();
-    g.csi_dirty = false;
-    if (!n) return PE_OK;
-    pe::CsiArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.n = n;
-    A.n_req = (uint32_t)g.csi_reqs.size();
-    for (uint32_t q = 0; q < A.n_req; q++) {
+// A group's request records against the snapshot's volumes for alloc index
+// `idx`: what isFeasible reads that does not depend on the node.
+static void csi_resolve(pe_stack* s, const TgPlan& g, uint32_t idx, pe::CsiReq* req) {
+    std::memset(req, 0, sizeof(pe::CsiReq) * pe::kMaxCsiReq);
+    for (uint32_t q = 0; q < (uint32_t)g.csi_reqs.size() && q < (uint32_t)pe::kMaxCsiReq; q++) {
         const pe_csi_request& r = g.csi_reqs[q];
-        pe::CsiReq& d = A.req[q];
+        pe::CsiReq& d = req[q];
         // SetVolumes (feasible.go:230-249): a per_alloc source takes AllocSuffix(allocName)
-        const uint32_t src = r.per_alloc ? s->lookup(s->S(r.source) + "[" + std::to_string(g.csi_idx) + "]") : r.source;
+        const uint32_t src = r.per_alloc ? s->lookup(s->S(r.source) + "[" + std::to_string(idx) + "]") : r.source;
         const auto it = src == PE_NONE ? s->csi.by_id.end() : s->csi.by_id.find({s->job_ns, src});
         if (it == s->csi.by_id.end()) continue;   // found = 0
         const uint32_t v = it->second;
@@ -4162,6 +4161,22 @@ int csi_refresh(pe_stack* s, TgPlan& g) {
                     d.vol_reason = PE_CSI_IN_USE;
         }
     }
+}
+
+// The request records of a CSI group against the snapshot's volumes, and one
+// k_csi_avail launch: the code column, stored straight into mapped page-locked
+// memory (no copy back, no wait here), and the group's node_ok / node_feas with
+// the availability folded in. Runs after the group's tables are built and again
+// when the requests, the alloc index or the table change.
+int csi_refresh(pe_stack* s, TgPlan& g) {
+    const uint32_t n = (uint32_t)s->nodes.size();
+    g.csi_dirty = false;
+    if (!n) return PE_OK;
+    pe::CsiArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.n = n;
+    A.n_req = (uint32_t)g.csi_reqs.size();
+    csi_resolve(s, g, g.csi_idx, A.req);
     {
         const int rc = flush_fold(s);   // the class table reaches the device with the group's fold
         if (rc) return rc;
@@ -4188,6 +4203,7 @@ int csi_refresh(pe_stack* s, TgPlan& g) {
         HIP_TRY(s, hipEventRecord(s->ev_csi0, s->stream));
     }
     HIP_TRY_STATE(s, pe_launch_csi_avail(&A, s->stream));
+    s->csi_avail_launches++;
     if (s->tun.csi_time) {
         HIP_TRY(s, hipEventRecord(s->ev_csi1, s->stream));
         s->csi_timed = true;
@@ -5230,6 +5246,8 @@ void pe_stack_destroy(pe_stack* s) {
     if (s->ev2) (void)hipEventDestroy(s->ev2);
     if (s->ev_csi0) (void)hipEventDestroy(s->ev_csi0);
     if (s->ev_csi1) (void)hipEventDestroy(s->ev_csi1);
+    for (hipEvent_t ev : s->ev_csip)
+        if (ev) (void)hipEventDestroy(ev);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -10722,6 +10740,241 @@ int pe_place(pe_stack* s, uint32_t tgi, uint32_t count, pe_ranked_node* out, uin
         for (uint32_t k = 0; k < p && k < count; k++)
             kid_log(s, 1, tgi, out[k].row, preempted_list(s, k, out[k]), out[k].n_preempted);
     return rc;
+}
+
+// ---- pe_place_csi: the count loop of a group with CSI requests -------------------
+// computePlacements' loop (generic_sched.go:552-627) for a group whose Selects
+// pass an availability checker: per placement SetVolumes with the alloc's name
+// index, Select, AppendAlloc. One k_csi_avail launch per distinct record set of
+// the call (codes only, into device columns), k_csi_first for the stop rule's
+// F[c], and k_csi_loop, which answers every Select including those pe_select
+// hands back (a stop while LimitIterator holds skipped options).
+static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32_t* alloc_idx, pe_ranked_node* out,
+                         uint32_t* placed) {
+    // refusals, all before anything changes
+    int rc = csi_refuse(s, nullptr);
+    if (rc) return rc;
+    if (s->cfg.stack_kind != PE_STACK_GENERIC)
+        return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes on a system stack (pe_select and pe_system_place place them)");
+    if (s->cfg.preempt)
+        return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes on a preempting stack (the loop retries a nil Select with Preempt)");
+    {
+        TgPlan& g0 = *s->tgs[tgi];
+        if (tg_full_scan(s, g0) || s->limit >= 0x7FFFFFFFu)
+            return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes in a group that runs full passes (affinities, spreads or a latched limit)");
+    }
+    const int hash_bits = hash_bits_for(count, false, 0);
+    if (((uint64_t)1 << hash_bits) < 2ull * std::max<uint32_t>(count, 1))   // (64 bits: no wrap for a huge count)
+        return s->fail(PE_EUNSUPPORTED, "pe_place_csi: count exceeds what the overlay of one launch holds");
+    rc = spec_flush(s);
+    if (rc) return rc;
+    HIP_TRY(s, hipSetDevice(s->device));
+    rc = prepare_tg(s, tgi, s->visit, s->offset);   // (pe_place's own refusals among them)
+    if (rc) return rc;
+    TgPlan& g = *s->tgs[tgi];
+    if (!g.escaped && !g.nonuniform.empty())
+        return s->fail(PE_EUNSUPPORTED, "CSI volumes with computed classes whose nodes differ in the group's checks");
+    if (!g.psets.empty() || g.psets_dynamic)
+        return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes in a group that runs full passes (distinct_property)");
+    if (g.md_on)
+        return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes with group networks on multi-device nodes");
+    if (!count) return PE_OK;
+    const uint32_t n_rows = (uint32_t)s->nodes.size(), m = (uint32_t)s->visit.size();
+    // the distinct record sets of the call, and each placement's column
+    struct RecSet { pe::CsiReq req[pe::kMaxCsiReq]; };
+    std::vector<RecSet> sets;
+    std::vector<uint8_t> set_of(count, 0);
+    {
+        bool per_alloc = false;
+        for (const pe_csi_request& r : g.csi_reqs) per_alloc = per_alloc || r.per_alloc;
+        std::map<uint32_t, uint8_t> by_idx;
+        for (uint32_t i = 0; i < count; i++) {
+            const uint32_t idx = alloc_idx && per_alloc ? alloc_idx[i] : g.csi_idx;
+            auto it = by_idx.find(idx);
+            if (it == by_idx.end()) {
+                RecSet rs;
+                csi_resolve(s, g, idx, rs.req);
+                size_t k = 0;
+                while (k < sets.size() && std::memcmp(sets[k].req, rs.req, sizeof(rs.req)) != 0) k++;
+                if (k == sets.size()) {
+                    if (sets.size() == (size_t)pe::kMaxCsiSets)
+                        return s->fail(PE_EUNSUPPORTED, "pe_place_csi: more than 8 distinct CSI record sets in one call");
+                    sets.push_back(rs);
+                }
+                it = by_idx.emplace(idx, (uint8_t)k).first;
+            }
+            set_of[i] = it->second;
+        }
+    }
+    // ---- nothing is refused from here on ----
+    s->gen++;
+    s->metrics_valid = false;
+    const uint32_t start = s->offset;
+    if (!m) {   // SetNodes([]): a nil Select
+        std::memset(&out[0], 0, sizeof(out[0]));
+        out[0].row = -1;
+        s->offset = 0;
+        return PE_OK;
+    }
+    elig_resolve(s);   // the memo as the earlier Selects left it
+    pe::CsiLoopArgs C;
+    std::memset(&C, 0, sizeof(C));
+    {
+        if (s->job_memo.size() != s->ncls) s->job_memo.assign(s->ncls, -1);
+        const std::vector<int8_t>& st = elig_tg(s, g.name).st;   // -1 unknown / 0 ineligible / 1 eligible
+        std::vector<uint8_t> cls_state(std::max<uint32_t>(s->ncls, 1), (uint8_t)pe::kCsiClsNever);
+        for (uint32_t c = 0; c < s->ncls && !g.escaped; c++) {
+            if (st[c] == 1) cls_state[c] = pe::kCsiClsEligible;
+            else if (st[c] == -1 && (s->job_escaped || s->job_memo[c] == 1)) cls_state[c] = pe::kCsiClsOpen;
+        }
+        HIP_TRY(s, upload_s(s, g.csi_cls_state, cls_state));
+        HIP_TRY(s, upload_s(s, g.csi_set_of, set_of));
+        HIP_TRY(s, g.csi_first.ensure(sizeof(uint32_t) * std::max<uint32_t>(s->ncls, 1)));
+        HIP_TRY(s, g.csi_cols.ensure(sizeof(uint16_t) * (size_t)n_rows * sets.size()));
+    }
+    C.codes = g.csi_cols.as<uint16_t>();
+    C.n_rows = n_rows;
+    C.n_sets = (uint32_t)sets.size();
+    C.set_of = g.csi_set_of.as<uint8_t>();
+    C.cls_state = g.csi_cls_state.as<uint8_t>();
+    C.ncls = s->ncls;
+    C.escaped = g.escaped ? 1u : 0u;
+    // a job with escaped constraints: the group's per-node verdict without CSI is the job checks (build_tables)
+    C.job_ok = s->job_escaped && !g.escaped ? g.csi_base_ok.as<uint8_t>() : nullptr;
+    C.first = g.csi_first.as<uint32_t>();
+    {
+        const int frc = flush_fold(s);   // the class table reaches the device with the group's fold
+        if (frc) return frc;
+    }
+    for (size_t k = 0; k < sets.size(); k++) {
+        pe::CsiArgs V;
+        std::memset(&V, 0, sizeof(V));
+        V.n = n_rows;
+        V.n_req = (uint32_t)g.csi_reqs.size();
+        std::memcpy(V.req, sets[k].req, sizeof(V.req));
+        V.plug_off = s->csi.plug_off.as<uint32_t>();
+        V.plug_id = s->csi.plug_id.as<uint32_t>();
+        V.plug_healthy = s->csi.plug_healthy.as<uint8_t>();
+        V.plug_max = s->csi.plug_max.as<int64_t>();
+        V.nvol_off = s->csi.nvol_off.as<uint32_t>();
+        V.nvol_plugin = s->csi.nvol_plugin.as<uint32_t>();
+        V.rec = soa_of(s).rec;
+        V.class_ok = g.class_ok.as<uint8_t>();
+        V.codes = g.csi_cols.as<uint16_t>() + k * (size_t)n_rows;
+        HIP_TRY_STATE(s, pe_launch_csi_codes(&V, s->stream));
+        s->csi_avail_launches++;
+    }
+    pe::BatchArgs A = batch_args(s, g);
+    // the verdict without CSI: class_ok[cls] && the column k_csi_avail folds into (never the folded bytes)
+    A.tg.node_feas = nullptr;
+    A.tg.node_ok = g.csi_base_ok.as<uint8_t>();
+    A.hash_bits = hash_bits;
+    A.packed_overlay = packed_kbits(s, 1u << hash_bits, false);
+    HIP_TRY(s, upload_visit(s, s->visit));
+    A.perms = s->d_visit.as<uint32_t>();
+    A.n_visit = m;
+    A.count = count;
+    A.offset0 = start % m;
+    A.commit = 1;
+    A.writeback = 1;
+    HIP_TRY(s, s->h_place_out.ensure(sizeof(pe_ranked_node) * (size_t)count));
+    HIP_TRY(s, s->h_place_status.ensure(16));
+    A.full_out = s->h_place_out.dev<pe_ranked_node>();
+    A.eval_status = s->h_place_status.dev<uint32_t>();
+    if (!A.full_out || !A.eval_status) return s->fail(PE_EHIP, "mapped result buffers unavailable");
+    const bool timed = s->tun.csi_time;
+    if (timed)
+        for (auto& ev : s->ev_csip)
+            if (!ev) HIP_TRY(s, hipEventCreate(&ev));
+    HIP_TRY(s, hipMemsetAsync(g.csi_first.p, 0xFF, sizeof(uint32_t) * std::max<uint32_t>(s->ncls, 1), s->stream));
+    if (timed) HIP_TRY(s, hipEventRecord(s->ev_csip[0], s->stream));
+    if (!g.escaped) HIP_TRY_STATE(s, pe_launch_csi_first(&A, &C, s->stream));
+    if (timed) HIP_TRY(s, hipEventRecord(s->ev_csip[1], s->stream));
+    HIP_TRY_STATE(s, pe_launch_csi_loop(&A, &C, s->stream));
+    if (timed) {
+        HIP_TRY(s, hipEventRecord(s->ev_csip[2], s->stream));
+        s->csip_timed = true;
+    }
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    uint32_t st2[3];
+    std::memcpy(st2, const_cast<const uint32_t*>(s->h_place_status.as<uint32_t>()), sizeof(st2));
+    if (st2[2]) return s->fail(PE_EINTERNAL, "k_csi_loop: the LimitIterator fold passed its event bound (evaluation stopped)");
+    const uint32_t p = std::min(st2[0], count), got = std::min(count, p + 1);
+    std::memcpy(out, s->h_place_out.as<pe_ranked_node>(), sizeof(pe_ranked_node) * got);
+    for (uint32_t i = 0; i < p; i++) plan_of(s).emplace_back(g.name, (uint32_t)out[i].row);
+    s->offset = st2[1];
+    // the eligibility span of each placement's consumed window (as csi_select)
+    uint32_t cur = start % m;
+    for (uint32_t i = 0; i < got; i++) {
+        elig_log_span(s, tgi, cur, out[i].nodes_evaluated);
+        cur = out[i].new_offset;
+    }
+    // the alloc index the last Select's SetVolumes left
+    if (alloc_idx) {
+        const uint32_t last = alloc_idx[got - 1];
+        if (last != g.csi_idx) {
+            g.csi_idx = last;
+            for (const pe_csi_request& r : g.csi_reqs)
+                if (r.per_alloc) g.csi_dirty = true;
+        }
+    }
+    if (placed) *placed = p;
+    if (g.ask.cores > 0)
+        for (uint32_t k = 0; k < p; k++) core_record(s, g, out[k].row, true, out[k].reserved_cores);
+    if (p) invalidate_job_distinct(s, tgi);
+    for (size_t k = 0; k < s->tgs.size(); k++)
+        if (k != tgi && s->tgs[k]->name == g.name) return build_collisions(s);
+    return PE_OK;
+}
+
+int pe_place_csi(pe_stack* s, uint32_t tgi, uint32_t count, const uint32_t* alloc_idx, pe_ranked_node* out,
+                 uint32_t* placed) {
+    if (!s || (!out && count)) return PE_EINVAL;
+    if (placed) *placed = 0;
+    // a group without CSI requests: the call is pe_place (a group that has
+    // them but no table is refused there as pe_select refuses it)
+    if (!s->have_job || tgi >= s->tgs.size() || !csi_active(*s->tgs[tgi])) return pe_place(s, tgi, count, out, placed);
+    PE_FLUSH_RESET(s);
+    CsiScope csi_scope_(s);
+    s->pre_overflow.clear();
+    return place_csi_one(s, tgi, count, alloc_idx, out, placed);
+}
+
+uint64_t pe_csi_avail_launches(const pe_stack* s) { return s ? s->csi_avail_launches : 0; }
+
+int pe_csi_place_ms(pe_stack* s, double* ms2) {
+    if (!s || !ms2) return PE_EINVAL;
+    if (!s->csip_timed) return PE_ESTATE;
+    float a = 0, b = 0;
+    if (hipEventSynchronize(s->ev_csip[2]) != hipSuccess ||
+        hipEventElapsedTime(&a, s->ev_csip[0], s->ev_csip[1]) != hipSuccess ||
+        hipEventElapsedTime(&b, s->ev_csip[1], s->ev_csip[2]) != hipSuccess)
+        return s->fail(PE_EHIP, "pe_csi_place_ms: event timing unavailable");
+    ms2[0] = a;
+    ms2[1] = b;
+    return PE_OK;
+}
+
+// The fold of csi_limit.h over a recorded stream (stateless, no device): item
+// i is an option with scores[i] (kind 0) or a transient nil (kind 1); after
+// item n - 1 the source returns nil for ever.
+int pe_csi_limit_fold(const double* scores, const uint8_t* kind, uint32_t n, uint32_t limit, int32_t* winner,
+                      uint32_t* seen, uint32_t* consumed, uint32_t* ended_nil) {
+    if ((n && (!scores || !kind)) || !winner || !seen || !consumed || !ended_nil) return PE_EINVAL;
+    pe::CsiLimit L;
+    bool done = pe::csi_limit_init(L, limit);
+    uint32_t used = 0;
+    while (!done && used < n) {
+        done = pe::csi_limit_step(L, kind[used] ? pe::kCsiNil : pe::kCsiOption, scores[used], (int32_t)used);
+        used++;
+    }
+    for (int t = 0; t < pe::kCsiTailEvents && !done; t++) done = pe::csi_limit_step(L, pe::kCsiNil, 0.0, -1);
+    if (!done) return PE_EINTERNAL;   // the bound of csi_limit.h does not hold
+    *winner = L.best_id;
+    *seen = L.seen;
+    *consumed = used;
+    *ended_nil = L.ended_nil;
+    return PE_OK;
 }
 
 int pe_preempted_of(const pe_stack* s, uint32_t record, uint32_t* out, uint32_t cap) {

@@ -386,6 +386,29 @@ struct CsiArgs {
     CsiReq req[kMaxCsiReq];
 };
 
+// k_csi_first / k_csi_loop (pe_place_csi): the count loop of a group with CSI
+// requests. The loop evaluates with the verdict without CSI (BatchArgs::tg has
+// node_feas null and node_ok = that column) and takes the availability per
+// placement from one of at most kMaxCsiSets code columns (k_csi_avail without
+// its fold, one launch per distinct record set).
+constexpr int kMaxCsiSets = 8;
+enum : uint8_t { kCsiClsNever = 0, kCsiClsEligible = 1, kCsiClsOpen = 2 };
+struct CsiLoopArgs {
+    const uint16_t* codes;         // [n_sets][n_rows]
+    uint32_t n_rows;
+    uint32_t n_sets;
+    const uint8_t* set_of;         // [count] the column of each placement (< n_sets)
+    // per computed class: kCsiClsEligible memoised eligible at call start (an
+    // unavailable node is a stop), kCsiClsOpen not memoised and passing the
+    // class-level job checks (a stop after the position that decides it),
+    // kCsiClsNever anything else (its nodes never reach the checker)
+    const uint8_t* cls_state;
+    uint32_t ncls;
+    uint32_t escaped;              // the group has no memo entry: never a stop
+    const uint8_t* job_ok;         // [n_rows] or null: the job checks per node (a job with escaped constraints)
+    uint32_t* first;               // [ncls] F[c]: the deciding position from the call's cursor, ~0u none
+};
+
 // Full-scan Select reduction record (one per workgroup, and per GPU shard).
 // With limit >= options the LimitIterator returns every option, the first
 // kMaxSkip non-positive ones (in visit order) moved to the end; MaxScore then

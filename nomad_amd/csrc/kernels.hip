@@ -24,6 +24,7 @@
 #include <type_traits>
 #include <cstring>
 #include "engine_types.h"
+#include "csi_limit.h"
 #include "gomath_dev.h"
 #include "gosort.h"
 #include "launchers.h"
@@ -4640,10 +4641,209 @@ __global__ void __launch_bounds__(256) k_csi_avail(CsiArgs A) {
             if (reason) code = q << 3 | reason;
         }
         A.codes[row] = (uint16_t)code;
+        if (!A.node_ok) continue;   // pe_place_csi's columns: the codes alone, nothing folded
         const bool ok = code == 0 && (!A.base_ok || A.base_ok[row] != 0);
         A.node_ok[row] = ok ? 1 : 0;
         A.node_feas[row] = (ok && A.class_ok[A.rec[row].cls] != 0) ? 1 : 0;
     }
+}
+
+// F[c] of pe_place_csi's stop rule: the first position, counted from the
+// call's cursor without wrapping, at which FeasibilityWrapper.Next would decide
+// class c's task-group status (feasible.go:1121-1143): the first node of the
+// class that passes the job checks. One lane per visit position, a min over
+// positions; classes the memo knows and nodes that fail the job checks do not
+// count. `first` is preset to ~0u.
+__global__ void __launch_bounds__(256) k_csi_first(const uint32_t* perm, uint32_t n, uint32_t offset,
+                                                   const NodeRec* rec, CsiLoopArgs C) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    uint32_t p = offset + j;
+    if (p >= n) p -= n;
+    const uint32_t row = perm[p];
+    const uint32_t c = rec[row].cls;
+    if (c >= C.ncls || C.cls_state[c] != kCsiClsOpen) return;
+    if (C.job_ok && !C.job_ok[row]) return;
+    // a clusterful of lanes shares a handful of classes: only a lane that can still lower the
+    // minimum goes to the atomic (a stale read only sends a lane there needlessly)
+    if (__hip_atomic_load(&C.first[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= j) return;
+    atomicMin(&C.first[c], j);
+}
+
+// pe_place_csi's count loop: k_window's shape (one wave, 64 positions per
+// chunk, the 128-position register ring of evaluated positions kept across
+// placements) with two differences. The ring holds the evaluation *without*
+// CSI plus FeasibilityWrapper's own verdict bit; whether a node is available is
+// read from the placement's code column when its position is consumed, so a
+// new alloc index does not empty the ring. And the LimitIterator /
+// MaxScoreIterator fold is csi_limit.h's state machine, stepped by every lane
+// in lockstep (uniform state) over the chunk's events in position order: an
+// option, or the nil of an unavailable node whose class is memoised eligible
+// (at call start, or decided at an earlier position of the call: F[c]). An
+// unavailable node of a class not yet decided is skipped and counts as
+// filtered, as a stop does.
+// Every loop is bounded without the data: chunks by n + skew, the events of a
+// chunk by its 64 lanes, the nils after the last position by kCsiTailEvents.
+__global__ void __launch_bounds__(64) k_csi_loop(BatchArgs A, CsiLoopArgs C) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
+    const int lane = threadIdx.x;
+    const uint32_t n = A.n_visit;
+    const uint32_t* perm = A.perms;
+    const uint8_t* class_ok = A.tg.class_ok;
+    const uint32_t H = 1u << A.hash_bits;
+    Overlay ov;
+    ov.bits = A.hash_bits;
+    ov.mask = H - 1;
+    ov.keys = reinterpret_cast<uint32_t*>(dyn_smem);
+    ov.k = A.packed_overlay ? nullptr : ov.keys + H;
+    ov.kshift = A.packed_overlay;
+    ov.kmask = A.packed_overlay ? (1u << A.packed_overlay) - 1u : 0u;
+    for (uint32_t i = lane; i < H; i += 64) ov.keys[i] = kEmpty;
+    __syncthreads();
+
+    uint32_t offset = n ? A.offset0 % n : 0u;
+    uint32_t placed = 0;
+    int st0 = kFiltered, st1 = kFiltered;
+    double sc0 = 0.0, sc1 = 0.0;
+    uint32_t rw0 = kEmpty, rw1 = kEmpty;
+    bool wf0 = false, wf1 = false;   // FeasibilityWrapper's verdict without CSI
+    uint32_t rb = 0;     // ring index of the cursor
+    uint32_t have = 0;   // relative positions [0, have) are cached
+    uint64_t walked = 0; // positions consumed since the call began
+    uint32_t fold_err = 0;
+
+    for (uint32_t it = 0; n && it < A.count; it++) {
+        const uint32_t set = min((uint32_t)C.set_of[it], C.n_sets - 1u);
+        const uint16_t* codes = C.codes + (size_t)set * C.n_rows;
+        CsiLimit L;
+        bool done = csi_limit_init(L, A.limit);
+        uint32_t n_filtered = 0, n_exhausted = 0;
+        uint32_t consumed = done ? 0u : n;
+        const uint32_t skew = rb & 63u;
+        for (uint32_t k = 0; !done && 64u * k < n + skew; k++) {
+            const int j = (int)(64u * k + (uint32_t)lane) - (int)skew;   // relative visit position
+            const bool valid = j >= 0 && (uint32_t)j < n;
+            const bool s1 = (((rb >> 6) + k) & 1u) != 0;
+            int st = s1 ? st1 : st0;
+            double sc = s1 ? sc1 : sc0;
+            bool wf = s1 ? wf1 : wf0;
+            uint32_t row = s1 ? rw1 : rw0;
+            const bool need = valid && (uint32_t)j >= have;
+            if (__ballot(need)) {
+                // as k_window: this chunk and the next one, all loads first
+                const uint32_t j2 = (uint32_t)(j + 64);
+                const bool need2 = j2 < n;
+                uint32_t p1 = need ? offset + (uint32_t)j : 0u;
+                uint32_t p2 = need2 ? offset + j2 : 0u;
+                if (p1 >= n) p1 -= n;
+                if (p2 >= n) p2 -= n;
+                const uint32_t row1 = perm[p1], row2 = perm[p2];
+                NodeIn in1, in2;
+                load_node(A.soa, A.tg, row1, in1);
+                load_node(A.soa, A.tg, row2, in2);
+                const bool w1 = class_ok[in1.r.cls] != 0 && (!A.tg.node_ok || A.tg.node_ok[row1] != 0);
+                const bool w2 = class_ok[in2.r.cls] != 0 && (!A.tg.node_ok || A.tg.node_ok[row2] != 0);
+                const uint32_t dk1 = ov_count(ov, row1), dk2 = ov_count(ov, row2);
+                NodeEval e1, e2;
+                e1.score = 0.0;
+                e2.score = 0.0;
+                eval_loaded<false>(A.soa, A.tg, class_ok, A.ask, dk1, A.penalty_bits, A.log10, nullptr, row1, in1,
+                                   &e1);
+                eval_loaded<false>(A.soa, A.tg, class_ok, A.ask, dk2, A.penalty_bits, A.log10, nullptr, row2, in2,
+                                   &e2);
+                if (need) {
+                    st = e1.status;
+                    sc = e1.score;
+                    wf = w1;
+                    row = row1;
+                    if (s1) { st1 = st; sc1 = sc; rw1 = row1; wf1 = w1; } else { st0 = st; sc0 = sc; rw0 = row1; wf0 = w1; }
+                }
+                if (need2) {
+                    if (s1) { st0 = e2.status; sc0 = e2.score; rw0 = row2; wf0 = w2; }
+                    else { st1 = e2.status; sc1 = e2.score; rw1 = row2; wf1 = w2; }
+                }
+                have = min(64u * (k + 2) - skew, n);
+            }
+
+            // the availability of this placement, at the time the position is consumed
+            const bool reach = valid && wf;   // the node reaches the availability checker
+            const bool unavailable = reach && row < C.n_rows && codes[row] != 0;
+            bool stop = false;
+            if (unavailable && !C.escaped) {
+                const uint32_t c = A.soa.rec[row].cls;
+                const uint8_t cs = c < C.ncls ? C.cls_state[c] : (uint8_t)kCsiClsNever;
+                stop = cs == kCsiClsEligible || (cs == kCsiClsOpen && walked + (uint64_t)j > (uint64_t)C.first[c]);
+            }
+            const bool is_opt = reach && !unavailable && st == kOption;
+            const bool is_exh = reach && !unavailable && st == kExhausted;
+            const bool is_filt = valid && !is_opt && !is_exh;
+            const uint64_t nil_m = __ballot(stop), opt_m = __ballot(is_opt);
+            uint64_t m = nil_m | opt_m;
+            int done_lane = 64;
+            while (m) {   // at most 64 events: one bit leaves m per turn
+                const int l = (int)__ffsll((long long)m) - 1;
+                m &= m - 1;
+                const double s_l = __shfl(sc, l);
+                const uint32_t kind = (nil_m >> l) & 1u ? kCsiNil : kCsiOption;
+                if (csi_limit_step(L, kind, s_l, (int32_t)(64u * k + (uint32_t)l) - (int32_t)skew)) {
+                    done = true;
+                    done_lane = l;
+                    break;
+                }
+            }
+            const bool pulled = valid && lane <= done_lane;
+            n_filtered += (uint32_t)__popcll(__ballot(pulled && is_filt));
+            n_exhausted += (uint32_t)__popcll(__ballot(pulled && is_exh));
+            if (done) consumed = 64u * k + (uint32_t)done_lane - skew + 1u;
+        }
+        // StaticIterator has nothing left for this Select: the same nil again and again
+        for (int t = 0; t < kCsiTailEvents && !done; t++) done = csi_limit_step(L, kCsiNil, 0.0, -1);
+        if (!done) {   // csi_limit.h's bound does not hold: no record, the host fails the call (as pe_csi_limit_fold)
+            fold_err = 1u;
+            break;
+        }
+
+        const int best_pos = L.best_id;
+        const double best_score = L.best_score;
+        int win_row = -1;
+        if (best_pos >= 0 && (uint32_t)best_pos < n) {
+            uint32_t pos = offset + (uint32_t)best_pos;
+            if (pos >= n) pos -= n;
+            win_row = (int)perm[pos];
+        }
+        uint32_t no = offset + (consumed % n);
+        if (no >= n) no -= n;
+        if (lane == 0) {
+            emit_placement(A, class_ok, ov, nullptr, 0u, it, win_row, best_score, consumed, n_filtered, n_exhausted,
+                           no);
+            if (win_row >= 0 && A.commit) ov_add(ov, (uint32_t)win_row);
+        }
+        wave_sync();
+        offset = no;
+        walked += consumed;
+        rb = (rb + consumed) & 127u;
+        have = have > consumed ? have - consumed : 0u;
+        if (win_row >= 0 && A.commit && have) {
+            // the winner's overlay count changed: cut the cache at its first cached position
+            const uint32_t j0 = ((uint32_t)lane - rb) & 127u, j1 = (64u + (uint32_t)lane - rb) & 127u;
+            const bool bad0 = j0 < have && rw0 == (uint32_t)win_row;
+            const bool bad1 = j1 < have && rw1 == (uint32_t)win_row;
+            if (__ballot(bad0 || bad1)) {
+                uint32_t cut = min(bad0 ? j0 : 128u, bad1 ? j1 : 128u);
+                for (int off = 32; off > 0; off >>= 1) cut = min(cut, (uint32_t)__shfl_xor((int)cut, off));
+                if (cut < have) have = cut;
+            }
+        }
+        wave_sync();
+        if (win_row < 0) break;
+        placed++;
+    }
+    if (lane == 0) {
+        A.eval_status[0] = placed;
+        A.eval_status[1] = offset;
+        A.eval_status[2] = fold_err;
+    }
+    if (A.writeback) writeback_overlay<64, false>(A, ov, H, nullptr);
 }
 
 // node_aux[row] (SweepArgs): verdict bit, affinity index (per class, or per
@@ -6251,6 +6451,36 @@ hipError_t pe_launch_csi_avail(const pe::CsiArgs* a, hipStream_t st) {
     if (blocks > 4096) blocks = 4096;
     if (blocks == 0) blocks = 1;
     hipLaunchKernelGGL(pe::k_csi_avail, dim3(blocks), dim3(256), 0, st, *a);
+    return hipGetLastError();
+}
+
+// The codes alone into a column of pe_place_csi (CsiArgs::node_ok and node_feas null).
+hipError_t pe_launch_csi_codes(const pe::CsiArgs* a, hipStream_t st) {
+    if (a->n_req > (uint32_t)pe::kMaxCsiReq || !a->plug_off || !a->nvol_off || !a->codes || a->node_ok || a->node_feas)
+        return hipErrorInvalidValue;
+    uint32_t blocks = (a->n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (blocks == 0) blocks = 1;
+    hipLaunchKernelGGL(pe::k_csi_avail, dim3(blocks), dim3(256), 0, st, *a);
+    return hipGetLastError();
+}
+
+hipError_t pe_launch_csi_first(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st) {
+    if (!a->perms || !a->soa.rec || !c->cls_state || !c->first || a->n_visit == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pe::k_csi_first, dim3((a->n_visit + 255u) / 256u), dim3(256), 0, st, a->perms, a->n_visit,
+                       a->offset0 % a->n_visit, a->soa.rec, *c);
+    return hipGetLastError();
+}
+
+// One evaluation, one wave; the overlay must hold the launch's placements.
+hipError_t pe_launch_csi_loop(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st) {
+    if (!a->perms || a->n_visit == 0 || !a->full_out || !a->eval_status || !c->codes || !c->set_of || !c->cls_state ||
+        !c->first || c->n_sets == 0 || c->n_sets > (uint32_t)pe::kMaxCsiSets || c->n_rows != a->soa.n ||
+        a->tg.node_feas || a->hash_bits < 0 || a->hash_bits > 30 ||
+        ((uint64_t)1 << a->hash_bits) < 2ull * a->count)
+        return hipErrorInvalidValue;
+    const size_t lds = pe_place_lds_bytes(false, a->hash_bits, a->packed_overlay != 0, 0);
+    hipLaunchKernelGGL(pe::k_csi_loop, dim3(1), dim3(64), lds, st, *a, *c);
     return hipGetLastError();
 }
 

@@ -68,6 +68,9 @@ uint32_t pe_ploop_max_n(uint32_t words);
 hipError_t pe_launch_commit_evicted(const pe::PreemptArgs* a, uint8_t* preempted, uint32_t* pcount,
                                     uint32_t* dev_free, uint32_t* placed, hipStream_t st);
 hipError_t pe_launch_csi_avail(const pe::CsiArgs* a, hipStream_t st);
+hipError_t pe_launch_csi_codes(const pe::CsiArgs* a, hipStream_t st);
+hipError_t pe_launch_csi_first(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st);
+hipError_t pe_launch_csi_loop(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st);
 size_t pe_fold_feas_max_classes();
 hipError_t pe_launch_fold_feas_staged(const pe::NodeSoA* s, const unsigned char* class_src, uint8_t* class_dst,
                                       uint32_t ncls, const uint8_t* node_ok, uint8_t* feas, hipStream_t st);

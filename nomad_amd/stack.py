@@ -452,6 +452,32 @@ class _Stack:
     def csi_last_ms(self) -> float:
         return float(self._lib.pe_csi_last_ms(self._h))
 
+    def PlaceCSI(self, tg, count: int, alloc_idx=None) -> List[RankedNode]:
+        """pe_place_csi: computePlacements' loop for `count` fresh placements of
+        a group with CSI requests in one launch; `alloc_idx[i]` is the name index
+        of placement i's alloc (per_alloc sources), None: the index CSIAllocIndex
+        holds. The records of the placements and, if the loop ended early, of the
+        failed Select. A group without CSI requests: Place."""
+        out = (abi.pe_ranked_node * max(1, count))()
+        placed = C.c_uint32(0)
+        idx = None
+        if alloc_idx is not None:
+            if len(alloc_idx) != count:
+                raise ValueError("alloc_idx needs one index per placement")
+            idx = (C.c_uint32 * max(1, count))(*[int(i) for i in alloc_idx])
+        self._check(self._lib.pe_place_csi(self._h, self._tg_index(tg), count, idx, out, C.byref(placed)))
+        n = min(count, placed.value + 1)
+        return [RankedNode.from_c(out[i], self.nodes, self._full_preempted(i, out[i])) for i in range(n)]
+
+    def csi_avail_launches(self) -> int:
+        return int(self._lib.pe_csi_avail_launches(self._h))
+
+    def csi_place_ms(self):
+        """(k_csi_first, k_csi_loop) device ms of the last PlaceCSI; PE_CSI_TIME=1 only."""
+        ms = (C.c_double * 2)()
+        self._check(self._lib.pe_csi_place_ms(self._h, ms))
+        return float(ms[0]), float(ms[1])
+
     def SetStateColumnar(self, cs):
         """Snapshot from a synth_columnar.ColumnarState (no per-node Python objects)."""
         self.nodes = None

@@ -20,9 +20,22 @@ unavailable nodes and some Selects take the second run of the stop rule; Selects
 engine hands back (PE_EUNSUPPORTED, the resume corner) are counted, not timed.
 
     python tools/csi_probe.py [--reps 20] [--selects 200] [--small] [--out profiles/csi/probe.json]
+
+--place: pe_place_csi against the per-placement sequence
+(pe_csi_alloc_index, pe_select, pe_commit per placement: the code as it was
+before pe_place_csi) on two handles of one build over cluster_c2, for counts
+1, 8 and 64, alloc indices 0 .. count - 1. Every repetition starts from
+pe_reset_plan and a cursor of its own; the two handles alternate. A Select the
+sequence hands back is counted, left out of its time, and the cursor moved on
+by one position (so its later placements differ from pe_place_csi's; the
+records are compared up to there). k_csi_first and k_csi_loop by HIP events on
+a third handle (PE_CSI_TIME=1).
+
+    python tools/csi_probe.py --place [--reps 24] [--small] [--out profiles/csi_place/probe.json]
 """
 import argparse
 import copy
+import ctypes
 import json
 import os
 import sys
@@ -116,8 +129,85 @@ def measure(name, nodes, allocs, job, reps, selects):
     return out
 
 
+def measure_place(nodes, allocs, job, reps, counts=(1, 8, 64)):
+    perm = synth.shuffle(len(nodes), 5)
+    volumes, node_volumes = csi_state(nodes, max(counts) + 1, seed=6)
+    csi = copy.deepcopy(job)
+    csi.task_groups[0].csi_volumes = list(REQS)
+    st_loop = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    st_seq = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    os.environ["PE_CSI_TIME"] = "1"
+    st_time = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    del os.environ["PE_CSI_TIME"]
+    limit = st_loop.GetCursor()[1]
+    n = len(nodes)
+    for st in (st_loop, st_seq, st_time):   # (the handle is a 64-bit pointer: never call without argtypes)
+        st._lib.pe_flush.restype = ctypes.c_int
+        st._lib.pe_flush.argtypes = [ctypes.c_void_p]
+
+    def stats(v):
+        a = np.asarray(v, dtype=np.float64)
+        return {"n": int(a.size), "median_us": float(np.median(a)), "p10_us": float(np.percentile(a, 10)),
+                "p90_us": float(np.percentile(a, 90))} if a.size else {"n": 0}
+    out = {"nodes": n, "requests": len(REQS), "limit": limit, "counts": {}}
+    for count in counts:
+        idx = list(range(count))
+        t_loop, t_seq, first_ms, loop_ms = [], [], [], []
+        handed_back = placed_loop = placed_seq = same = compared = 0
+        for rep in range(reps + 3):
+            cursor = (rep * 977 + 13) % n
+            for st in (st_loop, st_seq, st_time):
+                st.ResetPlan()
+                st.SetJob(csi)
+                st.SetNodes(perm)
+                st.SetCursor(cursor, limit)
+                st._check(st._lib.pe_flush(st._h))
+            t0 = time.perf_counter()
+            recs = st_loop.PlaceCSI(0, count, alloc_idx=idx)
+            dt_loop = (time.perf_counter() - t0) * 1e6
+            dt_seq, seq, diverged = 0.0, [], False
+            for i in range(count):
+                t0 = time.perf_counter()
+                try:
+                    st_seq.CSIAllocIndex(0, idx[i])
+                    r = st_seq.SelectRaw(0)
+                except Unsupported:
+                    handed_back += rep >= 3
+                    diverged = True
+                    st_seq.SetCursor((st_seq.GetCursor()[0] + 1) % n, limit)
+                    continue
+                if r.row >= 0:
+                    st_seq.Commit(0, r.row)
+                dt_seq += (time.perf_counter() - t0) * 1e6
+                if not diverged:
+                    seq.append(r)
+                if r.row < 0:
+                    break
+            st_time.PlaceCSI(0, count, alloc_idx=idx)
+            ms = st_time.csi_place_ms()
+            if rep < 3:
+                continue
+            t_loop.append(dt_loop)
+            t_seq.append(dt_seq)
+            first_ms.append(ms[0])
+            loop_ms.append(ms[1])
+            placed_loop += sum(1 for r in recs if r.row >= 0)
+            placed_seq += sum(1 for r in seq if r.row >= 0)
+            compared += len(seq)
+            same += sum(1 for a, b in zip(recs, seq) if (a.row, a.final_score, a.nodes_evaluated, a.new_offset) ==
+                        (b.row, b.final_score, b.nodes_evaluated, b.new_offset))
+        out["counts"][str(count)] = {
+            "pe_place_csi_us": stats(t_loop), "per_placement_sequence_us": stats(t_seq),
+            "k_csi_first_us": stats(np.asarray(first_ms) * 1e3), "k_csi_loop_us": stats(np.asarray(loop_ms) * 1e3),
+            "sequence_selects_handed_back": int(handed_back), "placed_per_call": placed_loop / max(1, len(t_loop)),
+            "records_compared": int(compared), "records_equal": int(same)}
+        print("place", count, json.dumps(out["counts"][str(count)]))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--place", action="store_true", help="the pe_place_csi leg (DESIGN.md §40)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--selects", type=int, default=200)
     ap.add_argument("--small", action="store_true", help="1/10 of the node counts (rehearsal)")
@@ -125,6 +215,16 @@ def main():
     a = ap.parse_args()
     scale = 10 if a.small else 1
     res = {"tool": "tools/csi_probe.py", "speculate": 0}
+    if a.place:
+        out = a.out if a.out != "profiles/csi/probe.json" else "profiles/csi_place/probe.json"
+        nodes, allocs = synth.cluster_c2(10000 // scale, seed=42)
+        res["tool"] += " --place"
+        res["cluster_c2"] = measure_place(nodes, allocs, synth.job_c2(64), max(a.reps, 20))
+        os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
+        return
     nodes, allocs = synth.cluster_c2(10000 // scale, seed=42)
     res["cluster_c2"] = measure("cluster_c2", nodes, allocs, synth.job_c2(a.selects), a.reps, a.selects)
     nodes, allocs = synth.cluster_c4(100000 // scale, seed=11)
