@@ -799,7 +799,11 @@ int pe_last_metrics_bin(const pe_stack* s, const pe_metric_count** counts, uint3
                         const pe_metric_score** scores, uint32_t* n_scores);
 /* The text of metric key `key` (an engine string or a caller string id):
  * writes at most cap bytes (NUL-terminated), returns the bytes needed or
- * PE_EINVAL for an unknown key. Scorer names: pe_scorer_name. */
+ * PE_EINVAL for an unknown key. Scorer names: pe_scorer_name.
+ * The engine's key table only grows. Most reasons are a fixed few texts; the
+ * CSI plugin reasons of pe_place_csi_metrics (PE_CSI_NO_PLUGIN, _UNHEALTHY,
+ * _MAX_VOLUMES) name the plugin and the node, so they add at most one string
+ * per (plugin, node) pair to a handle. */
 int64_t pe_metric_string(const pe_stack* s, uint32_t key, char* buf, size_t cap);
 const char* pe_scorer_name(uint32_t scorer);
 /* What update i's Select left in its AllocMetric maps (pe_last_metrics_bin
@@ -1069,6 +1073,64 @@ double pe_csi_last_ms(pe_stack* s);
 #define PE_MAX_CSI_SETS 8
 int pe_place_csi(pe_stack* s, uint32_t tg_index, uint32_t count, const uint32_t* alloc_idx, pe_ranked_node* out,
                  uint32_t* placed);
+/* pe_place_csi with AllocMetric kept: what GenericScheduler.computePlacements
+ * stores per placed alloc and, for the nil Select that ends the loop, in
+ * failedTGAllocs (generic_sched.go:552-627).
+ * With pe_set_metrics off the call is pe_place_csi: same records, same
+ * refusals, no further launch, and pe_place_csi_maps answers PE_ESTATE.
+ * With it on, the records out[0..*placed] (the failed Select's too), the
+ * cursor, the plan, the memo (pe_get_eligibility), the group's alloc index and
+ * every later observable state are exactly what pe_place_csi leaves with
+ * metrics off. pe_place_csi_maps then gives record k's AllocMetric maps as
+ * counts[counts_off[k] .. counts_off[k + 1]) and scores[scores_off[k] ..
+ * scores_off[k + 1]) for k < n_rec = the records written (the layout of
+ * pe_spec_view.mcounts / mscores; keys as pe_metric_count.key). They include
+ * what only CSIVolumeChecker.Feasible records (feasible.go:251-259): for every
+ * node the checker fails, ClassFiltered[NodeClass] and
+ * ConstraintFiltered[reason], the reason being pe_csi_reason_text's for the
+ * failing request, its volume and (plugin reasons) the node. The maps stay
+ * valid until the next placing or state call on the handle. pe_last_metrics*
+ * answers PE_ESTATE afterwards, as after the other batched metrics calls, and
+ * the metrics shadow of the memo advances as the per-Select sequence would
+ * advance it. The loop kernel additionally logs one byte per consumed visit
+ * position into mapped page-locked memory; the maps then cost one host walk
+ * over the consumed windows and one batched trace (everything it returns in
+ * one copy): two stream synchronisations per call, the loop's and the trace's,
+ * and no k_csi_avail launch beyond pe_place_csi's. A call that needs a larger
+ * log or trace buffer than the handle has allocated so far also pays that
+ * allocation, which waits for the device like any other.
+ * pe_set_metrics must be on from the job's first Select, as for the other
+ * metrics calls: the maps follow the metrics shadow of the memo, which only
+ * Selects made with metrics on advance. A caller that places the group with
+ * metrics off and then turns them on may get PE_EINTERNAL from this call after
+ * the loop has committed (the kernel's stops follow the real memo).
+ * PE_EUNSUPPORTED, all before anything changes (cursor, limit, memo, its
+ * metrics shadow and plan untouched): pe_place_csi's list without its
+ * pe_set_metrics row; with metrics on, a group without CSI requests (its maps
+ * come from pe_select or the served view), static port asks, group networks on
+ * multi-device nodes, reserved cores, two task groups of one name, and
+ * count * (visit list length) above 2^24 (the trace log of one call; a caller
+ * splits the loop). */
+int pe_place_csi_metrics(pe_stack* s, uint32_t tg_index, uint32_t count, const uint32_t* alloc_idx,
+                         pe_ranked_node* out, uint32_t* placed);
+int pe_place_csi_maps(const pe_stack* s, const pe_metric_count** counts, const uint32_t** counts_off,
+                      const pe_metric_score** scores, const uint32_t** scores_off, uint32_t* n_rec);
+/* Measurement aid, recorded only with PE_CSI_TIME=1 in the environment at
+ * pe_stack_create (no clock is read otherwise): the last pe_place_csi_metrics
+ * call that ran with metrics on, by the host clock in microseconds: us4[0] the loop (launches to the end of
+ * its synchronisation), [1] the host walk, [2] the trace (upload, launches,
+ * download), [3] the maps; and the trace log bytes the call wrote (its
+ * consumed positions). PE_ESTATE without PE_CSI_TIME=1 or when
+ * pe_place_csi_maps would answer so. */
+int pe_place_csi_metrics_stats(const pe_stack* s, double* us4, uint64_t* log_bytes);
+/* The reason text CSIVolumeChecker.Feasible records (feasible.go:19-26) for
+ * `reason` (PE_CSI_*): stateless, needs no device. `volume` is the request's
+ * source after the per_alloc suffix (reasons 1, 5, 6, 7), `plugin` the volume's
+ * plugin id and `node_id` Node.ID (reasons 2 to 4); NULL reads as "". Writes at
+ * most cap bytes (NUL-terminated) and returns the bytes needed, or PE_EINVAL
+ * for reason 0 or above 7. */
+int64_t pe_csi_reason_text(uint32_t reason, const char* plugin, const char* volume, const char* node_id, char* buf,
+                           size_t cap);
 /* k_csi_avail launches of the handle so far (pe_select's and pe_place_csi's). */
 uint64_t pe_csi_avail_launches(const pe_stack* s);
 /* Measurement aid: device time in ms of the last pe_place_csi's k_csi_first

@@ -238,10 +238,28 @@ def bind_csi(lib):
     lib.pe_csi_place_ms.restype = C.c_int
     lib.pe_csi_place_ms.argtypes = [H, f64p]
     bind_csi_limit_fold(lib)
+    if not hasattr(lib, "pe_place_csi_metrics"):   # (an A/B library from before the metrics form)
+        return lib
+    lib.pe_place_csi_metrics.restype = C.c_int
+    lib.pe_place_csi_metrics.argtypes = [H, C.c_uint32, C.c_uint32, u32p, C.POINTER(pe_ranked_node), u32p]
+    lib.pe_place_csi_maps.restype = C.c_int
+    lib.pe_place_csi_maps.argtypes = [H, C.POINTER(C.POINTER(pe_metric_count)), C.POINTER(u32p),
+                                      C.POINTER(C.POINTER(pe_metric_score)), C.POINTER(u32p), u32p]
+    lib.pe_place_csi_metrics_stats.restype = C.c_int
+    lib.pe_place_csi_metrics_stats.argtypes = [H, f64p, C.POINTER(C.c_uint64)]
+    bind_csi_reason_text(lib)
     return lib
 
 
 PE_MAX_CSI_SETS = 8
+PE_CSI_LOG_CAP = 1 << 24   # pe_place_csi_metrics: count * len(visit list) at most
+
+
+def bind_csi_reason_text(lib):
+    """pe_csi_reason_text: stateless, needs no device (any loaded libnomadpe.so)."""
+    lib.pe_csi_reason_text.restype = C.c_int64
+    lib.pe_csi_reason_text.argtypes = [C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
+    return lib
 
 
 def bind_csi_limit_fold(lib):
@@ -295,6 +313,7 @@ ENGINE_SYMBOLS = [
     "pe_inplace_update_metrics", "pe_inplace_metrics",
     "pe_inplace_update_spread", "pe_inplace_spread_ms",
     "pe_place_csi", "pe_csi_avail_launches", "pe_csi_place_ms", "pe_csi_limit_fold",
+    "pe_place_csi_metrics", "pe_place_csi_maps", "pe_place_csi_metrics_stats", "pe_csi_reason_text",
 ]
 
 

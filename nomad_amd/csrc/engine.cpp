@@ -42,6 +42,7 @@
 #include "gosort.h"
 #include "launchers.h"
 #include "csi_limit.h"
+#include "csi_reason.h"
 
 // ---- RCCL, bound at run time ------------------------------------------------
 // The engine's collectives (pe_comm_init / pe_place_sharded, the one-handle
@@ -869,6 +870,20 @@ struct pe_stack {
     uint64_t csi_avail_launches = 0;   // k_csi_avail launches of the handle (pe_csi_avail_launches)
     hipEvent_t ev_csip[3] = {nullptr, nullptr, nullptr};   // PE_CSI_TIME: before k_csi_first, between, after k_csi_loop
     bool csip_timed = false;
+    // pe_place_csi_metrics: k_csi_loop<true>'s trace log (mapped page-locked, one
+    // byte per consumed position), and the call's maps in pe_spec_view's layout
+    // (pe_place_csi_maps), valid while `gen` is the handle's
+    PinnedMem h_csi_log;
+    struct CsiMaps {
+        uint64_t gen = 0;
+        uint32_t n_rec = 0;
+        std::vector<pe_metric_count> counts;
+        std::vector<pe_metric_score> scores;
+        std::vector<uint32_t> counts_off, scores_off;
+        uint64_t log_bytes = 0;         // the log bytes the last call wrote (its consumed positions)
+        bool timed = false;             // PE_CSI_TIME=1: us[] holds the last call's split
+        double us[4] = {0, 0, 0, 0};    // loop, host walk, trace and maps (host clock)
+    } csi_m;
 
     // The unchanged SystemScheduler caller (scheduler_system.go:289-302):
     // SetNodes([node]) then Select for every node. From the third single-node
@@ -5737,7 +5752,8 @@ static int set_job_one(pe_stack* s, const pe_strtab* strs, const pe_job* j) {
                     for (auto& a : r.affinities) g->ask.dev_tw += std::fabs((double)a.weight);
                 }
             }
-            if (g->unsupported.empty()) {
+            // (a group the CSI gate alone refuses is placed once csi_gate lifts it: its table is built now)
+            if (g->unsupported.empty() || (g->unsupported == kCsiRefused && g->unsupported_else.empty())) {
                 int rc = build_dev_classes(s, *g);
                 if (rc) return rc;
             }
@@ -6036,10 +6052,20 @@ struct MetricAcc {
 // order against the reference memo shadow (feasible.go:1061-1153); rows that
 // pass go to `rows` for k_trace. `log` (or null) receives the memo changes.
 // `why_out` (or null): the reason key of the k-th visited row where it fails.
+// `csi` (or null; pe_place_csi_metrics): the window's bytes of k_csi_loop's
+// trace log. A row that passes the job's and the group's checks and whose byte
+// is non-zero failed the CSI checker, which records the FilterNode itself
+// (feasible.go:251-259) on the slow path (:1145-1149) and the fast one
+// (:1112-1119) alike: it goes to csi->hits for the caller to key, not to `rows`.
+struct CsiWalk {
+    const uint8_t* log = nullptr;                       // [evaluated]
+    std::vector<std::pair<uint32_t, uint8_t>> hits;     // (row, byte)
+    bool bad = false;   // a byte where the node never reaches the checker, or a stop bit the memo contradicts
+};
 static void metrics_walk(pe_stack* s, TgPlan& g, const std::vector<uint32_t>& order, uint32_t start,
                          uint32_t evaluated, MetricAcc& acc, std::vector<uint32_t>& rows,
                          std::vector<MemoDelta>* log = nullptr, std::vector<uint8_t>* pass = nullptr,
-                         uint32_t* why_out = nullptr) {
+                         uint32_t* why_out = nullptr, CsiWalk* csi = nullptr) {
     const size_t m = order.size();
     if (s->ref_job_memo.size() != s->ncls) s->ref_job_memo.assign(s->ncls, -1);
     auto& rt = s->ref_tg_memo[g.name];
@@ -6084,6 +6110,8 @@ static void metrics_walk(pe_stack* s, TgPlan& g, const std::vector<uint32_t>& or
             if (why) set_job(c, 0);
             else if (jm[c] == -1) set_job(c, 1);
         }
+        // (CSI) the group's entry as the checker's caller finds it: eligible is the fast path, a stop
+        const bool elig_before = csi && !tg_esc && tm[c] == 1;
         if (!why) {
             if (tg_esc) {
                 why = tg_fail(s, ev, g, s->view(row));
@@ -6098,6 +6126,10 @@ static void metrics_walk(pe_stack* s, TgPlan& g, const std::vector<uint32_t>& or
             const uint32_t key = why == kIneligible ? ineligible : s->mkey_p(why);
             acc.filter(s, row, key);
             if (why_out) why_out[k] = key;
+            if (csi && csi->log[k]) csi->bad = true;
+        } else if (csi && csi->log[k]) {
+            if (pe::csi_log_stop(csi->log[k]) != elig_before) csi->bad = true;
+            csi->hits.emplace_back(row, csi->log[k]);
         } else {
             rows.push_back(row);
             if (pass) (*pass)[p] = 1;
@@ -6607,6 +6639,192 @@ static void spec_metrics_push(pe_stack::Spec& sp, MetricAcc& acc) {
     sp.mscores_off.push_back((uint32_t)sp.mscores.size());
 }
 
+// The entries of one batched trace: per record its rows (walked on the host
+// into xrows from rsrc[k], or the cached whole-list walk `list` rotated:
+// kTraceRot | index), the running end of its entries, and the row its Select
+// placed (-1: none), which is what later records' dk counts.
+struct TraceRecs {
+    uint32_t n_rec = 0;
+    const int32_t* rec_row = nullptr;
+    std::vector<uint32_t> xrows, rec_end, rsrc, list;
+    uint32_t n_entries = 0;
+};
+
+// The checkpoint of the dynamic columns (spec_copy) as a trace's state.
+static void trace_ckpt_state(pe_stack* s, pe::NodeSoA* soa, pe::TgTables* t) {
+    soa->rec = s->ck_rec.as<pe::NodeRec>();
+    soa->coll_job = s->ck_coll_job.as<uint32_t>();
+    t->coll_tg = s->ck_coll_tg.as<uint32_t>();
+    if (t->dev_free) t->dev_free = s->ck_dev_free.as<uint32_t>();
+}
+
+// The device half of a batch of records' maps (spec_metrics,
+// pe_place_csi_metrics): every entry of R through k_trace against the state
+// `soa` / `t` with dk = the earlier records' placements on the row, every
+// record's ScoreMetaData from k_trace_top; then record k's maps from acc[k]
+// (the host walk's filters) plus its entries' outcomes, appended to the
+// pe_spec_view layout (mcounts / mscores with their per-record offsets).
+static int trace_records(pe_stack* s, TgPlan& g, pe::NodeSoA soa, pe::TgTables t, const TraceRecs& R, MetricAcc* acc,
+                         std::vector<pe_metric_count>& mcounts, std::vector<uint32_t>& mcounts_off,
+                         std::vector<pe_metric_score>& mscores, std::vector<uint32_t>& mscores_off,
+                         double* t_traced = nullptr, bool allow_list = true) {
+    const uint32_t n_rec = R.n_rec, n_entries = R.n_entries;
+    const std::vector<uint32_t>&xrows = R.xrows, &rec_end = R.rec_end, &rsrc = R.rsrc, &list = R.list;
+    auto row_of = [&](uint32_t k, uint32_t j) -> uint32_t {   // trace_row on the host
+        const uint32_t src = rsrc[k];
+        if (!(src & pe::kTraceRot)) return xrows[src + j];
+        size_t p = (size_t)(src - pe::kTraceRot) + j;
+        if (p >= list.size()) p -= list.size();
+        return list[p];
+    };
+    // one upload (walked rows, records' ends and sources, the cached list, the
+    // placements) and one download (every record's ScoreMetaData from
+    // k_trace_top, its count, the outcome codes) through buffers kept across
+    // runs; the score values stay on the device
+    const size_t n_rows = n_entries;
+    const size_t top_bytes = 5 * sizeof(pe_metric_score) * (size_t)n_rec;
+    // per record: its entries that are not options, and the first kOther of
+    // them (entry, code) as k_trace_top lists them
+    constexpr uint32_t kOther = 128;   // = kTopOther (kernels.hip)
+    const size_t other_at = (top_bytes + n_rec + 15) & ~size_t(15);
+    const size_t olist_at = (other_at + 4 * (size_t)n_rec + 15) & ~size_t(15);
+    const size_t codes_at = (olist_at + 8 * (size_t)kOther * n_rec + 15) & ~size_t(15);
+    // the lists pay off when the codes are many times their size (full passes)
+    // (allow_list false: everything in one copy whatever the sizes, so the trace ends in one synchronisation)
+    const bool use_list = allow_list && 4 * (size_t)n_rows > 4 * 8 * (size_t)kOther * n_rec;
+    bool all_codes = !use_list;
+    HIP_TRY(s, s->h_trace_top.ensure(codes_at + std::max<size_t>(n_rows, 1) * sizeof(uint32_t)));
+    const uint32_t* olist = reinterpret_cast<const uint32_t*>(s->h_trace_top.as<uint8_t>() + olist_at);
+    const uint32_t* n_other = reinterpret_cast<const uint32_t*>(s->h_trace_top.as<uint8_t>() + other_at);
+    const pe_metric_score* top = s->h_trace_top.as<pe_metric_score>();
+    const uint8_t* n_top = s->h_trace_top.as<uint8_t>() + top_bytes;
+    const uint32_t* codes = reinterpret_cast<const uint32_t*>(s->h_trace_top.as<uint8_t>() + codes_at);
+    pe::Ask a = ask_for(s, g);
+    if (n_rows) {
+        std::vector<uint64_t> pl;   // (row, record) of the run's placements
+        for (uint32_t k = 0; k < n_rec; k++) {
+            const int32_t row = R.rec_row[k];
+            if (row >= 0) pl.push_back((uint64_t)(uint32_t)row << 32 | k);
+        }
+        std::sort(pl.begin(), pl.end());
+        std::vector<uint32_t> in;
+        in.reserve(xrows.size() + 2 * (size_t)n_rec + list.size() + 2 * pl.size() + 1);
+        in.insert(in.end(), xrows.begin(), xrows.end());
+        const size_t at_end = in.size();
+        in.insert(in.end(), rec_end.begin(), rec_end.end());
+        const size_t at_src = in.size();
+        in.insert(in.end(), rsrc.begin(), rsrc.end());
+        const size_t at_list = in.size();
+        in.insert(in.end(), list.begin(), list.end());
+        if (in.size() & 1) in.push_back(0u);
+        const size_t at_pl = in.size();
+        in.resize(at_pl + 2 * pl.size());
+        if (!pl.empty()) std::memcpy(in.data() + at_pl, pl.data(), pl.size() * sizeof(uint64_t));
+        HIP_TRY(s, upload_s(s, s->d_trace_rows, in));
+        const uint32_t* d_in = s->d_trace_rows.as<uint32_t>();
+        pe::TraceSrc src{};
+        src.rows = d_in;
+        src.rec_end = d_in + at_end;
+        src.rsrc = d_in + at_src;
+        src.list = d_in + at_list;
+        src.pl = reinterpret_cast<const uint64_t*>(d_in + at_pl);
+        src.n_rec = n_rec;
+        src.n_list = (uint32_t)list.size();
+        src.n_pl = (uint32_t)pl.size();
+        HIP_TRY(s, s->d_trace_scores.ensure(n_rows * 6 * sizeof(double)));
+        HIP_TRY(s, s->d_trace_top.ensure(codes_at + n_rows * sizeof(uint32_t)));
+        uint32_t* d_codes = reinterpret_cast<uint32_t*>(s->d_trace_top.as<uint8_t>() + codes_at);
+        const double* stab = nullptr;
+        if (t.n_spread > 0) {   // every record's boosts from its own use counts (k_spread_tables)
+            for (int p = 0; p < t.n_psets; p++) t.pset_counts[p] = s->ck_pset[p].as<uint32_t>();
+            const size_t nc = t.pset_cnt_total;
+            std::vector<uint32_t> delta((size_t)n_rec * nc, 0u), cur(nc, 0u);
+            for (uint32_t k = 0; k < n_rec; k++) {
+                std::copy(cur.begin(), cur.end(), delta.begin() + (size_t)k * nc);
+                const int32_t row = R.rec_row[k];
+                if (row < 0) continue;
+                for (int p = 0; p < t.n_psets; p++) {
+                    const PsetDev& ps = *g.psets[p];
+                    const uint32_t c = s->nodes[(uint32_t)row].cls;
+                    if (ps.per_node ? ps.h_val_node.size() <= (size_t)row : ps.h_val_class.size() <= c)
+                        return s->fail(PE_EINTERNAL, "spec_metrics: a spread set's host values are missing");
+                    const uint32_t v = ps.per_node ? ps.h_val_node[(uint32_t)row] : ps.h_val_class[c];
+                    if (v != pe::kMissing) cur[t.pset_cnt_off[p] + v]++;
+                }
+            }
+            HIP_TRY(s, upload_s(s, s->d_trace_delta, delta));
+            HIP_TRY(s, s->d_trace_tabs.ensure(sizeof(double) * (size_t)n_rec * t.pset_tab_total));
+            HIP_TRY_STATE(s, pe_launch_spread_tables(&t, n_rec, s->d_trace_delta.as<uint32_t>(),
+                                                     s->d_trace_tabs.as<double>(), s->stream));
+            stab = s->d_trace_tabs.as<double>();
+        }
+        HIP_TRY_STATE(s, pe_launch_trace_batch(&soa, &t, &a, &src, (uint32_t)n_rows, d_codes, s->log10, stab,
+                                               s->d_trace_scores.as<double>(), s->stream));
+        const uint32_t flags = (a.dev_tw != 0.0 ? 1u : 0u) | (a.anti_aff ? 2u : 0u) |
+                               (!g.affinities.empty() ? 4u : 0u) |
+                               (s->cfg.stack_kind == PE_STACK_GENERIC ? 8u : 0u);
+        HIP_TRY_STATE(s, pe_launch_trace_top(d_codes, s->d_trace_scores.as<double>(), &src, flags,
+                                             s->d_trace_top.as<pe_metric_score>(),
+                                             s->d_trace_top.as<uint8_t>() + top_bytes, s->stream, (uint32_t)n_rows,
+                                             reinterpret_cast<uint32_t*>(s->d_trace_top.as<uint8_t>() + other_at),
+                                             use_list ? reinterpret_cast<uint2*>(s->d_trace_top.as<uint8_t>() +
+                                                                                 olist_at)
+                                                      : nullptr));
+        if (use_list) {
+            // the ScoreMetaData, the per-record counts and lists first; every
+            // code only when a record has more than its list holds
+            HIP_TRY(s, hipMemcpyAsync(s->h_trace_top.p, s->d_trace_top.p, codes_at, hipMemcpyDeviceToHost,
+                                      s->stream));
+            HIP_TRY(s, hipStreamSynchronize(s->stream));
+            for (uint32_t k = 0; k < n_rec && !all_codes; k++) all_codes = n_other[k] > kOther;
+            if (all_codes) {
+                HIP_TRY(s, hipMemcpyAsync(s->h_trace_top.as<uint8_t>() + codes_at, d_codes,
+                                          n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+                HIP_TRY(s, hipStreamSynchronize(s->stream));
+            }
+        } else {   // short runs: everything in one copy
+            HIP_TRY(s, hipMemcpyAsync(s->h_trace_top.p, s->d_trace_top.p, codes_at + n_rows * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(s, hipStreamSynchronize(s->stream));
+        }
+    } else {
+        std::memset(s->h_trace_top.as<uint8_t>() + top_bytes, 0, codes_at - top_bytes);
+    }
+    if (t_traced) *t_traced = now_us();
+    mcounts.clear();
+    mscores.clear();
+    mcounts_off.assign(1, 0u);
+    mscores_off.assign(1, 0u);
+    std::map<int, std::vector<uint32_t>> counts;
+    size_t i = 0;
+    for (uint32_t k = 0; k < n_rec; k++) {
+        const size_t b = i;
+        if (!n_other[k]) {
+            i = rec_end[k];   // options only
+        } else if (use_list && n_other[k] <= kOther) {   // the listed entries (maps are counts: order is free)
+            for (uint32_t q = 0; q < n_other[k]; q++) {
+                const uint32_t j = olist[2 * ((size_t)k * kOther + q)], code = olist[2 * ((size_t)k * kOther + q) + 1];
+                const int rc = metrics_outcome(s, g, a, row_of(k, j), code, nullptr, acc[k], counts);
+                if (rc) return rc;
+            }
+            i = rec_end[k];
+        }
+        for (; i < rec_end[k]; i++) {   // the options' ScoreMetaData came from k_trace_top
+            if ((codes[i] & 255u) == pe::kTrOption) continue;
+            const int rc = metrics_outcome(s, g, a, row_of(k, (uint32_t)(i - b)), codes[i], nullptr, acc[k], counts);
+            if (rc) return rc;
+        }
+        acc[k].cf.append(PE_METRIC_CLASS_FILTERED, mcounts);
+        acc[k].kf.append(PE_METRIC_CONSTRAINT_FILTERED, mcounts);
+        acc[k].ce.append(PE_METRIC_CLASS_EXHAUSTED, mcounts);
+        acc[k].de.append(PE_METRIC_DIMENSION_EXHAUSTED, mcounts);
+        mscores.insert(mscores.end(), top + 5 * (size_t)k, top + 5 * (size_t)k + n_top[k]);
+        mcounts_off.push_back((uint32_t)mcounts.size());
+        mscores_off.push_back((uint32_t)mscores.size());
+    }
+    return PE_OK;
+}
+
 // AllocMetric maps of every record of a speculative run (§25): record k's
 // Select saw the run's starting state plus the placements of records < k, so
 // its window is walked on the host in record order (the FeasibilityWrapper
@@ -6636,7 +6854,11 @@ static int spec_metrics(pe_stack* s, TgPlan& g, uint32_t off0) {
     // record k's rows: walked on the host into xrows (rsrc[k] = their offset),
     // or, once a whole-list walk no longer changes the memo, the cached walk's
     // passing rows `list` rotated to the record's start (kTraceRot | index)
-    std::vector<uint32_t> xrows, rec_end(sp.n_rec), rsrc(sp.n_rec), list, lpos;
+    TraceRecs R;
+    std::vector<uint32_t>&xrows = R.xrows, &rec_end = R.rec_end, &rsrc = R.rsrc, &list = R.list;
+    std::vector<uint32_t> lpos;
+    rec_end.resize(sp.n_rec);
+    rsrc.resize(sp.n_rec);
     xrows.reserve(16 * (size_t)sp.n_rec);
     bool list_live = false, list_done = false;   // one cached list per batch
     uint32_t off = off0, n_entries = 0;
@@ -6679,161 +6901,23 @@ static int spec_metrics(pe_stack* s, TgPlan& g, uint32_t off0) {
         rec_end[k] = n_entries;
         off = sp.compact ? sp.crecs[k].new_offset : sp.recs[k].new_offset;
     }
-    auto row_of = [&](uint32_t k, uint32_t j) -> uint32_t {   // trace_row on the host
-        const uint32_t src = rsrc[k];
-        if (!(src & pe::kTraceRot)) return xrows[src + j];
-        size_t p = (size_t)(src - pe::kTraceRot) + j;
-        if (p >= list.size()) p -= list.size();
-        return list[p];
-    };
     const double t1 = prof ? now_us() : 0.0;
-    // one upload (walked rows, records' ends and sources, the cached list, the
-    // placements) and one download (every record's ScoreMetaData from
-    // k_trace_top, its count, the outcome codes) through buffers kept across
-    // runs; the score values stay on the device
-    const size_t n_rows = n_entries;
-    const size_t top_bytes = 5 * sizeof(pe_metric_score) * (size_t)sp.n_rec;
-    // per record: its entries that are not options, and the first kOther of
-    // them (entry, code) as k_trace_top lists them
-    constexpr uint32_t kOther = 128;   // = kTopOther (kernels.hip)
-    const size_t other_at = (top_bytes + sp.n_rec + 15) & ~size_t(15);
-    const size_t olist_at = (other_at + 4 * (size_t)sp.n_rec + 15) & ~size_t(15);
-    const size_t codes_at = (olist_at + 8 * (size_t)kOther * sp.n_rec + 15) & ~size_t(15);
-    // the lists pay off when the codes are many times their size (full passes)
-    const bool use_list = 4 * (size_t)n_rows > 4 * 8 * (size_t)kOther * sp.n_rec;
-    bool all_codes = !use_list;
-    HIP_TRY(s, s->h_trace_top.ensure(codes_at + std::max<size_t>(n_rows, 1) * sizeof(uint32_t)));
-    const uint32_t* olist = reinterpret_cast<const uint32_t*>(s->h_trace_top.as<uint8_t>() + olist_at);
-    const uint32_t* n_other = reinterpret_cast<const uint32_t*>(s->h_trace_top.as<uint8_t>() + other_at);
-    const pe_metric_score* top = s->h_trace_top.as<pe_metric_score>();
-    const uint8_t* n_top = s->h_trace_top.as<uint8_t>() + top_bytes;
-    const uint32_t* codes = reinterpret_cast<const uint32_t*>(s->h_trace_top.as<uint8_t>() + codes_at);
-    pe::Ask a = ask_for(s, g);
-    if (n_rows) {
-        std::vector<uint64_t> pl;   // (row, record) of the run's placements
-        for (uint32_t k = 0; k < sp.n_rec; k++) {
-            const int32_t row = spec_rec_row(sp, k);
-            if (row >= 0) pl.push_back((uint64_t)(uint32_t)row << 32 | k);
-        }
-        std::sort(pl.begin(), pl.end());
-        std::vector<uint32_t> in;
-        in.reserve(xrows.size() + 2 * (size_t)sp.n_rec + list.size() + 2 * pl.size() + 1);
-        in.insert(in.end(), xrows.begin(), xrows.end());
-        const size_t at_end = in.size();
-        in.insert(in.end(), rec_end.begin(), rec_end.end());
-        const size_t at_src = in.size();
-        in.insert(in.end(), rsrc.begin(), rsrc.end());
-        const size_t at_list = in.size();
-        in.insert(in.end(), list.begin(), list.end());
-        if (in.size() & 1) in.push_back(0u);
-        const size_t at_pl = in.size();
-        in.resize(at_pl + 2 * pl.size());
-        if (!pl.empty()) std::memcpy(in.data() + at_pl, pl.data(), pl.size() * sizeof(uint64_t));
-        HIP_TRY(s, upload_s(s, s->d_trace_rows, in));
-        const uint32_t* d_in = s->d_trace_rows.as<uint32_t>();
-        pe::TraceSrc src{};
-        src.rows = d_in;
-        src.rec_end = d_in + at_end;
-        src.rsrc = d_in + at_src;
-        src.list = d_in + at_list;
-        src.pl = reinterpret_cast<const uint64_t*>(d_in + at_pl);
-        src.n_rec = sp.n_rec;
-        src.n_list = (uint32_t)list.size();
-        src.n_pl = (uint32_t)pl.size();
-        HIP_TRY(s, s->d_trace_scores.ensure(n_rows * 6 * sizeof(double)));
-        HIP_TRY(s, s->d_trace_top.ensure(codes_at + n_rows * sizeof(uint32_t)));
-        uint32_t* d_codes = reinterpret_cast<uint32_t*>(s->d_trace_top.as<uint8_t>() + codes_at);
+    double t2 = 0.0;
+    {
+        static thread_local std::vector<int32_t> rec_row;
+        rec_row.resize(sp.n_rec);
+        for (uint32_t k = 0; k < sp.n_rec; k++) rec_row[k] = spec_rec_row(sp, k);
+        R.n_rec = sp.n_rec;
+        R.rec_row = rec_row.data();
+        R.n_entries = n_entries;
         pe::NodeSoA soa = soa_of(s);   // the run's starting state: the checkpoint
         pe::TgTables t = tables_of(g);
-        soa.rec = s->ck_rec.as<pe::NodeRec>();
-        soa.coll_job = s->ck_coll_job.as<uint32_t>();
-        t.coll_tg = s->ck_coll_tg.as<uint32_t>();
-        if (t.dev_free) t.dev_free = s->ck_dev_free.as<uint32_t>();
-        const double* stab = nullptr;
-        if (t.n_spread > 0) {   // every record's boosts from its own use counts (k_spread_tables)
-            for (int p = 0; p < t.n_psets; p++) t.pset_counts[p] = s->ck_pset[p].as<uint32_t>();
-            const size_t nc = t.pset_cnt_total;
-            std::vector<uint32_t> delta((size_t)sp.n_rec * nc, 0u), cur(nc, 0u);
-            for (uint32_t k = 0; k < sp.n_rec; k++) {
-                std::copy(cur.begin(), cur.end(), delta.begin() + (size_t)k * nc);
-                const int32_t row = spec_rec_row(sp, k);
-                if (row < 0) continue;
-                for (int p = 0; p < t.n_psets; p++) {
-                    const PsetDev& ps = *g.psets[p];
-                    const uint32_t c = s->nodes[(uint32_t)row].cls;
-                    if (ps.per_node ? ps.h_val_node.size() <= (size_t)row : ps.h_val_class.size() <= c)
-                        return s->fail(PE_EINTERNAL, "spec_metrics: a spread set's host values are missing");
-                    const uint32_t v = ps.per_node ? ps.h_val_node[(uint32_t)row] : ps.h_val_class[c];
-                    if (v != pe::kMissing) cur[t.pset_cnt_off[p] + v]++;
-                }
-            }
-            HIP_TRY(s, upload_s(s, s->d_trace_delta, delta));
-            HIP_TRY(s, s->d_trace_tabs.ensure(sizeof(double) * (size_t)sp.n_rec * t.pset_tab_total));
-            HIP_TRY_STATE(s, pe_launch_spread_tables(&t, sp.n_rec, s->d_trace_delta.as<uint32_t>(),
-                                                     s->d_trace_tabs.as<double>(), s->stream));
-            stab = s->d_trace_tabs.as<double>();
-        }
-        HIP_TRY_STATE(s, pe_launch_trace_batch(&soa, &t, &a, &src, (uint32_t)n_rows, d_codes, s->log10, stab,
-                                               s->d_trace_scores.as<double>(), s->stream));
-        const uint32_t flags = (a.dev_tw != 0.0 ? 1u : 0u) | (a.anti_aff ? 2u : 0u) |
-                               (!g.affinities.empty() ? 4u : 0u) |
-                               (s->cfg.stack_kind == PE_STACK_GENERIC ? 8u : 0u);
-        HIP_TRY_STATE(s, pe_launch_trace_top(d_codes, s->d_trace_scores.as<double>(), &src, flags,
-                                             s->d_trace_top.as<pe_metric_score>(),
-                                             s->d_trace_top.as<uint8_t>() + top_bytes, s->stream, (uint32_t)n_rows,
-                                             reinterpret_cast<uint32_t*>(s->d_trace_top.as<uint8_t>() + other_at),
-                                             use_list ? reinterpret_cast<uint2*>(s->d_trace_top.as<uint8_t>() +
-                                                                                 olist_at)
-                                                      : nullptr));
-        if (use_list) {
-            // the ScoreMetaData, the per-record counts and lists first; every
-            // code only when a record has more than its list holds
-            HIP_TRY(s, hipMemcpyAsync(s->h_trace_top.p, s->d_trace_top.p, codes_at, hipMemcpyDeviceToHost,
-                                      s->stream));
-            HIP_TRY(s, hipStreamSynchronize(s->stream));
-            for (uint32_t k = 0; k < sp.n_rec && !all_codes; k++) all_codes = n_other[k] > kOther;
-            if (all_codes) {
-                HIP_TRY(s, hipMemcpyAsync(s->h_trace_top.as<uint8_t>() + codes_at, d_codes,
-                                          n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-                HIP_TRY(s, hipStreamSynchronize(s->stream));
-            }
-        } else {   // short runs: everything in one copy
-            HIP_TRY(s, hipMemcpyAsync(s->h_trace_top.p, s->d_trace_top.p, codes_at + n_rows * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, s->stream));
-            HIP_TRY(s, hipStreamSynchronize(s->stream));
-        }
-    } else {
-        std::memset(s->h_trace_top.as<uint8_t>() + top_bytes, 0, codes_at - top_bytes);
+        trace_ckpt_state(s, &soa, &t);
+        const int rc = trace_records(s, g, soa, t, R, acc.data(), sp.mcounts, sp.mcounts_off, sp.mscores,
+                                     sp.mscores_off, prof ? &t2 : nullptr);
+        if (rc) return rc;
     }
-    const double t2 = prof ? now_us() : 0.0;
-    spec_metrics_reset(sp);
-    std::map<int, std::vector<uint32_t>> counts;
-    size_t i = 0;
-    for (uint32_t k = 0; k < sp.n_rec; k++) {
-        const size_t b = i;
-        if (!n_other[k]) {
-            i = rec_end[k];   // options only
-        } else if (use_list && n_other[k] <= kOther) {   // the listed entries (maps are counts: order is free)
-            for (uint32_t q = 0; q < n_other[k]; q++) {
-                const uint32_t j = olist[2 * ((size_t)k * kOther + q)], code = olist[2 * ((size_t)k * kOther + q) + 1];
-                const int rc = metrics_outcome(s, g, a, row_of(k, j), code, nullptr, acc[k], counts);
-                if (rc) return rc;
-            }
-            i = rec_end[k];
-        }
-        for (; i < rec_end[k]; i++) {   // the options' ScoreMetaData came from k_trace_top
-            if ((codes[i] & 255u) == pe::kTrOption) continue;
-            const int rc = metrics_outcome(s, g, a, row_of(k, (uint32_t)(i - b)), codes[i], nullptr, acc[k], counts);
-            if (rc) return rc;
-        }
-        acc[k].cf.append(PE_METRIC_CLASS_FILTERED, sp.mcounts);
-        acc[k].kf.append(PE_METRIC_CONSTRAINT_FILTERED, sp.mcounts);
-        acc[k].ce.append(PE_METRIC_CLASS_EXHAUSTED, sp.mcounts);
-        acc[k].de.append(PE_METRIC_DIMENSION_EXHAUSTED, sp.mcounts);
-        sp.mscores.insert(sp.mscores.end(), top + 5 * (size_t)k, top + 5 * (size_t)k + n_top[k]);
-        sp.mcounts_off.push_back((uint32_t)sp.mcounts.size());
-        sp.mscores_off.push_back((uint32_t)sp.mscores.size());
-    }
+    const size_t n_rows = n_entries;
     sp.metrics = true;
     if (prof)
         std::fprintf(stderr, "spec_metrics: %u records, %llu walked, %zu traced rows: walk %.1f us, trace %.1f us, "
@@ -7217,8 +7301,9 @@ int pe_select(pe_stack* s, uint32_t tgi, const pe_select_options* opts, pe_ranke
 // is already memoised eligible (:1112-1119).
 
 // What a placing call refuses for a CSI group, before anything changes.
-static int csi_refuse(pe_stack* s, const pe_select_options* opts) {
-    if (s->metrics_on) return s->fail(PE_EUNSUPPORTED, "CSI volumes with pe_set_metrics on");
+// `traced`: pe_place_csi_metrics, the one placing call that keeps AllocMetric for such a group.
+static int csi_refuse(pe_stack* s, const pe_select_options* opts, bool traced = false) {
+    if (s->metrics_on && !traced) return s->fail(PE_EUNSUPPORTED, "CSI volumes with pe_set_metrics on");
     if (!s->kids.empty()) return s->fail(PE_EUNSUPPORTED, "CSI volumes on a handle over several devices");
     if (s->cfg.stack_kind == PE_STACK_GENERIC && opts && (opts->preferred_count || opts->preempt))
         return s->fail(PE_EUNSUPPORTED, "CSI volumes in a Select with preferred nodes or Preempt");
@@ -10749,11 +10834,39 @@ int pe_place(pe_stack* s, uint32_t tgi, uint32_t count, pe_ranked_node* out, uin
 // the call (codes only, into device columns), k_csi_first for the stop rule's
 // F[c], and k_csi_loop, which answers every Select including those pe_select
 // hands back (a stop while LimitIterator holds skipped options).
+struct CsiRecSet { pe::CsiReq req[pe::kMaxCsiReq]; };   // one alloc index's resolved request records
+static int csi_place_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec, const pe_ranked_node* recs,
+                          const uint32_t* alloc_idx, const uint8_t* set_of, const CsiRecSet* sets, double t_loop0);
+
+// `metrics` (pe_place_csi_metrics with AllocMetric on): k_csi_loop<true> logs the
+// checker's verdict per consumed position, and the records' maps follow from
+// the host walk and one batched trace against the checkpoint (csi_place_maps).
 static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32_t* alloc_idx, pe_ranked_node* out,
-                         uint32_t* placed) {
+                         uint32_t* placed, bool metrics = false) {
     // refusals, all before anything changes
-    int rc = csi_refuse(s, nullptr);
+    int rc = csi_refuse(s, nullptr, metrics);
     if (rc) return rc;
+    if (metrics) {
+        // what the batched trace of a speculative run does not rebuild (spec_eligible's rows)
+        const TgPlan& gm = *s->tgs[tgi];
+        if (has_static(gm))
+            return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: static port asks (the reason texts read port mirrors "
+                                            "that hold the call's end state)");
+        if (tg_md(s, gm))
+            return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: group networks on multi-device nodes (the port "
+                                            "texts come from per-Select host records)");
+        if (gm.ask.cores > 0)
+            return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: reserved cores (the trace reads the cores in use "
+                                            "after the call's placements)");
+        for (size_t k = 0; k < s->tgs.size(); k++)
+            if (k != tgi && s->tgs[k]->name == gm.name)
+                return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: two task groups of one name (the checkpoint "
+                                                "holds one group's collision counts)");
+        // one log byte per position the call can consume, compared in 64 bits
+        if ((uint64_t)count * (uint64_t)s->visit.size() > pe::kCsiLogCap)
+            return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: count times the visit list's length exceeds the "
+                                            "trace log of one call (2^24 positions; split the loop)");
+    }
     if (s->cfg.stack_kind != PE_STACK_GENERIC)
         return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes on a system stack (pe_select and pe_system_place place them)");
     if (s->cfg.preempt)
@@ -10781,7 +10894,7 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
     if (!count) return PE_OK;
     const uint32_t n_rows = (uint32_t)s->nodes.size(), m = (uint32_t)s->visit.size();
     // the distinct record sets of the call, and each placement's column
-    struct RecSet { pe::CsiReq req[pe::kMaxCsiReq]; };
+    using RecSet = CsiRecSet;
     std::vector<RecSet> sets;
     std::vector<uint8_t> set_of(count, 0);
     {
@@ -10814,8 +10927,20 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
         std::memset(&out[0], 0, sizeof(out[0]));
         out[0].row = -1;
         s->offset = 0;
+        if (metrics) {   // its maps are empty
+            pe_stack::CsiMaps& M = s->csi_m;
+            M.counts.clear();
+            M.scores.clear();
+            M.counts_off.assign(2, 0u);
+            M.scores_off.assign(2, 0u);
+            M.n_rec = 1;
+            M.log_bytes = 0;
+            M.timed = false;
+            M.gen = s->gen;
+        }
         return PE_OK;
     }
+    const double t_loop0 = metrics && s->tun.csi_time ? now_us() : 0.0;
     elig_resolve(s);   // the memo as the earlier Selects left it
     pe::CsiLoopArgs C;
     std::memset(&C, 0, sizeof(C));
@@ -10890,7 +11015,18 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
     if (timed) HIP_TRY(s, hipEventRecord(s->ev_csip[0], s->stream));
     if (!g.escaped) HIP_TRY_STATE(s, pe_launch_csi_first(&A, &C, s->stream));
     if (timed) HIP_TRY(s, hipEventRecord(s->ev_csip[1], s->stream));
-    HIP_TRY_STATE(s, pe_launch_csi_loop(&A, &C, s->stream));
+    uint8_t* d_log = nullptr;
+    uint32_t log_cap = 0;
+    if (metrics) {
+        // the state the call's first Select sees, for the trace (the loop commits and writes back)
+        rc = spec_copy(s, g, true);
+        if (rc) return rc;
+        log_cap = (uint32_t)((uint64_t)count * m);   // (<= kCsiLogCap: refused above otherwise)
+        HIP_TRY(s, s->h_csi_log.ensure(log_cap));
+        d_log = s->h_csi_log.dev<uint8_t>();
+        if (!d_log) return s->fail(PE_EHIP, "mapped result buffers unavailable");
+    }
+    HIP_TRY_STATE(s, pe_launch_csi_loop(&A, &C, s->stream, d_log, log_cap));
     if (timed) {
         HIP_TRY(s, hipEventRecord(s->ev_csip[2], s->stream));
         s->csip_timed = true;
@@ -10919,6 +11055,10 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
         }
     }
     if (placed) *placed = p;
+    if (metrics) {
+        rc = csi_place_maps(s, g, start % m, got, out, alloc_idx, set_of.data(), sets.data(), t_loop0);
+        if (rc) return rc;
+    }
     if (g.ask.cores > 0)
         for (uint32_t k = 0; k < p; k++) core_record(s, g, out[k].row, true, out[k].reserved_cores);
     if (p) invalidate_job_distinct(s, tgi);
@@ -10938,6 +11078,142 @@ int pe_place_csi(pe_stack* s, uint32_t tgi, uint32_t count, const uint32_t* allo
     CsiScope csi_scope_(s);
     s->pre_overflow.clear();
     return place_csi_one(s, tgi, count, alloc_idx, out, placed);
+}
+
+// The maps of pe_place_csi_metrics' records, after the loop's synchronisation:
+// record k's window [its start, + nodes_evaluated) is walked on the host against
+// the reference memo shadow with its bytes of the trace log (metrics_walk), a
+// CSI failure becomes FilterNode(node, reason text), and every row that passes
+// the wrapper goes through one batched trace (trace_records) against the
+// checkpoint taken before the loop, with the tables as the loop read them:
+// node_feas null and node_ok the column without CSI (the folded bytes belong to
+// one alloc index).
+static int csi_place_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec, const pe_ranked_node* recs,
+                          const uint32_t* alloc_idx, const uint8_t* set_of, const CsiRecSet* sets, double t_loop0) {
+    const bool timed = s->tun.csi_time;   // PE_CSI_TIME=1: the call's split (pe_place_csi_metrics_stats)
+    const double t0 = timed ? now_us() : 0.0;
+    pe_stack::CsiMaps& M = s->csi_m;
+    M.gen = 0;
+    static thread_local std::vector<MetricAcc> acc;
+    if (acc.size() < n_rec) acc.resize(n_rec);
+    for (uint32_t k = 0; k < n_rec; k++) acc[k].reset();
+    TraceRecs R;
+    R.rec_end.resize(n_rec);
+    R.rsrc.resize(n_rec);
+    R.xrows.reserve(16 * (size_t)n_rec);
+    std::vector<int32_t> rec_row(n_rec);
+    const uint8_t* log = s->h_csi_log.as<uint8_t>();
+    CsiWalk W;
+    uint32_t off = start;
+    uint64_t walked = 0;
+    std::string vol;
+    char text[512];
+    for (uint32_t k = 0; k < n_rec; k++) {
+        const uint32_t ev = recs[k].nodes_evaluated;
+        if (walked + ev > (uint64_t)s->h_csi_log.bytes)
+            return s->fail(PE_EINTERNAL, "k_csi_loop: the records consumed more positions than the trace log holds");
+        W.log = log + walked;
+        W.hits.clear();
+        const size_t x0 = R.xrows.size();
+        metrics_walk(s, g, s->visit, off, ev, acc[k], R.xrows, nullptr, nullptr, nullptr, &W);
+        if (W.bad) return s->fail(PE_EINTERNAL, "k_csi_loop: the trace log differs from the host walk");
+        const uint32_t idx = alloc_idx ? alloc_idx[k] : g.csi_idx;
+        for (const auto& h : W.hits) {
+            const uint32_t q = pe::csi_log_request(h.second), reason = pe::csi_log_reason(h.second);
+            if (q >= g.csi_reqs.size() || !reason)
+                return s->fail(PE_EINTERNAL, "k_csi_loop: a trace log byte names no request of the group");
+            const pe_csi_request& r = g.csi_reqs[q];
+            vol = s->S(r.source);
+            if (r.per_alloc) vol += "[" + std::to_string(idx) + "]";
+            const bool node_part = reason >= PE_CSI_NO_PLUGIN && reason <= PE_CSI_MAX_VOLUMES;
+            const char* plugin = node_part ? s->S(sets[set_of[k]].req[q].plugin).c_str() : "";
+            const char* node_id = node_part ? s->S(s->nodes[h.first].id).c_str() : "";
+            const int64_t need = pe::csi_reason_text(reason, plugin, vol.c_str(), node_id, text, sizeof(text));
+            if (need < 0) return s->fail(PE_EINTERNAL, "k_csi_loop: a trace log byte names no reason");
+            if ((size_t)need <= sizeof(text)) {
+                acc[k].filter(s, h.first, s->mkey(text));
+            } else {   // a long id: the text in full
+                std::string full((size_t)need, '\0');
+                pe::csi_reason_text(reason, plugin, vol.c_str(), node_id, full.data(), full.size());
+                full.resize((size_t)need - 1);
+                acc[k].filter(s, h.first, s->mkey(full));
+            }
+        }
+        R.rsrc[k] = (uint32_t)x0;
+        R.rec_end[k] = (uint32_t)R.xrows.size();
+        rec_row[k] = recs[k].row;
+        walked += ev;
+        off = recs[k].new_offset;
+    }
+    R.n_rec = n_rec;
+    R.rec_row = rec_row.data();
+    R.n_entries = (uint32_t)R.xrows.size();
+    const double t1 = timed ? now_us() : 0.0;
+    double t2 = t1;
+    pe::NodeSoA soa = soa_of(s);   // the state the call's first Select saw: the checkpoint
+    pe::TgTables t = tables_of(g);
+    trace_ckpt_state(s, &soa, &t);
+    t.node_feas = nullptr;
+    t.node_ok = g.csi_base_ok.as<uint8_t>();
+    const int rc = trace_records(s, g, soa, t, R, acc.data(), M.counts, M.counts_off, M.scores, M.scores_off,
+                                 timed ? &t2 : nullptr, false);
+    if (rc) return rc;
+    M.n_rec = n_rec;
+    M.log_bytes = walked;
+    M.gen = s->gen;
+    M.timed = timed;
+    if (timed) {
+        M.us[0] = t0 - t_loop0;
+        M.us[1] = t1 - t0;
+        M.us[2] = t2 - t1;
+        M.us[3] = now_us() - t2;
+    }
+    return PE_OK;
+}
+
+int pe_place_csi_metrics(pe_stack* s, uint32_t tgi, uint32_t count, const uint32_t* alloc_idx, pe_ranked_node* out,
+                         uint32_t* placed) {
+    if (!s || (!out && count)) return PE_EINVAL;
+    // AllocMetric off: the call is pe_place_csi (no maps: pe_place_csi_maps answers PE_ESTATE)
+    if (!s->metrics_on) return pe_place_csi(s, tgi, count, alloc_idx, out, placed);
+    if (placed) *placed = 0;
+    if (!s->have_job || tgi >= s->tgs.size() || s->tgs[tgi]->has_csi != csi_active(*s->tgs[tgi]))
+        return pe_place(s, tgi, count, out, placed);   // (no job, no such group, a CSI group without its table)
+    PE_FLUSH_RESET(s);
+    if (!csi_active(*s->tgs[tgi]))
+        return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: a group without CSI requests (its maps come from "
+                                        "pe_select or the served view)");
+    CsiScope csi_scope_(s);
+    s->pre_overflow.clear();
+    return place_csi_one(s, tgi, count, alloc_idx, out, placed, true);
+}
+
+int pe_place_csi_maps(const pe_stack* s, const pe_metric_count** counts, const uint32_t** counts_off,
+                      const pe_metric_score** scores, const uint32_t** scores_off, uint32_t* n_rec) {
+    if (!s || !counts || !counts_off || !scores || !scores_off || !n_rec) return PE_EINVAL;
+    const pe_stack::CsiMaps& M = s->csi_m;
+    if (!M.gen || M.gen != s->gen) return PE_ESTATE;
+    *counts = M.counts.data();
+    *counts_off = M.counts_off.data();
+    *scores = M.scores.data();
+    *scores_off = M.scores_off.data();
+    *n_rec = M.n_rec;
+    return PE_OK;
+}
+
+int pe_place_csi_metrics_stats(const pe_stack* s, double* us4, uint64_t* log_bytes) {
+    if (!s || !us4 || !log_bytes) return PE_EINVAL;
+    const pe_stack::CsiMaps& M = s->csi_m;
+    if (!M.gen || M.gen != s->gen || !M.timed) return PE_ESTATE;
+    std::memcpy(us4, M.us, sizeof(M.us));
+    *log_bytes = M.log_bytes;
+    return PE_OK;
+}
+
+int64_t pe_csi_reason_text(uint32_t reason, const char* plugin, const char* volume, const char* node_id, char* buf,
+                           size_t cap) {
+    const int64_t need = pe::csi_reason_text(reason, plugin, volume, node_id, buf, cap);
+    return need < 0 ? PE_EINVAL : need;
 }
 
 uint64_t pe_csi_avail_launches(const pe_stack* s) { return s ? s->csi_avail_launches : 0; }

@@ -25,6 +25,7 @@
 #include <cstring>
 #include "engine_types.h"
 #include "csi_limit.h"
+#include "csi_reason.h"
 #include "gomath_dev.h"
 #include "gosort.h"
 #include "launchers.h"
@@ -4684,7 +4685,14 @@ __global__ void __launch_bounds__(256) k_csi_first(const uint32_t* perm, uint32_
 // filtered, as a stop does.
 // Every loop is bounded without the data: chunks by n + skew, the events of a
 // chunk by its 64 lanes, the nils after the last position by kCsiTailEvents.
-__global__ void __launch_bounds__(64) k_csi_loop(BatchArgs A, CsiLoopArgs C) {
+// kMetrics (pe_place_csi_metrics): the trace log, one byte per consumed
+// position of the call in consumption order (csi_reason.h: the placement's
+// availability code and whether the node was a stop). The index is
+// walked + j; the lanes a Select pulled store their byte after the chunk's
+// fold, so a Select that ends mid-chunk logs exactly its consumed prefix.
+// `log` is mapped page-locked memory of log_cap >= count * n_visit bytes.
+template <bool kMetrics>
+__global__ void __launch_bounds__(64) k_csi_loop(BatchArgs A, CsiLoopArgs C, uint8_t* log, uint32_t log_cap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
     const int lane = threadIdx.x;
     const uint32_t n = A.n_visit;
@@ -4794,6 +4802,11 @@ __global__ void __launch_bounds__(64) k_csi_loop(BatchArgs A, CsiLoopArgs C) {
             const bool pulled = valid && lane <= done_lane;
             n_filtered += (uint32_t)__popcll(__ballot(pulled && is_filt));
             n_exhausted += (uint32_t)__popcll(__ballot(pulled && is_exh));
+            if constexpr (kMetrics) {
+                const uint64_t at = walked + (uint64_t)(pulled ? j : 0);
+                if (pulled && at < (uint64_t)log_cap)
+                    log[at] = csi_log_pack(unavailable ? (uint32_t)codes[row] : 0u, stop);
+            }
             if (done) consumed = 64u * k + (uint32_t)done_lane - skew + 1u;
         }
         // StaticIterator has nothing left for this Select: the same nil again and again
@@ -6473,14 +6486,20 @@ hipError_t pe_launch_csi_first(const pe::BatchArgs* a, const pe::CsiLoopArgs* c,
 }
 
 // One evaluation, one wave; the overlay must hold the launch's placements.
-hipError_t pe_launch_csi_loop(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st) {
+hipError_t pe_launch_csi_loop(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st, uint8_t* log,
+                              uint32_t log_cap) {
     if (!a->perms || a->n_visit == 0 || !a->full_out || !a->eval_status || !c->codes || !c->set_of || !c->cls_state ||
         !c->first || c->n_sets == 0 || c->n_sets > (uint32_t)pe::kMaxCsiSets || c->n_rows != a->soa.n ||
         a->tg.node_feas || a->hash_bits < 0 || a->hash_bits > 30 ||
         ((uint64_t)1 << a->hash_bits) < 2ull * a->count)
         return hipErrorInvalidValue;
+    if (a->ask.n_dev > 0 && (!a->tg.dev_cls || !a->tg.dev_free)) return hipErrorInvalidValue;   // a device ask reads both
+    // the trace log holds every position the call can consume (a Select consumes at most n_visit)
+    if (log && ((uint64_t)a->count * a->n_visit > (uint64_t)log_cap || (uint64_t)log_cap > pe::kCsiLogCap))
+        return hipErrorInvalidValue;
     const size_t lds = pe_place_lds_bytes(false, a->hash_bits, a->packed_overlay != 0, 0);
-    hipLaunchKernelGGL(pe::k_csi_loop, dim3(1), dim3(64), lds, st, *a, *c);
+    if (log) hipLaunchKernelGGL(pe::k_csi_loop<true>, dim3(1), dim3(64), lds, st, *a, *c, log, log_cap);
+    else hipLaunchKernelGGL(pe::k_csi_loop<false>, dim3(1), dim3(64), lds, st, *a, *c, (uint8_t*)nullptr, 0u);
     return hipGetLastError();
 }
 

@@ -70,7 +70,10 @@ hipError_t pe_launch_commit_evicted(const pe::PreemptArgs* a, uint8_t* preempted
 hipError_t pe_launch_csi_avail(const pe::CsiArgs* a, hipStream_t st);
 hipError_t pe_launch_csi_codes(const pe::CsiArgs* a, hipStream_t st);
 hipError_t pe_launch_csi_first(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st);
-hipError_t pe_launch_csi_loop(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st);
+// log (or null): the trace log of pe_place_csi_metrics (k_csi_loop<true>), mapped
+// page-locked memory of log_cap >= count * n_visit bytes
+hipError_t pe_launch_csi_loop(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st,
+                              uint8_t* log = nullptr, uint32_t log_cap = 0);
 size_t pe_fold_feas_max_classes();
 hipError_t pe_launch_fold_feas_staged(const pe::NodeSoA* s, const unsigned char* class_src, uint8_t* class_dst,
                                       uint32_t ncls, const uint8_t* node_ok, uint8_t* feas, hipStream_t st);

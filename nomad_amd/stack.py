@@ -469,6 +469,36 @@ class _Stack:
         n = min(count, placed.value + 1)
         return [RankedNode.from_c(out[i], self.nodes, self._full_preempted(i, out[i])) for i in range(n)]
 
+    def PlaceCSIMetrics(self, tg, count: int, alloc_idx=None) -> List[RankedNode]:
+        """pe_place_csi_metrics: PlaceCSI with AllocMetric kept. The records are
+        PlaceCSI's; with EnableMetrics on, PlaceCSIMaps() then gives each
+        record's maps, the failed Select's included."""
+        out = (abi.pe_ranked_node * max(1, count))()
+        placed = C.c_uint32(0)
+        idx = None
+        if alloc_idx is not None:
+            if len(alloc_idx) != count:
+                raise ValueError("alloc_idx needs one index per placement")
+            idx = (C.c_uint32 * max(1, count))(*[int(i) for i in alloc_idx])
+        self._check(self._lib.pe_place_csi_metrics(self._h, self._tg_index(tg), count, idx, out, C.byref(placed)))
+        n = min(count, placed.value + 1)
+        return [RankedNode.from_c(out[i], self.nodes, self._full_preempted(i, out[i])) for i in range(n)]
+
+    def PlaceCSIMaps(self) -> List[Dict]:
+        """pe_place_csi_maps: the maps of the last PlaceCSIMetrics' records, one
+        dict per record in LastMetrics' shape."""
+        c, sc = C.POINTER(abi.pe_metric_count)(), C.POINTER(abi.pe_metric_score)()
+        co, so, n = abi.u32p(), abi.u32p(), C.c_uint32(0)
+        self._check(self._lib.pe_place_csi_maps(self._h, C.byref(c), C.byref(co), C.byref(sc), C.byref(so),
+                                                C.byref(n)))
+        return [decode_metrics(self, c, co[k], co[k + 1], sc, so[k], so[k + 1]) for k in range(n.value)]
+
+    def place_csi_metrics_stats(self):
+        """([loop, walk, trace, maps] in us by the host clock, trace log bytes) of the last PlaceCSIMetrics."""
+        us, nb = (C.c_double * 4)(), C.c_uint64(0)
+        self._check(self._lib.pe_place_csi_metrics_stats(self._h, us, C.byref(nb)))
+        return [float(x) for x in us], int(nb.value)
+
     def csi_avail_launches(self) -> int:
         return int(self._lib.pe_csi_avail_launches(self._h))
 

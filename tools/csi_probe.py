@@ -32,6 +32,16 @@ records are compared up to there). k_csi_first and k_csi_loop by HIP events on
 a third handle (PE_CSI_TIME=1).
 
     python tools/csi_probe.py --place [--reps 24] [--small] [--out profiles/csi_place/probe.json]
+
+--place-metrics: pe_place_csi_metrics with AllocMetric on
+against pe_place_csi with it off, on two handles of one build over the same
+setup (counts 1, 8 and 64, 24 repetitions after 3 warm-up ones, each from
+pe_reset_plan and a cursor of its own). Per count: both calls' host-clock time,
+the metrics call's split into loop, host walk, trace and maps and the trace log
+bytes written per call (pe_place_csi_metrics_stats on a third handle created
+with PE_CSI_TIME=1), and whether the records are equal.
+
+    python tools/csi_probe.py --place-metrics [--reps 24] [--small] [--out profiles/csi_place_metrics/probe.json]
 """
 import argparse
 import copy
@@ -205,9 +215,88 @@ def measure_place(nodes, allocs, job, reps, counts=(1, 8, 64)):
     return out
 
 
+def measure_place_metrics(nodes, allocs, job, reps, counts=(1, 8, 64)):
+    """pe_place_csi_metrics with AllocMetric on against pe_place_csi with it off, on
+    two handles of one build that alternate; §40's setup otherwise."""
+    perm = synth.shuffle(len(nodes), 5)
+    volumes, node_volumes = csi_state(nodes, max(counts) + 1, seed=6)
+    csi = copy.deepcopy(job)
+    csi.task_groups[0].csi_volumes = list(REQS)
+    st_met = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    st_met.EnableMetrics(True)
+    st_off = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    os.environ["PE_CSI_TIME"] = "1"     # read at create: only st_time reads the clock inside the call
+    st_time = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    del os.environ["PE_CSI_TIME"]
+    st_time.EnableMetrics(True)
+    limit = st_met.GetCursor()[1]
+    n = len(nodes)
+    for st in (st_met, st_off, st_time):   # (the handle is a 64-bit pointer: never call without argtypes)
+        st._lib.pe_flush.restype = ctypes.c_int
+        st._lib.pe_flush.argtypes = [ctypes.c_void_p]
+
+    def stats(v):
+        a = np.asarray(v, dtype=np.float64)
+        return {"n": int(a.size), "median_us": float(np.median(a)), "p10_us": float(np.percentile(a, 10)),
+                "p90_us": float(np.percentile(a, 90))} if a.size else {"n": 0}
+    out = {"nodes": n, "requests": len(REQS), "limit": limit, "counts": {}}
+    for count in counts:
+        idx = list(range(count))
+        t_met, t_off, t_decode, log_bytes, keys = [], [], [], [], []
+        split = {"loop": [], "walk": [], "trace": [], "maps": []}
+        placed = same = compared = csi_filtered = 0
+        for rep in range(reps + 3):
+            cursor = (rep * 977 + 13) % n
+            for st in (st_met, st_off, st_time):
+                st.ResetPlan()
+                st.SetJob(csi)
+                st.SetNodes(perm)
+                st.SetCursor(cursor, limit)
+                st._check(st._lib.pe_flush(st._h))
+            t0 = time.perf_counter()
+            recs = st_met.PlaceCSIMetrics(0, count, alloc_idx=idx)
+            dt_met = (time.perf_counter() - t0) * 1e6
+            t0 = time.perf_counter()
+            maps = st_met.PlaceCSIMaps()
+            dt_decode = (time.perf_counter() - t0) * 1e6
+            t0 = time.perf_counter()
+            plain = st_off.PlaceCSI(0, count, alloc_idx=idx)
+            dt_off = (time.perf_counter() - t0) * 1e6
+            st_time.PlaceCSIMetrics(0, count, alloc_idx=idx)
+            us, nb = st_time.place_csi_metrics_stats()
+            if rep < 3:
+                continue
+            t_met.append(dt_met)
+            t_off.append(dt_off)
+            t_decode.append(dt_decode)
+            log_bytes.append(nb)
+            for k, v in zip(("loop", "walk", "trace", "maps"), us):
+                split[k].append(v)
+            placed += sum(1 for r in recs if r.row >= 0)
+            compared += len(plain)
+            same += sum(1 for a, b in zip(recs, plain) if (a.row, a.final_score, a.nodes_evaluated, a.nodes_filtered,
+                                                            a.new_offset) ==
+                        (b.row, b.final_score, b.nodes_evaluated, b.nodes_filtered, b.new_offset))
+            assert len(maps) == len(recs)
+            csi_filtered += sum(c for m in maps for k, c in m["ConstraintFiltered"].items()
+                                if k.startswith(("CSI ", "missing CSI ")))
+            keys.append(sum(len(m["ConstraintFiltered"]) for m in maps))
+        out["counts"][str(count)] = {
+            "pe_place_csi_metrics_on_us": stats(t_met), "pe_place_csi_metrics_off_us": stats(t_off),
+            "split_us": {k: stats(v) for k, v in split.items()},
+            "python_decode_of_maps_us": stats(t_decode),
+            "log_bytes_per_call": {"median": float(np.median(log_bytes)), "min": int(np.min(log_bytes)),
+                                   "max": int(np.max(log_bytes))}, "placed_per_call": placed / max(1, len(t_met)),
+            "records_compared": int(compared), "records_equal": int(same),
+            "csi_filter_entries": int(csi_filtered), "constraint_keys_per_call": float(np.mean(keys))}
+        print("place-metrics", count, json.dumps(out["counts"][str(count)]))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--place", action="store_true", help="the pe_place_csi leg (DESIGN.md §40)")
+    ap.add_argument("--place-metrics", action="store_true", help="the pe_place_csi_metrics leg (DESIGN.md §41)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--selects", type=int, default=200)
     ap.add_argument("--small", action="store_true", help="1/10 of the node counts (rehearsal)")
@@ -215,6 +304,16 @@ def main():
     a = ap.parse_args()
     scale = 10 if a.small else 1
     res = {"tool": "tools/csi_probe.py", "speculate": 0}
+    if a.place_metrics:
+        out = a.out if a.out != "profiles/csi/probe.json" else "profiles/csi_place_metrics/probe.json"
+        nodes, allocs = synth.cluster_c2(10000 // scale, seed=42)
+        res["tool"] += " --place-metrics"
+        res["cluster_c2"] = measure_place_metrics(nodes, allocs, synth.job_c2(64), max(a.reps, 24))
+        os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
+        return
     if a.place:
         out = a.out if a.out != "profiles/csi/probe.json" else "profiles/csi_place/probe.json"
         nodes, allocs = synth.cluster_c2(10000 // scale, seed=42)
