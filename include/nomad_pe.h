@@ -517,8 +517,8 @@ int pe_inplace_update_metrics(pe_stack* s, uint32_t tg_index, const uint32_t* al
                               pe_ranked_node* out, uint8_t* status, uint32_t* updated);
 /* (pe_inplace_metric and pe_inplace_metrics: below, with the AllocMetric types.) */
 /* pe_inplace_update_metrics that does not refuse spread stanzas, at job or
- * group level: the most general of the in-place calls, the one a caller
- * should use. SpreadIterator never filters (spread.go:110-174), so the walk
+ * group level (a caller uses pe_inplace_update_csi below, which is this call
+ * for every group without CSI requests). SpreadIterator never filters (spread.go:110-174), so the walk
  * decides the statuses without the spread sets; a second stage then adds the
  * allocation-spread part and the FinalScore built from it in list order, from
  * the property counts each update's Select sees in the per-call sequence
@@ -537,6 +537,38 @@ int pe_inplace_update_metrics(pe_stack* s, uint32_t tg_index, const uint32_t* al
  * synchronisation. */
 int pe_inplace_update_spread(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n,
                              pe_ranked_node* out, uint8_t* status, uint32_t* updated);
+/* pe_inplace_update_spread that does not refuse a task group with CSI volume
+ * requests (pe_set_csi, pe_set_csi_requests below), which the four calls above
+ * do: the call for every group. alloc_idx[i] is the name index of allocs[i]
+ * (AllocSuffix, funcs.go:402), which per_alloc sources take as their suffix
+ * for that update only; NULL: every update uses the index pe_csi_alloc_index
+ * holds. Records, statuses and every later observable state are those of the
+ * per-call sequence with pe_csi_alloc_index(alloc_idx[i]) before each
+ * pe_select. CSIVolumeChecker runs behind the wrapper's job and group checks
+ * and reads the state snapshot alone (feasible.go:261-337): an update whose
+ * node passes those checks and is unavailable for its alloc index has status
+ * 1 and a nil record (nodes_evaluated 1, nodes_filtered 1) before
+ * distinct_hosts and BinPack are asked, so no fit and, on a preempting stack,
+ * no eviction is tried for it; an update the wrapper filters keeps the
+ * wrapper's reason, and the class memo advances as if the checker did not
+ * exist (feasible.go:1141-1149). With pe_set_metrics on, pe_inplace_metrics
+ * gives an unavailable update class_key as for any filtered node, reason_key
+ * the engine key of pe_csi_reason_text for the failing request (the keys of
+ * pe_place_csi_metrics) and score PE_NONE. The second stage of a job with
+ * spreads counts such an update like any other status-1 update: not at all.
+ * Afterwards the group's alloc index is alloc_idx[n - 1]. On a group without
+ * CSI requests the call is pe_inplace_update_spread (alloc_idx is not read).
+ * Otherwise it adds one store-only k_csi_avail launch per distinct set of
+ * resolved request records among the listed indices (pe_csi_avail_launches)
+ * and one upload of n bytes, and no synchronisation or copy back.
+ * PE_EINVAL cases, pe_inplace_update_preempted, pe_inplace_metrics and
+ * pe_inplace_spread_ms are pe_inplace_update_spread's. PE_EUNSUPPORTED
+ * (checked before anything changes): pe_inplace_update_spread's list without
+ * "CSI volumes"; a CSI group without a table or without requests, as pe_select
+ * refuses it; computed classes whose nodes differ in the group's checks; more
+ * than PE_MAX_CSI_SETS distinct record sets in the list. */
+int pe_inplace_update_csi(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, const uint32_t* alloc_idx,
+                          uint32_t n, pe_ranked_node* out, uint8_t* status, uint32_t* updated);
 /* HIP-event times of the last pe_inplace_update* call's launches in ms:
  * ms2[0] the walk(s), ms2[1] pe_inplace_update_spread's second stage (0 when
  * it did not run). pe_last_kernel_ms gives their sum. */

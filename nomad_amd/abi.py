@@ -311,7 +311,7 @@ ENGINE_SYMBOLS = [
     "pe_chain_wide_stats", "pe_chain_wide_launches", "pe_chain_wide_one_lds",
     "pe_inplace_update_preempt", "pe_inplace_update_preempted",
     "pe_inplace_update_metrics", "pe_inplace_metrics",
-    "pe_inplace_update_spread", "pe_inplace_spread_ms",
+    "pe_inplace_update_spread", "pe_inplace_spread_ms", "pe_inplace_update_csi",
     "pe_place_csi", "pe_csi_avail_launches", "pe_csi_place_ms", "pe_csi_limit_fold",
     "pe_place_csi_metrics", "pe_place_csi_maps", "pe_place_csi_metrics_stats", "pe_csi_reason_text",
 ]

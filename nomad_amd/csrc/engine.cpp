@@ -865,6 +865,7 @@ struct pe_stack {
         DevMem plug_off, plug_id, plug_healthy, plug_max, nvol_off, nvol_plugin;
     } csi;
     bool csi_scope = false;            // inside pe_select / pe_system_place: the calls that place a CSI group
+    bool csi_defer = false;            // inside pe_inplace_update_csi: prepare_tg leaves the fold to the next Select
     hipEvent_t ev_csi0 = nullptr, ev_csi1 = nullptr;   // around the last k_csi_avail
     bool csi_timed = false;
     uint64_t csi_avail_launches = 0;   // k_csi_avail launches of the handle (pe_csi_avail_launches)
@@ -1024,6 +1025,8 @@ struct pe_stack {
     // indices per set, their own flags, the start columns), the chunks' prefix
     // rows, and the walk's records when the caller asked for the maps alone
     DevMem d_inplace_sp_in, d_inplace_sp_pre, d_inplace_sp_rec;
+    // pe_inplace_update_csi: each update's code column, by list position
+    DevMem d_inplace_csi_set;
     double inplace_stage_ms[2] = {0, 0};   // the walk, the spread stage (pe_inplace_spread_ms)
     SysGroupsState sysg;   // pe_system_place_groups*: buffers, and what the accessors read
     bool stopped(uint32_t ai) const { return ai < stop_count.size() && stop_count[ai] > 0; }
@@ -4254,7 +4257,8 @@ int prepare_tg(pe_stack* s, uint32_t tgi, const std::vector<uint32_t>& order, ui
         int rc = build_tables(s, g, order, start);
         if (rc) return rc;
     }
-    if (csi_active(g) && g.csi_dirty) return csi_refresh(s, g);
+    // (pe_inplace_update_csi reads the verdict without CSI and its own code columns: the group stays dirty)
+    if (csi_active(g) && g.csi_dirty && !s->csi_defer) return csi_refresh(s, g);
     return PE_OK;
 }
 
@@ -6283,6 +6287,34 @@ static bool trace_key(pe_stack* s, uint32_t code, uint32_t* kind, uint32_t* key)
         default: return false;
     }
     *key = s->mkey_p(t);
+    return true;
+}
+
+// The engine key of the reason CSIVolumeChecker.Feasible records for a node
+// (feasible.go:251-259): pe_csi_reason_text for request `q` of the group failing
+// with `reason` at alloc index `idx`, the suffixed volume source, and for the
+// node-level reasons the volume's plugin (a string id) and the node's id.
+// False: the pair names no request or no reason.
+static bool csi_reason_key(pe_stack* s, const TgPlan& g, uint32_t q, uint32_t reason, uint32_t idx, uint32_t plugin,
+                           uint32_t row, uint32_t* key) {
+    if (q >= g.csi_reqs.size() || !reason) return false;
+    const pe_csi_request& r = g.csi_reqs[q];
+    std::string vol = s->S(r.source);
+    if (r.per_alloc) vol += "[" + std::to_string(idx) + "]";
+    const bool node_part = reason >= PE_CSI_NO_PLUGIN && reason <= PE_CSI_MAX_VOLUMES;
+    const char* pl = node_part ? s->S(plugin).c_str() : "";
+    const char* node_id = node_part ? s->S(s->nodes[row].id).c_str() : "";
+    char text[512];
+    const int64_t need = pe::csi_reason_text(reason, pl, vol.c_str(), node_id, text, sizeof(text));
+    if (need < 0) return false;
+    if ((size_t)need <= sizeof(text)) {
+        *key = s->mkey(text);
+    } else {   // a long id: the text in full
+        std::string full((size_t)need, '\0');
+        pe::csi_reason_text(reason, pl, vol.c_str(), node_id, full.data(), full.size());
+        full.resize((size_t)need - 1);
+        *key = s->mkey(full);
+    }
     return true;
 }
 
@@ -8735,6 +8767,69 @@ static int inplace_csr_set(pe_stack* s, const std::vector<std::pair<uint32_t, st
     return PE_OK;
 }
 
+struct CsiRecSet { pe::CsiReq req[pe::kMaxCsiReq]; };   // one alloc index's resolved request records
+
+// The distinct record sets of a call that takes an alloc index per position
+// (pe_place_csi, pe_inplace_update_csi), compared as bytes, and each position's
+// set. `alloc_idx` null, or a group without per_alloc sources: the group's own
+// index throughout. False: more than kMaxCsiSets sets.
+static bool csi_record_sets(pe_stack* s, const TgPlan& g, const uint32_t* alloc_idx, uint32_t n,
+                            std::vector<CsiRecSet>& sets, std::vector<uint8_t>& set_of) {
+    bool per_alloc = false;
+    for (const pe_csi_request& r : g.csi_reqs) per_alloc = per_alloc || r.per_alloc;
+    std::map<uint32_t, uint8_t> by_idx;
+    set_of.assign(n, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t idx = alloc_idx && per_alloc ? alloc_idx[i] : g.csi_idx;
+        auto it = by_idx.find(idx);
+        if (it == by_idx.end()) {
+            CsiRecSet rs;
+            csi_resolve(s, g, idx, rs.req);
+            size_t k = 0;
+            while (k < sets.size() && std::memcmp(sets[k].req, rs.req, sizeof(rs.req)) != 0) k++;
+            if (k == sets.size()) {
+                if (sets.size() == (size_t)pe::kMaxCsiSets) return false;
+                sets.push_back(rs);
+            }
+            it = by_idx.emplace(idx, (uint8_t)k).first;
+        }
+        set_of[i] = it->second;
+    }
+    return true;
+}
+
+// One k_csi_avail launch per record set, store-only, into the group's code columns [set][row].
+static int csi_launch_columns(pe_stack* s, TgPlan& g, const std::vector<CsiRecSet>& sets) {
+    const uint32_t n_rows = (uint32_t)s->nodes.size();
+    for (size_t k = 0; k < sets.size(); k++) {
+        pe::CsiArgs V;
+        std::memset(&V, 0, sizeof(V));
+        V.n = n_rows;
+        V.n_req = (uint32_t)g.csi_reqs.size();
+        std::memcpy(V.req, sets[k].req, sizeof(V.req));
+        V.plug_off = s->csi.plug_off.as<uint32_t>();
+        V.plug_id = s->csi.plug_id.as<uint32_t>();
+        V.plug_healthy = s->csi.plug_healthy.as<uint8_t>();
+        V.plug_max = s->csi.plug_max.as<int64_t>();
+        V.nvol_off = s->csi.nvol_off.as<uint32_t>();
+        V.nvol_plugin = s->csi.nvol_plugin.as<uint32_t>();
+        V.rec = soa_of(s).rec;
+        V.class_ok = g.class_ok.as<uint8_t>();
+        V.codes = g.csi_cols.as<uint16_t>() + k * (size_t)n_rows;
+        HIP_TRY_STATE(s, pe_launch_csi_codes(&V, s->stream));
+        s->csi_avail_launches++;
+    }
+    return PE_OK;
+}
+
+// What pe_inplace_update_csi's maps need beside the walk's codes: each update's
+// alloc index and record set.
+struct InplaceCsi {
+    const uint32_t* alloc_idx;   // by list position, or null: the group's index
+    const uint8_t* set_of;
+    const CsiRecSet* sets;
+};
+
 // pe_inplace_update_metrics' maps from what the walk left by
 // list position: `code` (k_trace's code space) and `named` (k_trace's six
 // score values) beside the statuses. The FeasibilityWrapper reasons are the
@@ -8744,8 +8839,14 @@ static int inplace_csr_set(pe_stack* s, const std::vector<std::pair<uint32_t, st
 // later ones "computed class ineligible", escaped constraints are decided per
 // node), which also leaves the memo where that sequence leaves it. A device
 // status that disagrees with the walk is the kTrMismatch guard.
+//
+// `csi` (pe_inplace_update_csi): a kTrCsi code is a node that
+// passed the wrapper, so the walk advanced the shadow for it as for any such
+// node, and failed the CSI checker, which records FilterNode(node, reason
+// text) itself (feasible.go:251-259): the keys pe_place_csi_metrics interns.
 static int inplace_metrics_finish(pe_stack* s, TgPlan& g, uint32_t n, const uint8_t* status, const uint32_t* code,
-                                  const double* named, bool evicting, const std::string& fn) {
+                                  const double* named, bool evicting, const std::string& fn,
+                                  const InplaceCsi* csi = nullptr) {
     std::vector<uint8_t> pass(n, 0);
     std::vector<uint32_t> why(n, PE_NONE), passed;
     {
@@ -8781,6 +8882,15 @@ static int inplace_metrics_finish(pe_stack* s, TgPlan& g, uint32_t n, const uint
         }
         if (status[i] == 2 && base == pe::kTrOption) {   // BinPack with evict gave the node up without ExhaustedNode
             if (!evicting) return mismatch();
+            continue;
+        }
+        if (base == pe::kTrCsi) {   // CSIVolumeChecker's own FilterNode
+            const uint32_t c16 = (code[i] >> 8) & 0xFFFFu, q = c16 >> 3, reason = c16 & 7u;
+            if (!csi || status[i] != 1) return mismatch();
+            const uint32_t idx = csi->alloc_idx ? csi->alloc_idx[i] : g.csi_idx;
+            const uint32_t plugin = q < (uint32_t)pe::kMaxCsiReq ? csi->sets[csi->set_of[i]].req[q].plugin : PE_NONE;
+            if (!csi_reason_key(s, g, q, reason, idx, plugin, row, &e.reason_key)) return mismatch();
+            e.class_key = MetricAcc::mclass(s, row);
             continue;
         }
         uint32_t kind, key;
@@ -8879,11 +8989,19 @@ static int inplace_spread_inputs(pe_stack* s, TgPlan& g, const uint32_t* allocs,
 // forms: codes and named scores by list position sit behind the statuses in
 // the same result buffer and come back in the same DMA;
 // inplace_metrics_finish turns them into the updates' maps.
+//
+// `csi_call`: pe_inplace_update_csi, a spr_call that does not
+// refuse a group with CSI requests. `alloc_idx` (or null: the group's index)
+// is each update's name index. One code column per distinct record set of the
+// list (k_csi_avail, store-only) and a set index by list position go to the
+// walks, which run on the verdict without CSI and filter an update whose node
+// passes the wrapper and has a code.
 static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
                               uint8_t* status, uint32_t* updated, bool pre_call, bool met_call = false,
-                              bool spr_call = false) {
+                              bool spr_call = false, bool csi_call = false, const uint32_t* alloc_idx = nullptr) {
     if (!s) return PE_EINVAL;
-    const std::string fn = spr_call ? "pe_inplace_update_spread: "
+    const std::string fn = csi_call ? "pe_inplace_update_csi: "
+                           : spr_call ? "pe_inplace_update_spread: "
                            : met_call ? "pe_inplace_update_metrics: "
                                       : (pre_call ? "pe_inplace_update_preempt: " : "pe_inplace_update: ");
     const bool metrics = met_call && s->metrics_on;
@@ -8928,8 +9046,23 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
         if (!why && c.op == "distinct_property") why = "distinct_property";
     if (why) return s->fail(PE_EUNSUPPORTED, fn + why);
     if (!g.unsupported.empty()) return s->fail(PE_EUNSUPPORTED, g.unsupported);
-    if (csi_active(g)) return s->fail(PE_EUNSUPPORTED, fn + "CSI volumes");
+    const bool csi = csi_active(g);
+    if (csi && !csi_call) return s->fail(PE_EUNSUPPORTED, fn + "CSI volumes");
     if (!s->cores_unsupported.empty()) return s->fail(PE_EUNSUPPORTED, s->cores_unsupported);
+    // the distinct record sets of the list and each update's column (csi), all on the host
+    std::vector<CsiRecSet> csi_sets;
+    std::vector<uint8_t> csi_set_of;
+    if (csi) {
+        if (!g.escaped) {   // the classes' verdicts as build_tables classifies them: no state of the handle moves
+            pe::ConstraintEvaluator ev;
+            if (g.sig_tg.size() != s->sig_rep.size()) g.sig_tg.clear();
+            classify_classes(s, g, ev);
+            if (!g.nonuniform.empty())
+                return s->fail(PE_EUNSUPPORTED, "CSI volumes with computed classes whose nodes differ in the group's checks");
+        }
+        if (!csi_record_sets(s, g, alloc_idx, n, csi_sets, csi_set_of))
+            return s->fail(PE_EUNSUPPORTED, fn + "more than 8 distinct CSI record sets in one call");
+    }
     // the eviction walk: what evict_eval would flag kEvictUnsup for (a device
     // ask: PreemptForDevice, and the old alloc's instances stay with it,
     // util.go:767-782, while a preempting Select would offer instances whose
@@ -9081,6 +9214,21 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     A.out = out ? reinterpret_cast<pe::EmitRec*>(dres) : nullptr;
     A.status = dres + st_off;
     if (spread) A.tg.n_psets = A.tg.n_spread = 0;   // the walk's view: no spread sets
+    if (csi) {
+        // prepare_tg left node_ok / node_feas as build_tables folds them: the verdict without CSI
+        // (csi_base_ok and the class table); the group stays dirty for the next Select's fold
+        const uint32_t n_rows = (uint32_t)s->nodes.size();
+        rc = flush_fold(s);   // the class table reaches the device with the group's fold
+        if (rc) return rc;
+        HIP_TRY(s, g.csi_cols.ensure(sizeof(uint16_t) * (size_t)n_rows * csi_sets.size()));
+        HIP_TRY(s, upload_s(s, s->d_inplace_csi_set, csi_set_of));
+        rc = csi_launch_columns(s, g, csi_sets);
+        if (rc) return rc;
+        A.tg.node_ok = g.csi_base_ok.as<uint8_t>();
+        A.csi_codes = g.csi_cols.as<uint16_t>();
+        A.csi_set = s->d_inplace_csi_set.as<uint8_t>();
+        A.csi_rows = n_rows;
+    }
     if (stage2 && !out) {   // the maps alone: the score parts still pass through records
         HIP_TRY(s, s->d_inplace_sp_rec.ensure(sizeof(pe::EmitRec) * (size_t)n));
         A.out = s->d_inplace_sp_rec.as<pe::EmitRec>();
@@ -9225,10 +9373,15 @@ static int inplace_update_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
         rc = inplace_csr_set(s, evicted);
         if (rc) return rc;
     }
+    const InplaceCsi csi_view{alloc_idx, csi_set_of.data(), csi_sets.data()};
     if (metrics) {
         rc = inplace_metrics_finish(s, g, n, status, reinterpret_cast<const uint32_t*>(h + code_off),
-                                    reinterpret_cast<const double*>(h + named_off), evicting, fn);
+                                    reinterpret_cast<const double*>(h + named_off), evicting, fn, csi ? &csi_view : nullptr);
         if (rc) return rc;
+    }
+    if (csi && alloc_idx && alloc_idx[n - 1] != g.csi_idx) {   // the alloc index the last Select's SetVolumes left
+        g.csi_idx = alloc_idx[n - 1];
+        g.csi_dirty = true;
     }
     if (updated) *updated = up;
     s->offer_row = -1;
@@ -10773,6 +10926,22 @@ int pe_inplace_update_spread(pe_stack* s, uint32_t tgi, const uint32_t* allocs, 
     return inplace_update_one(s, tgi, allocs, n, out, status, updated, true, true, true);
 }
 
+int pe_inplace_update_csi(pe_stack* s, uint32_t tgi, const uint32_t* allocs, const uint32_t* alloc_idx, uint32_t n,
+                          pe_ranked_node* out, uint8_t* status, uint32_t* updated) {
+    PE_FLUSH_RESET(s);
+    // a group without CSI requests: the call is pe_inplace_update_spread (a group that has
+    // them but no table is refused there as pe_select refuses it)
+    if (!s || !s->have_job || tgi >= s->tgs.size() || !csi_active(*s->tgs[tgi]))
+        return inplace_update_one(s, tgi, allocs, n, out, status, updated, true, true, true);
+    CsiScope csi_scope_(s);
+    struct Defer {   // prepare_tg leaves the fold of one alloc index to the next Select
+        pe_stack* s;
+        explicit Defer(pe_stack* st) : s(st) { s->csi_defer = true; }
+        ~Defer() { s->csi_defer = false; }
+    } defer_(s);
+    return inplace_update_one(s, tgi, allocs, n, out, status, updated, true, true, true, true, alloc_idx);
+}
+
 int pe_inplace_spread_ms(const pe_stack* s, double* ms2) {
     if (!s || !ms2) return PE_EINVAL;
     ms2[0] = s->inplace_stage_ms[0];
@@ -10834,7 +11003,6 @@ int pe_place(pe_stack* s, uint32_t tgi, uint32_t count, pe_ranked_node* out, uin
 // the call (codes only, into device columns), k_csi_first for the stop rule's
 // F[c], and k_csi_loop, which answers every Select including those pe_select
 // hands back (a stop while LimitIterator holds skipped options).
-struct CsiRecSet { pe::CsiReq req[pe::kMaxCsiReq]; };   // one alloc index's resolved request records
 static int csi_place_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec, const pe_ranked_node* recs,
                           const uint32_t* alloc_idx, const uint8_t* set_of, const CsiRecSet* sets, double t_loop0);
 
@@ -10894,31 +11062,10 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
     if (!count) return PE_OK;
     const uint32_t n_rows = (uint32_t)s->nodes.size(), m = (uint32_t)s->visit.size();
     // the distinct record sets of the call, and each placement's column
-    using RecSet = CsiRecSet;
-    std::vector<RecSet> sets;
-    std::vector<uint8_t> set_of(count, 0);
-    {
-        bool per_alloc = false;
-        for (const pe_csi_request& r : g.csi_reqs) per_alloc = per_alloc || r.per_alloc;
-        std::map<uint32_t, uint8_t> by_idx;
-        for (uint32_t i = 0; i < count; i++) {
-            const uint32_t idx = alloc_idx && per_alloc ? alloc_idx[i] : g.csi_idx;
-            auto it = by_idx.find(idx);
-            if (it == by_idx.end()) {
-                RecSet rs;
-                csi_resolve(s, g, idx, rs.req);
-                size_t k = 0;
-                while (k < sets.size() && std::memcmp(sets[k].req, rs.req, sizeof(rs.req)) != 0) k++;
-                if (k == sets.size()) {
-                    if (sets.size() == (size_t)pe::kMaxCsiSets)
-                        return s->fail(PE_EUNSUPPORTED, "pe_place_csi: more than 8 distinct CSI record sets in one call");
-                    sets.push_back(rs);
-                }
-                it = by_idx.emplace(idx, (uint8_t)k).first;
-            }
-            set_of[i] = it->second;
-        }
-    }
+    std::vector<CsiRecSet> sets;
+    std::vector<uint8_t> set_of;
+    if (!csi_record_sets(s, g, alloc_idx, count, sets, set_of))
+        return s->fail(PE_EUNSUPPORTED, "pe_place_csi: more than 8 distinct CSI record sets in one call");
     // ---- nothing is refused from here on ----
     s->gen++;
     s->metrics_valid = false;
@@ -10971,24 +11118,8 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
         const int frc = flush_fold(s);   // the class table reaches the device with the group's fold
         if (frc) return frc;
     }
-    for (size_t k = 0; k < sets.size(); k++) {
-        pe::CsiArgs V;
-        std::memset(&V, 0, sizeof(V));
-        V.n = n_rows;
-        V.n_req = (uint32_t)g.csi_reqs.size();
-        std::memcpy(V.req, sets[k].req, sizeof(V.req));
-        V.plug_off = s->csi.plug_off.as<uint32_t>();
-        V.plug_id = s->csi.plug_id.as<uint32_t>();
-        V.plug_healthy = s->csi.plug_healthy.as<uint8_t>();
-        V.plug_max = s->csi.plug_max.as<int64_t>();
-        V.nvol_off = s->csi.nvol_off.as<uint32_t>();
-        V.nvol_plugin = s->csi.nvol_plugin.as<uint32_t>();
-        V.rec = soa_of(s).rec;
-        V.class_ok = g.class_ok.as<uint8_t>();
-        V.codes = g.csi_cols.as<uint16_t>() + k * (size_t)n_rows;
-        HIP_TRY_STATE(s, pe_launch_csi_codes(&V, s->stream));
-        s->csi_avail_launches++;
-    }
+    rc = csi_launch_columns(s, g, sets);
+    if (rc) return rc;
     pe::BatchArgs A = batch_args(s, g);
     // the verdict without CSI: class_ok[cls] && the column k_csi_avail folds into (never the folded bytes)
     A.tg.node_feas = nullptr;
@@ -11106,8 +11237,6 @@ static int csi_place_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec
     CsiWalk W;
     uint32_t off = start;
     uint64_t walked = 0;
-    std::string vol;
-    char text[512];
     for (uint32_t k = 0; k < n_rec; k++) {
         const uint32_t ev = recs[k].nodes_evaluated;
         if (walked + ev > (uint64_t)s->h_csi_log.bytes)
@@ -11120,24 +11249,11 @@ static int csi_place_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec
         const uint32_t idx = alloc_idx ? alloc_idx[k] : g.csi_idx;
         for (const auto& h : W.hits) {
             const uint32_t q = pe::csi_log_request(h.second), reason = pe::csi_log_reason(h.second);
-            if (q >= g.csi_reqs.size() || !reason)
-                return s->fail(PE_EINTERNAL, "k_csi_loop: a trace log byte names no request of the group");
-            const pe_csi_request& r = g.csi_reqs[q];
-            vol = s->S(r.source);
-            if (r.per_alloc) vol += "[" + std::to_string(idx) + "]";
-            const bool node_part = reason >= PE_CSI_NO_PLUGIN && reason <= PE_CSI_MAX_VOLUMES;
-            const char* plugin = node_part ? s->S(sets[set_of[k]].req[q].plugin).c_str() : "";
-            const char* node_id = node_part ? s->S(s->nodes[h.first].id).c_str() : "";
-            const int64_t need = pe::csi_reason_text(reason, plugin, vol.c_str(), node_id, text, sizeof(text));
-            if (need < 0) return s->fail(PE_EINTERNAL, "k_csi_loop: a trace log byte names no reason");
-            if ((size_t)need <= sizeof(text)) {
-                acc[k].filter(s, h.first, s->mkey(text));
-            } else {   // a long id: the text in full
-                std::string full((size_t)need, '\0');
-                pe::csi_reason_text(reason, plugin, vol.c_str(), node_id, full.data(), full.size());
-                full.resize((size_t)need - 1);
-                acc[k].filter(s, h.first, s->mkey(full));
-            }
+            uint32_t key;
+            if (!csi_reason_key(s, g, q, reason, idx, q < g.csi_reqs.size() ? sets[set_of[k]].req[q].plugin : PE_NONE,
+                                h.first, &key))
+                return s->fail(PE_EINTERNAL, "k_csi_loop: a trace log byte names no request of the group or no reason");
+            acc[k].filter(s, h.first, key);
         }
         R.rsrc[k] = (uint32_t)x0;
         R.rec_end[k] = (uint32_t)R.xrows.size();

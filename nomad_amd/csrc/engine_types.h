@@ -31,6 +31,8 @@ enum : uint32_t {
     kTrOption = 0, kTrDistinctHosts = 1, kTrDistinctProp = 2,
     kTrWrapper = 3,             // k_inplace's metrics form only: the folded FeasibilityWrapper verdict
                                 // filtered the node (the reason is the host walk's)
+    kTrCsi = 4,                 // k_inplace's metrics form only (pe_inplace_update_csi): the node passed the
+                                // wrapper's checks and failed the CSI checker; bits 8..23 hold the PE_CSI_* code
     kTrNoAddr = 10, kTrDynPorts = 11, kTrNoNetworks = 12, kTrBandwidth = 13, kTrTaskDyn = 14,
     kTrStaticPort = 15,         // the reason string is rebuilt on the host (static_port_reason)
     kTrTaskStatic = 16,         // the task network's static ports (task_port_reason)
@@ -598,6 +600,12 @@ struct InplaceArgs {
     double log10;
     EmitRec* out;                     // [n] by list position, or null
     uint8_t* status;                  // [n] by list position: 0 updated, 1 filtered, 2 exhausted
+    // pe_inplace_update_csi, or null: k_csi_avail's code columns, one per distinct
+    // record set of the call, and each update's column. A node that passes the wrapper's checks
+    // with a code other than 0 is filtered before distinct_hosts and BinPack.
+    const uint16_t* csi_codes;        // [n_sets][csi_rows]
+    const uint8_t* csi_set;           // [n] by list position (< n_sets)
+    uint32_t csi_rows;                // snapshot rows: a column's stride
 };
 
 // pe_inplace_update_preempt: the stopping form of the walk

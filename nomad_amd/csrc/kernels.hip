@@ -4932,6 +4932,13 @@ __device__ __forceinline__ uint32_t wave_slot(uint32_t* counter);
 // values in k_trace's layout, from the record's own score_into call, whether or
 // not records were asked for. With kStop an exhausted plain fit is not final
 // and records nothing.
+//
+// kCsi (pe_inplace_update_csi): an update whose node passes the
+// wrapper's checks and has a code in its record set's column is filtered before
+// distinct_hosts and the fit (inplace_csi_code below): status 1, a nil record,
+// the metrics form's code kTrCsi with the 16-bit code above it, no commit, and
+// with kStop no hand-off, so the eviction walk never sees the group because of
+// it. k_inplace_evict applies the same fold to the updates it re-runs.
 __device__ __forceinline__ uint32_t inplace_filter_code(const TgTables& t, uint32_t row, const NodeIn& in) {
     bool ok;
     if (t.node_feas) ok = in.feas != 0;
@@ -4949,6 +4956,22 @@ __device__ __forceinline__ uint32_t inplace_exhaust_code(const NodeSoA& s, const
     return code == kTrOption ? (uint32_t)kTrMismatch : code;
 }
 
+// pe_inplace_update_csi: the update's PE_CSI_* code where the
+// CSI checker is the one that fails its Select, else 0. The checker runs behind
+// the wrapper's job and group checks (feasible.go:1141-1149) and reads the
+// snapshot alone, so the code is a 2-byte load from the column of the update's
+// record set; a node the wrapper filters keeps the wrapper's reason. kCsi is a
+// template parameter of the walks and not a null test: the walks sit at a VGPR
+// step, and the test alone cost the other forms 32 bytes of scratch per lane.
+template <bool kCsi>
+__device__ __forceinline__ uint32_t inplace_csi_code(const InplaceArgs& A, uint32_t pos, uint32_t row,
+                                                     const NodeIn& in) {
+    if (!kCsi) return 0u;
+    const uint32_t code = A.csi_codes[(size_t)A.csi_set[pos] * A.csi_rows + row];
+    if (!code) return 0u;
+    return inplace_filter_code(A.tg, row, in) == kTrWrapper ? 0u : code;
+}
+
 // score_into's parts (append order) by scorer, as k_trace names them.
 __device__ __forceinline__ void inplace_named(const Ask& a, const ScoreIn& si, const double* parts, double norm,
                                               double* o) {
@@ -4962,7 +4985,7 @@ __device__ __forceinline__ void inplace_named(const Ask& a, const ScoreIn& si, c
     o[5] = norm;
 }
 
-template <bool kStop, bool kMetrics>
+template <bool kStop, bool kMetrics, bool kCsi>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
 k_inplace(InplaceArgs A, InplaceStopArgs S, InplaceMetricsArgs M) {
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -4993,7 +5016,9 @@ k_inplace(InplaceArgs A, InplaceStopArgs S, InplaceMetricsArgs M) {
             if (x.flags & kInplaceOwnTg) t.coll_tg -= 1u;
             if (tj != cj) A.soa.coll_job[row] = tj;   // DistinctHostsIterator reads the column
             ScoreIn si;
-            const int st = status_loaded<false>(A.soa, A.tg, A.tg.class_ok, A.ask, 0u, row, t, &si);
+            int st = status_loaded<false>(A.soa, A.tg, A.tg.class_ok, A.ask, 0u, row, t, &si);
+            const uint32_t csi = inplace_csi_code<kCsi>(A, x.pos, row, t);
+            if (csi) st = kFiltered;   // unavailable: no fit is tried, nothing is handed to the eviction walk
             if (kStop && st == kExhausted) {   // the eviction walk takes the group from here
                 if (tj != cj) A.soa.coll_job[row] = cj;
                 S.resume[g] = u;
@@ -5018,6 +5043,7 @@ k_inplace(InplaceArgs A, InplaceStopArgs S, InplaceMetricsArgs M) {
             }
             if (kMetrics)
                 M.code[x.pos] = st == kOption ? (uint32_t)kTrOption
+                                : csi        ? (uint32_t)kTrCsi | csi << 8
                                 : (st == kFiltered ? inplace_filter_code(A.tg, row, t)
                                                    : inplace_exhaust_code(A.soa, A.tg, A.ask, row, t));
             if (st != kOption) {
@@ -5134,7 +5160,7 @@ __device__ __forceinline__ void inplace_store(const InplaceArgs& A, uint32_t row
 // ScoreNode values and the dimension of an update that stays exhausted (0: it
 // gave the node up without ExhaustedNode). All by list position, so a relaunch
 // at a wider width rewrites the same words.
-template <int W, bool kMetrics>
+template <int W, bool kMetrics, bool kCsi>
 __global__ void __launch_bounds__(256) k_inplace_evict(InplaceEvictArgs V, InplaceMetricsArgs M) {
     const InplaceArgs& A = V.I;
     const uint32_t n = *V.n_stopped;
@@ -5172,6 +5198,8 @@ __global__ void __launch_bounds__(256) k_inplace_evict(InplaceEvictArgs V, Inpla
             if (tj != cj) A.soa.coll_job[row] = tj;   // DistinctHostsIterator reads the column
             ScoreIn si;
             int st = status_loaded<false>(A.soa, A.tg, A.tg.class_ok, A.ask, 0u, row, t, &si);
+            const uint32_t csi = inplace_csi_code<kCsi>(A, x.pos, row, t);
+            if (csi) st = kFiltered;   // unavailable: no eviction is tried for this update
             double final_score = 0.0, parts[PE_MAX_SCORES];
             uint32_t ns = 0, exhausted = st == kExhausted;
             uint32_t mcode = kTrOption;   // (kMetrics)
@@ -5181,7 +5209,7 @@ __global__ void __launch_bounds__(256) k_inplace_evict(InplaceEvictArgs V, Inpla
                 final_score = score_into<true>(A.ask, A.log10, si, parts, &ns);
                 if (kMetrics) inplace_named(A.ask, si, parts, final_score, M.named + (size_t)x.pos * kInplaceNamed);
             } else if (kMetrics && st == kFiltered) {
-                mcode = inplace_filter_code(A.tg, row, t);
+                mcode = csi ? (uint32_t)kTrCsi | csi << 8 : inplace_filter_code(A.tg, row, t);
             } else if (st == kExhausted) {
                 // the trial, where evict_eval reads it
                 inplace_store(A, row, t);
@@ -6114,18 +6142,27 @@ hipError_t pe_launch_system(const pe::SystemArgs* a, hipStream_t st) {
     return hipGetLastError();
 }
 
+// The code columns of pe_inplace_update_csi come with their set index and span the snapshot's rows.
+static bool inplace_csi_args_ok(const pe::InplaceArgs* a) {
+    return !a->csi_codes || (a->csi_set && a->csi_rows == a->soa.n);
+}
+
 // `m` (or null): the metrics form (pe_inplace_update_metrics with AllocMetric on).
 hipError_t pe_launch_inplace(const pe::InplaceArgs* a, const pe::InplaceMetricsArgs* m, hipStream_t st) {
     if (!a->n_groups) return hipSuccess;
+    if (!inplace_csi_args_ok(a)) return hipErrorInvalidValue;
     uint32_t blocks = (a->n_groups + 255) / 256;
     if (blocks > 2048) blocks = 2048;   // grid-stride beyond
     const pe::InplaceStopArgs none{nullptr, nullptr, nullptr, nullptr};
-    if (m) {
-        if (!m->code || !m->named) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((pe::k_inplace<false, true>), dim3(blocks), dim3(256), 0, st, *a, none, *m);
+    const pe::InplaceMetricsArgs nom{nullptr, nullptr};
+    if (m && (!m->code || !m->named)) return hipErrorInvalidValue;
+    if (a->csi_codes) {   // pe_inplace_update_csi
+        if (m) hipLaunchKernelGGL((pe::k_inplace<false, true, true>), dim3(blocks), dim3(256), 0, st, *a, none, *m);
+        else hipLaunchKernelGGL((pe::k_inplace<false, false, true>), dim3(blocks), dim3(256), 0, st, *a, none, nom);
+    } else if (m) {
+        hipLaunchKernelGGL((pe::k_inplace<false, true, false>), dim3(blocks), dim3(256), 0, st, *a, none, *m);
     } else {
-        hipLaunchKernelGGL((pe::k_inplace<false, false>), dim3(blocks), dim3(256), 0, st, *a, none,
-                           pe::InplaceMetricsArgs{nullptr, nullptr});
+        hipLaunchKernelGGL((pe::k_inplace<false, false, false>), dim3(blocks), dim3(256), 0, st, *a, none, nom);
     }
     return hipGetLastError();
 }
@@ -6136,12 +6173,18 @@ hipError_t pe_launch_inplace_stop(const pe::InplaceArgs* a, const pe::InplaceSto
     if (!a->n_groups) return hipSuccess;
     if (!s->resume || !s->stopped || !s->n_stopped || !s->own_existing) return hipErrorInvalidValue;
     if (m && (!m->code || !m->named)) return hipErrorInvalidValue;
+    if (!inplace_csi_args_ok(a)) return hipErrorInvalidValue;
     uint32_t blocks = (a->n_groups + 255) / 256;
     if (blocks > 2048) blocks = 2048;   // grid-stride beyond
-    if (m) hipLaunchKernelGGL((pe::k_inplace<true, true>), dim3(blocks), dim3(256), 0, st, *a, *s, *m);
-    else
-        hipLaunchKernelGGL((pe::k_inplace<true, false>), dim3(blocks), dim3(256), 0, st, *a, *s,
-                           pe::InplaceMetricsArgs{nullptr, nullptr});
+    const pe::InplaceMetricsArgs nom{nullptr, nullptr};
+    if (a->csi_codes) {   // pe_inplace_update_csi
+        if (m) hipLaunchKernelGGL((pe::k_inplace<true, true, true>), dim3(blocks), dim3(256), 0, st, *a, *s, *m);
+        else hipLaunchKernelGGL((pe::k_inplace<true, false, true>), dim3(blocks), dim3(256), 0, st, *a, *s, nom);
+    } else if (m) {
+        hipLaunchKernelGGL((pe::k_inplace<true, true, false>), dim3(blocks), dim3(256), 0, st, *a, *s, *m);
+    } else {
+        hipLaunchKernelGGL((pe::k_inplace<true, false, false>), dim3(blocks), dim3(256), 0, st, *a, *s, nom);
+    }
     return hipGetLastError();
 }
 
@@ -6266,17 +6309,32 @@ hipError_t pe_launch_inplace_evict(const pe::InplaceEvictArgs* a, const pe::Inpl
         !a->n_wider || !a->app || !a->n_app || !a->flags || !a->I.status || !a->I.preempted || !a->I.allocs)
         return hipErrorInvalidValue;
     if (m && (!m->code || !m->named)) return hipErrorInvalidValue;
+    if (!inplace_csi_args_ok(&a->I)) return hipErrorInvalidValue;
     const uint32_t blocks = evict_blocks(max_groups, words);
     const pe::InplaceMetricsArgs none{nullptr, nullptr};
-    if (m) {
-        if (words == 1u) hipLaunchKernelGGL((pe::k_inplace_evict<1, true>), dim3(blocks), dim3(256), 0, st, *a, *m);
-        else if (words == 8u) hipLaunchKernelGGL((pe::k_inplace_evict<8, true>), dim3(blocks), dim3(256), 0, st, *a, *m);
-        else hipLaunchKernelGGL((pe::k_inplace_evict<32, true>), dim3(blocks), dim3(256), 0, st, *a, *m);
+    const pe::InplaceMetricsArgs& ma = m ? *m : none;
+#define PE_INPLACE_EVICT(W, MET, CSI) \
+    hipLaunchKernelGGL((pe::k_inplace_evict<W, MET, CSI>), dim3(blocks), dim3(256), 0, st, *a, ma)
+    if (a->I.csi_codes) {   // pe_inplace_update_csi
+        if (m) {
+            if (words == 1u) PE_INPLACE_EVICT(1, true, true);
+            else if (words == 8u) PE_INPLACE_EVICT(8, true, true);
+            else PE_INPLACE_EVICT(32, true, true);
+        } else {
+            if (words == 1u) PE_INPLACE_EVICT(1, false, true);
+            else if (words == 8u) PE_INPLACE_EVICT(8, false, true);
+            else PE_INPLACE_EVICT(32, false, true);
+        }
+    } else if (m) {
+        if (words == 1u) PE_INPLACE_EVICT(1, true, false);
+        else if (words == 8u) PE_INPLACE_EVICT(8, true, false);
+        else PE_INPLACE_EVICT(32, true, false);
     } else {
-        if (words == 1u) hipLaunchKernelGGL((pe::k_inplace_evict<1, false>), dim3(blocks), dim3(256), 0, st, *a, none);
-        else if (words == 8u) hipLaunchKernelGGL((pe::k_inplace_evict<8, false>), dim3(blocks), dim3(256), 0, st, *a, none);
-        else hipLaunchKernelGGL((pe::k_inplace_evict<32, false>), dim3(blocks), dim3(256), 0, st, *a, none);
+        if (words == 1u) PE_INPLACE_EVICT(1, false, false);
+        else if (words == 8u) PE_INPLACE_EVICT(8, false, false);
+        else PE_INPLACE_EVICT(32, false, false);
     }
+#undef PE_INPLACE_EVICT
     return hipGetLastError();
 }
 

@@ -89,6 +89,10 @@ def load_engine():
             lib.pe_inplace_update_spread.argtypes = lib.pe_inplace_update.argtypes
             lib.pe_inplace_spread_ms.restype = C.c_int
             lib.pe_inplace_spread_ms.argtypes = [C.c_void_p, abi.f64p]
+        if hasattr(lib, "pe_inplace_update_csi"):
+            lib.pe_inplace_update_csi.restype = C.c_int
+            lib.pe_inplace_update_csi.argtypes = [C.c_void_p, C.c_uint32, abi.u32p, abi.u32p, C.c_uint32,
+                                                  C.POINTER(abi.pe_ranked_node), abi.u8p, abi.u32p]
         if hasattr(lib, "pe_system_place_groups"):   # present or absent behind one ABI version
             lib.pe_system_place_groups.restype = C.c_int
             lib.pe_system_place_groups.argtypes = [C.c_void_p, abi.u32p, C.c_uint32, abi.f64p, abi.u8p, abi.u32p,
@@ -737,6 +741,49 @@ class _Stack:
         assert updated.value == sum(1 for r in records if r is not None)
         return records, [int(x) for x in status[:n]], (self.InplaceMetrics(status[:n]) if on else None)
 
+    def InplaceUpdateCSI(self, tg, allocs: Sequence[int], alloc_idx: Optional[Sequence[int]] = None,
+                         fallback: bool = True):
+        """InplaceUpdateSpread for a group that may carry CSI volume requests
+        (pe_inplace_update_csi): the in-place call for every group.
+        `alloc_idx[i]` is the name index of allocs[i], which per_alloc sources
+        take as their suffix for that update; None: the index CSIAllocIndex
+        holds. Returns (records, status, metrics) in InplaceUpdateSpread's
+        shape; an update whose node passes the job and group checks and is
+        unavailable for its volumes has status 1 and, with EnableMetrics on,
+        the CSI checker's reason. On a group without CSI requests the call is
+        InplaceUpdateSpread. A job the call refuses (Unsupported) is answered
+        by inplace_update_csi_by_select when `fallback`: the per-alloc
+        sequence with CSIAllocIndex before each Select (which, for a CSI group
+        with EnableMetrics on, Select itself refuses)."""
+        allocs = [int(a) for a in allocs]
+        n = len(allocs)
+        if alloc_idx is not None:
+            alloc_idx = [int(i) for i in alloc_idx]
+            if len(alloc_idx) != n:
+                raise ValueError("alloc_idx needs one index per listed alloc")
+        on = getattr(self, "_metrics_on", False)
+        try:
+            if not hasattr(self._lib, self._p + "inplace_update_csi"):
+                raise Unsupported(abi.PE_EUNSUPPORTED, "no batched in-place update with CSI volumes behind this ABI")
+            a = np.ascontiguousarray(np.asarray(allocs or [0], dtype=np.uint32))
+            idx = None
+            if alloc_idx is not None:
+                idx = np.ascontiguousarray(np.asarray(alloc_idx or [0], dtype=np.uint32))
+            out = (abi.pe_ranked_node * max(1, n))()
+            status = np.zeros(max(1, n), dtype=np.uint8)
+            updated = C.c_uint32(0)
+            self._check(self._fn("inplace_update_csi")(self._h, self._tg_index(tg), a.ctypes.data_as(abi.u32p),
+                                                       None if idx is None else idx.ctypes.data_as(abi.u32p), n,
+                                                       out, status.ctypes.data_as(abi.u8p), C.byref(updated)))
+        except Unsupported:
+            if not fallback:
+                raise
+            return inplace_update_csi_by_select(self, tg, allocs, alloc_idx, metrics=on)
+        full = SystemStack.InplaceUpdatePreempted(self)
+        records = [RankedNode.from_c(out[i], self.nodes, full.get(i)) if status[i] == 0 else None for i in range(n)]
+        assert updated.value == sum(1 for r in records if r is not None)
+        return records, [int(x) for x in status[:n]], (self.InplaceMetrics(status[:n]) if on else None)
+
     def inplace_stage_ms(self):
         """HIP-event times (ms) of the last InplaceUpdate* call: (the walk, the
         spread stage; 0.0 when it did not run)."""
@@ -1143,6 +1190,37 @@ def inplace_update_metrics_by_select(stack, tg, allocs: Sequence[int]):
             records.append(None)
             status.append(1 if r.nodes_filtered else 2)
     return records, status, metrics
+
+
+def inplace_update_csi_by_select(stack, tg, allocs: Sequence[int], alloc_idx: Optional[Sequence[int]] = None,
+                                 metrics: bool = False):
+    """inplace_update_by_select for a group with CSI volume requests: the
+    update's name index goes to the checker (CSIAllocIndex, SetVolumes with the
+    alloc's name) before its Select. `metrics`: LastMetrics() after each
+    Select, as inplace_update_metrics_by_select reads it. Returns (records,
+    status, metrics or None) in InplaceUpdateCSI's shape."""
+    node_row = stack.state.alloc_table.node_row
+    records, status, maps = [], [], []
+    for i, ai in enumerate(allocs):
+        ai = int(ai)
+        row = int(node_row[ai])
+        stack.StopAllocs([ai])
+        stack.SetNodes(np.asarray([row], dtype=np.uint32))
+        if alloc_idx is not None:
+            stack.CSIAllocIndex(tg, int(alloc_idx[i]))
+        r = stack.SelectRaw(tg)
+        if metrics:
+            maps.append(stack.LastMetrics())
+        stack.PopUpdate(ai)
+        if r.row >= 0:
+            stack.StopAllocs([ai])        # the in-place alloc replaces the old one (same ID)
+            stack.Commit(tg, r.row)
+            records.append(r)
+            status.append(0)
+        else:
+            records.append(None)
+            status.append(1 if r.nodes_filtered else 2)
+    return records, status, (maps if metrics else None)
 
 
 class GenericStack(_Stack):
