@@ -1099,12 +1099,39 @@ double pe_csi_last_ms(pe_stack* s);
  * the cursor, the limit, the memo and the plan untouched: pe_set_metrics on, a
  * handle over several devices, a system stack, a preempting stack, computed
  * classes whose nodes differ in the group's checks, a group that runs full
- * passes (affinities, spreads, distinct_property, a latched limit), whatever
+ * passes (affinities, spreads, distinct_property, a latched limit;
+ * pe_place_csi_full places all of these but distinct_property), whatever
  * pe_place refuses, more than PE_MAX_CSI_SETS distinct record sets, and a
  * count beyond the overlay of one launch. */
 #define PE_MAX_CSI_SETS 8
 int pe_place_csi(pe_stack* s, uint32_t tg_index, uint32_t count, const uint32_t* alloc_idx, pe_ranked_node* out,
                  uint32_t* placed);
+/* pe_place_csi for a group that runs full passes: node affinities or spreads at
+ * job or group level, or a limit an earlier Select of a sibling group latched
+ * to MaxInt32 (stack.go:165-167). Arguments, records and contract are
+ * pe_place_csi's: alloc_idx NULL means the held index, the failed Select's
+ * record is written, the group's alloc index afterwards is the last attempted
+ * placement's. Each Select may consume the whole list from the cursor, wrapping
+ * (StaticIterator.seen is reset per Select); it ends at a stop with no skipped
+ * option pending, or at the end of the list, and the next one starts after that
+ * position; a Select that starts on a stop is nil and ends the loop. Afterwards
+ * the cursor, the limit (latched as Select latches it), the memo, the plan,
+ * the property-set counts behind later spread scores and every record are what
+ * the reference chain leaves after computePlacements' loop. One launch of
+ * k_csi_full and one synchronisation per call, the k_csi_avail and k_csi_first
+ * launches as pe_place_csi.
+ * On every other group the call is pe_place_csi (and so pe_place without CSI
+ * requests). PE_EUNSUPPORTED, with cursor, limit, memo, plan and alloc index
+ * untouched: pe_place_csi's list without its full-pass row, distinct_property
+ * at job or group level (it filters above the wrapper), and spread values
+ * cleared by plan stops (the counts are rebuilt on the host per commit).
+ * pe_csi_place_ms then reports k_csi_full in ms2[1]. */
+int pe_place_csi_full(pe_stack* s, uint32_t tg_index, uint32_t count, const uint32_t* alloc_idx, pe_ranked_node* out,
+                      uint32_t* placed);
+/* Lanes of k_csi_full's one workgroup: a placement's passes take the visit list
+ * in chunks of this many positions (tests choose list lengths around it).
+ * Stateless, needs no device. */
+uint32_t pe_csi_full_block(void);
 /* pe_place_csi with AllocMetric kept: what GenericScheduler.computePlacements
  * stores per placed alloc and, for the nil Select that ends the loop, in
  * failedTGAllocs (generic_sched.go:552-627).
@@ -1178,6 +1205,14 @@ int pe_csi_place_ms(pe_stack* s, double* ms2);
  * at a nil Next rather than at seen == limit. */
 int pe_csi_limit_fold(const double* scores, const uint8_t* kind, uint32_t n, uint32_t limit, int32_t* winner,
                       uint32_t* seen, uint32_t* consumed, uint32_t* ended_nil);
+/* The same fold at limit MaxInt32 as pe_place_csi_full's kernel runs it: the
+ * stream is compressed to its first 7 nils, its first 6 non-positive options
+ * and the collapsed runs of options between them (csi_limit.h), and those are
+ * stepped. Outputs as pe_csi_limit_fold(..., limit = 0x7FFFFFFF), which it
+ * equals on every stream; PE_EINTERNAL if a bound of the compression does not
+ * hold. Needs no device. */
+int pe_csi_full_fold(const double* scores, const uint8_t* kind, uint32_t n, int32_t* winner, uint32_t* seen,
+                     uint32_t* consumed, uint32_t* ended_nil);
 /* Host-side constraint semantics used for pre-resolution (checkConstraint,
  * feasible.go:785-820), exposed for known-answer tests; needs no device.
  * l_state / r_state: 0 nil (unknown ${...} target), 1 found, 2 missing ("", false). */

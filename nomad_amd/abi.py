@@ -248,6 +248,11 @@ def bind_csi(lib):
     lib.pe_place_csi_metrics_stats.restype = C.c_int
     lib.pe_place_csi_metrics_stats.argtypes = [H, f64p, C.POINTER(C.c_uint64)]
     bind_csi_reason_text(lib)
+    if not hasattr(lib, "pe_place_csi_full"):   # (an A/B library from before the full-pass form)
+        return lib
+    lib.pe_place_csi_full.restype = C.c_int
+    lib.pe_place_csi_full.argtypes = [H, C.c_uint32, C.c_uint32, u32p, C.POINTER(pe_ranked_node), u32p]
+    bind_csi_full_fold(lib)
     return lib
 
 
@@ -266,6 +271,13 @@ def bind_csi_limit_fold(lib):
     """pe_csi_limit_fold: stateless, needs no device (any loaded libnomadpe.so)."""
     lib.pe_csi_limit_fold.restype = C.c_int
     lib.pe_csi_limit_fold.argtypes = [f64p, u8p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), u32p, u32p, u32p]
+    return lib
+
+
+def bind_csi_full_fold(lib):
+    """pe_csi_full_fold: stateless, needs no device (any loaded libnomadpe.so)."""
+    lib.pe_csi_full_fold.restype = C.c_int
+    lib.pe_csi_full_fold.argtypes = [f64p, u8p, C.c_uint32, C.POINTER(C.c_int32), u32p, u32p, u32p]
     return lib
 
 
@@ -314,6 +326,7 @@ ENGINE_SYMBOLS = [
     "pe_inplace_update_spread", "pe_inplace_spread_ms", "pe_inplace_update_csi",
     "pe_place_csi", "pe_csi_avail_launches", "pe_csi_place_ms", "pe_csi_limit_fold",
     "pe_place_csi_metrics", "pe_place_csi_maps", "pe_place_csi_metrics_stats", "pe_csi_reason_text",
+    "pe_place_csi_full", "pe_csi_full_fold", "pe_csi_full_block",
 ]
 
 

@@ -7,7 +7,9 @@
 //
 // The fold is written once, as a state machine stepped with one source event
 // at a time: k_csi_loop steps it on the device, pe_csi_limit_fold on the host
-// (the tests' entry), and both run these lines.
+// (the tests' entry), and both run these lines. At limit MaxInt32 runs of
+// options collapse into one event each (below: csi_limit_run, csi_full_fold),
+// which k_csi_full and pe_csi_full_fold run.
 //
 // LimitIterator.Next calls source.Next() at three places; the phase says which
 // one the next event answers:
@@ -103,6 +105,120 @@ PE_CSI_HD bool csi_limit_step(CsiLimit& L, uint32_t kind, double score, int32_t 
     if (L.best_id < 0 || score > L.best_score) { L.best_score = score; L.best_id = id; }
     L.phase = kCsiTop;
     return L.seen == L.limit;
+}
+
+// ---- the fold at an unbounded limit (k_csi_full, pe_csi_full_fold) --------------------
+// At limit MaxInt32 (stack.go:165-167) `seen == limit` never fires, and two
+// facts of csi_limit_step make the event stream compressible: an option with
+// score > threshold is returned in every phase, and once n_skip == kCsiMaxSkip
+// every option is returned. A maximal run of consecutive such options (no nil
+// inside) therefore equals one option event that carries the run's first
+// strict maximum and its id: phase, n_skip, pop, best_* and ended_nil come out
+// identical, and `seen` grows by the run's length, minus one when the run
+// starts in kCsiAfter (that Next was counted when the skip loop ended).
+//
+// What is still stepped one at a time (the specials): nils, and non-positive
+// options that arrive while n_skip < kCsiMaxSkip. Such an option is either
+// appended (at most kCsiMaxSkip appends, duplicates included) or returned at
+// kCsiAfter (once per append run), so there are at most kCsiFullOptions of
+// them per Select, and they are the first non-positive options of the stream.
+// A nil moves kCsiSkip -> kCsiAfter (once per append run), pops an entry (at
+// most kCsiMaxSkip) or ends the Select: at most kCsiFullNils per Select, so no
+// position past the kCsiFullNils-th nil is ever consumed.
+constexpr uint32_t kCsiUnbounded = 0x7FFFFFFFu;
+constexpr int kCsiFullOptions = 2 * kCsiMaxSkip;
+constexpr int kCsiFullNils = 2 * kCsiMaxSkip + 1;
+constexpr int kCsiFullSpecials = kCsiFullOptions + kCsiFullNils;
+
+// `count` consecutive options, each of which csi_limit_step would return
+// (score > threshold, or n_skip == kCsiMaxSkip), as one event: (score, id) is
+// the run's first strict maximum. For a fold at limit kCsiUnbounded only.
+PE_CSI_HD void csi_limit_run(CsiLimit& L, uint32_t count, double score, int32_t id) {
+    if (count == 0) return;
+    L.seen += count - (L.phase == kCsiAfter ? 1u : 0u);
+    if (L.best_id < 0 || score > L.best_score) { L.best_score = score; L.best_id = id; }
+    L.phase = kCsiTop;
+}
+
+struct CsiSpecial {     // an event stepped on its own, at source position `pos`
+    uint32_t pos, kind; // kCsiNil, or kCsiOption with a score <= threshold
+    double score;
+};
+struct CsiSegment {     // the positions between two specials, collapsed
+    uint32_t options;   // options among them
+    uint32_t nonpos;    // of which score <= threshold
+    int32_t id;         // first strict maximum over the options
+    uint32_t _pad;
+    double score;
+};
+
+// One Select at limit kCsiUnbounded over specials in position order and the
+// collapsed segments around them: seg[i] precedes sp[i], seg[n_spec] follows
+// the last special up to the end of the source. `closed`: the source was cut
+// after its kCsiFullNils-th nil, which is sp[n_spec - 1] (no seg[n_spec]).
+// Returns 0 when the Select ended at special *ended_at, 1 when it ended at the
+// nils after the source's last position, -1 when a bound above does not hold
+// (a non-positive option inside a segment entered with n_skip < kCsiMaxSkip,
+// a closed source that did not end the Select, tail nils that did not).
+PE_CSI_HD int csi_full_fold(CsiLimit& L, const CsiSegment* seg, const CsiSpecial* sp, uint32_t n_spec, bool closed,
+                            uint32_t* ended_at) {
+    csi_limit_init(L, kCsiUnbounded);
+    if (n_spec > (uint32_t)kCsiFullSpecials) return -1;
+    for (uint32_t i = 0; i <= n_spec; i++) {
+        if (i < n_spec || !closed) {
+            const CsiSegment g = seg[i];
+            if (g.options) {
+                if (g.nonpos && L.n_skip < (uint32_t)kCsiMaxSkip) return -1;
+                csi_limit_run(L, g.options, g.score, g.id);
+            }
+        }
+        if (i == n_spec) break;
+        if (csi_limit_step(L, sp[i].kind, sp[i].score, (int32_t)sp[i].pos)) {
+            *ended_at = i;
+            return 0;
+        }
+    }
+    if (closed) return -1;
+    for (int t = 0; t < kCsiTailEvents; t++)
+        if (csi_limit_step(L, kCsiNil, 0.0, -1)) {
+            *ended_at = n_spec;
+            return 1;
+        }
+    return -1;
+}
+
+// The compression of a plain stream, as k_csi_full's passes do it: the first
+// kCsiFullNils nils, the first kCsiFullOptions non-positive options before the
+// last of those nils, and per segment between them the option count, the
+// non-positive count and the first strict maximum. Item i is an option with
+// scores[i] (kind 0) or a nil (kind 1). seg has kCsiFullSpecials + 1 entries,
+// sp kCsiFullSpecials. Returns the number of specials; *closed as above.
+inline uint32_t csi_full_compress(const double* scores, const uint8_t* kind, uint32_t n, CsiSegment* seg,
+                                  CsiSpecial* sp, bool* closed, double threshold = 0.0) {
+    uint32_t end = n, nils = 0;
+    for (uint32_t i = 0; i < n && nils < (uint32_t)kCsiFullNils; i++)
+        if (kind[i] && ++nils == (uint32_t)kCsiFullNils) end = i + 1;
+    *closed = nils == (uint32_t)kCsiFullNils;
+    uint32_t n_spec = 0, n_np = 0;
+    CsiSegment cur = {0, 0, -1, 0, 0.0};
+    for (uint32_t i = 0; i < end; i++) {
+        const bool np = !kind[i] && scores[i] <= threshold;
+        if (kind[i] || (np && n_np < (uint32_t)kCsiFullOptions)) {
+            seg[n_spec] = cur;
+            cur = CsiSegment{0, 0, -1, 0, 0.0};
+            sp[n_spec].pos = i;
+            sp[n_spec].kind = kind[i] ? kCsiNil : kCsiOption;
+            sp[n_spec].score = kind[i] ? 0.0 : scores[i];
+            n_spec++;
+            n_np += np ? 1u : 0u;
+            continue;
+        }
+        if (cur.options == 0 || scores[i] > cur.score) { cur.score = scores[i]; cur.id = (int32_t)i; }
+        cur.options++;
+        cur.nonpos += np ? 1u : 0u;
+    }
+    seg[n_spec] = cur;
+    return n_spec;
 }
 
 }  // namespace pe

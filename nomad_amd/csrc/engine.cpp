@@ -473,6 +473,8 @@ struct TgPlan {
     // memory, nothing copied back), the column of each placement, the class
     // states of the stop rule and F[c]
     DevMem csi_cols, csi_set_of, csi_cls_state, csi_first;
+    // pe_place_csi_full: k_csi_full's per-position scores and classes of one placement
+    DevMem csi_full_score, csi_full_kind;
 };
 
 // A group with has_csi_volumes is refused with this text until it has both a
@@ -11009,8 +11011,11 @@ static int csi_place_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec
 // `metrics` (pe_place_csi_metrics with AllocMetric on): k_csi_loop<true> logs the
 // checker's verdict per consumed position, and the records' maps follow from
 // the host walk and one batched trace against the checkpoint (csi_place_maps).
+// `full` (pe_place_csi_full): the group runs full passes (affinities, spreads or
+// a latched limit); k_csi_full answers the Selects, the limit is latched as
+// Select latches it, and the spread counts are written back with the overlay.
 static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32_t* alloc_idx, pe_ranked_node* out,
-                         uint32_t* placed, bool metrics = false) {
+                         uint32_t* placed, bool metrics = false, bool full = false) {
     // refusals, all before anything changes
     int rc = csi_refuse(s, nullptr, metrics);
     if (rc) return rc;
@@ -11039,13 +11044,14 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
         return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes on a system stack (pe_select and pe_system_place place them)");
     if (s->cfg.preempt)
         return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes on a preempting stack (the loop retries a nil Select with Preempt)");
-    {
+    if (!full) {
         TgPlan& g0 = *s->tgs[tgi];
         if (tg_full_scan(s, g0) || s->limit >= 0x7FFFFFFFu)
-            return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes in a group that runs full passes (affinities, spreads or a latched limit)");
+            return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes in a group that runs full passes (affinities, spreads or a latched limit; pe_place_csi_full places it)");
     }
-    const int hash_bits = hash_bits_for(count, false, 0);
-    if (((uint64_t)1 << hash_bits) < 2ull * std::max<uint32_t>(count, 1))   // (64 bits: no wrap for a huge count)
+    // (full: the overlay shares LDS with the spread tables, whose size is known once the group's tables are built)
+    int hash_bits = hash_bits_for(count, false, 0);
+    if (!full && ((uint64_t)1 << hash_bits) < 2ull * std::max<uint32_t>(count, 1))   // (64 bits: no wrap for a huge count)
         return s->fail(PE_EUNSUPPORTED, "pe_place_csi: count exceeds what the overlay of one launch holds");
     rc = spec_flush(s);
     if (rc) return rc;
@@ -11055,8 +11061,17 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
     TgPlan& g = *s->tgs[tgi];
     if (!g.escaped && !g.nonuniform.empty())
         return s->fail(PE_EUNSUPPORTED, "CSI volumes with computed classes whose nodes differ in the group's checks");
-    if (!g.psets.empty() || g.psets_dynamic)
+    if (full) {
+        if (g.n_spread != (int)g.psets.size())
+            return s->fail(PE_EUNSUPPORTED, "pe_place_csi_full: CSI volumes with distinct_property (it filters above the wrapper)");
+        if (g.psets_dynamic)
+            return s->fail(PE_EUNSUPPORTED, "pe_place_csi_full: plan stops clear spread values (the counts are rebuilt on the host after every commit)");
+        hash_bits = hash_bits_for(count, true, pset_lds_bytes(tables_of(g)));
+        if (((uint64_t)1 << hash_bits) < 2ull * std::max<uint32_t>(count, 1))
+            return s->fail(PE_EUNSUPPORTED, "pe_place_csi: count exceeds what the overlay of one launch holds");
+    } else if (!g.psets.empty() || g.psets_dynamic) {
         return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes in a group that runs full passes (distinct_property)");
+    }
     if (g.md_on)
         return s->fail(PE_EUNSUPPORTED, "pe_place_csi: CSI volumes with group networks on multi-device nodes");
     if (!count) return PE_OK;
@@ -11069,6 +11084,7 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
     // ---- nothing is refused from here on ----
     s->gen++;
     s->metrics_valid = false;
+    if (full && tg_full_scan(s, g)) s->limit = 0x7FFFFFFF;   // never reset until SetNodes (stack.go:165-167)
     const uint32_t start = s->offset;
     if (!m) {   // SetNodes([]): a nil Select
         std::memset(&out[0], 0, sizeof(out[0]));
@@ -11125,7 +11141,13 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
     A.tg.node_feas = nullptr;
     A.tg.node_ok = g.csi_base_ok.as<uint8_t>();
     A.hash_bits = hash_bits;
-    A.packed_overlay = packed_kbits(s, 1u << hash_bits, false);
+    A.packed_overlay = full ? 0 : packed_kbits(s, 1u << hash_bits, false);
+    if (full) {   // the spread tables and counts: LDS, or HBM beyond the budget (as run_place)
+        rc = place_pset_tables(s, A, 1, s->d_pset_g);
+        if (rc) return rc;
+        HIP_TRY(s, g.csi_full_score.ensure(sizeof(double) * (size_t)std::max<uint32_t>(m, 1)));
+        HIP_TRY(s, g.csi_full_kind.ensure(std::max<uint32_t>(m, 1)));
+    }
     HIP_TRY(s, upload_visit(s, s->visit));
     A.perms = s->d_visit.as<uint32_t>();
     A.n_visit = m;
@@ -11157,7 +11179,10 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
         d_log = s->h_csi_log.dev<uint8_t>();
         if (!d_log) return s->fail(PE_EHIP, "mapped result buffers unavailable");
     }
-    HIP_TRY_STATE(s, pe_launch_csi_loop(&A, &C, s->stream, d_log, log_cap));
+    if (full)
+        HIP_TRY_STATE(s, pe_launch_csi_full(&A, &C, g.csi_full_score.as<double>(), g.csi_full_kind.as<uint8_t>(), s->stream));
+    else
+        HIP_TRY_STATE(s, pe_launch_csi_loop(&A, &C, s->stream, d_log, log_cap));
     if (timed) {
         HIP_TRY(s, hipEventRecord(s->ev_csip[2], s->stream));
         s->csip_timed = true;
@@ -11165,7 +11190,9 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     uint32_t st2[3];
     std::memcpy(st2, const_cast<const uint32_t*>(s->h_place_status.as<uint32_t>()), sizeof(st2));
-    if (st2[2]) return s->fail(PE_EINTERNAL, "k_csi_loop: the LimitIterator fold passed its event bound (evaluation stopped)");
+    if (st2[2])
+        return s->fail(PE_EINTERNAL, full ? "k_csi_full: the LimitIterator fold passed a bound of its compression (evaluation stopped)"
+                                          : "k_csi_loop: the LimitIterator fold passed its event bound (evaluation stopped)");
     const uint32_t p = std::min(st2[0], count), got = std::min(count, p + 1);
     std::memcpy(out, s->h_place_out.as<pe_ranked_node>(), sizeof(pe_ranked_node) * got);
     for (uint32_t i = 0; i < p; i++) plan_of(s).emplace_back(g.name, (uint32_t)out[i].row);
@@ -11210,6 +11237,24 @@ int pe_place_csi(pe_stack* s, uint32_t tgi, uint32_t count, const uint32_t* allo
     s->pre_overflow.clear();
     return place_csi_one(s, tgi, count, alloc_idx, out, placed);
 }
+
+// computePlacements' loop for a CSI group that runs full passes: node affinities
+// or spreads at job or group level, or a limit an earlier Select of a sibling
+// group latched to MaxInt32. Every other group: the call is pe_place_csi.
+int pe_place_csi_full(pe_stack* s, uint32_t tgi, uint32_t count, const uint32_t* alloc_idx, pe_ranked_node* out,
+                      uint32_t* placed) {
+    if (!s || (!out && count)) return PE_EINVAL;
+    if (!s->have_job || tgi >= s->tgs.size() || !csi_active(*s->tgs[tgi]) ||
+        (!tg_full_scan(s, *s->tgs[tgi]) && s->limit < 0x7FFFFFFFu))
+        return pe_place_csi(s, tgi, count, alloc_idx, out, placed);
+    if (placed) *placed = 0;
+    PE_FLUSH_RESET(s);
+    CsiScope csi_scope_(s);
+    s->pre_overflow.clear();
+    return place_csi_one(s, tgi, count, alloc_idx, out, placed, false, true);
+}
+
+uint32_t pe_csi_full_block(void) { return pe_csi_full_threads(); }
 
 // The maps of pe_place_csi_metrics' records, after the loop's synchronisation:
 // record k's window [its start, + nodes_evaluated) is walked on the host against
@@ -11365,6 +11410,27 @@ int pe_csi_limit_fold(const double* scores, const uint8_t* kind, uint32_t n, uin
     *winner = L.best_id;
     *seen = L.seen;
     *consumed = used;
+    *ended_nil = L.ended_nil;
+    return PE_OK;
+}
+
+// The same stream through the fold at an unbounded limit as k_csi_full runs it:
+// compressed to specials and collapsed segments (csi_full_compress), stepped by
+// csi_full_fold. Equal to pe_csi_limit_fold at limit MaxInt32 on every stream.
+int pe_csi_full_fold(const double* scores, const uint8_t* kind, uint32_t n, int32_t* winner, uint32_t* seen,
+                     uint32_t* consumed, uint32_t* ended_nil) {
+    if ((n && (!scores || !kind)) || !winner || !seen || !consumed || !ended_nil) return PE_EINVAL;
+    pe::CsiSegment seg[pe::kCsiFullSpecials + 1];
+    pe::CsiSpecial sp[pe::kCsiFullSpecials];
+    bool closed = false;
+    const uint32_t n_spec = pe::csi_full_compress(scores, kind, n, seg, sp, &closed);
+    pe::CsiLimit L;
+    uint32_t ended_at = 0;
+    const int rc = pe::csi_full_fold(L, seg, sp, n_spec, closed, &ended_at);
+    if (rc < 0) return PE_EINTERNAL;   // a bound of csi_limit.h does not hold
+    *winner = L.best_id;
+    *seen = L.seen;
+    *consumed = rc == 0 ? sp[ended_at].pos + 1u : n;
     *ended_nil = L.ended_nil;
     return PE_OK;
 }

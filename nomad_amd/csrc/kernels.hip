@@ -5908,6 +5908,311 @@ __global__ void __launch_bounds__(256) k_sysg_scatter(SysCompactArgs A) {
         if (hit[j]) A.score[at++] = __longlong_as_double((long long)v[j]);
 }
 
+// (defined last: the kernels above keep their places in the code object)
+// pe_place_csi_full's count loop: a CSI group that runs full passes (node
+// affinities, spreads, or a limit latched to MaxInt32). k_place's full-pass
+// shape (one workgroup, lanes stride over relative positions from the cursor,
+// the spread tables rebuilt per placement, the overlay and the counts in LDS)
+// with k_csi_loop's wrapper bit, code column and stop test, and csi_limit.h's
+// fold at an unbounded limit: no serial loop over options.
+// Per placement:
+//   1 every position is evaluated without CSI and classified (filtered,
+//     exhausted, option, stop); its class and score go to ev_kind / ev_score,
+//     written and read back by the same lane. A block prefix per chunk of BLOCK
+//     positions collects, in position order, the first kCsiFullNils stops and the
+//     first kCsiFullOptions non-positive options. Chunks past the kCsiFullNils-th
+//     stop are not evaluated: no Select consumes them.
+//   2 the specials, merged by position, delimit at most kCsiFullSpecials + 1
+//     segments. Every lane reduces its positions of each segment (first strict
+//     maximum, option / non-positive / filtered / exhausted counts), every wave
+//     its lanes by shuffles; the per-wave partials of all segments meet in LDS.
+//   3 lane 0 merges the partials and steps csi_full_fold over specials and
+//     collapsed segments. A Select at this limit ends at a special or at the end
+//     of the list, so consumed / filtered / exhausted are sums over whole segments.
+//   4 record, commit, next placement.
+// Every loop is bounded without the data: positions by n, specials and segments
+// by csi_limit.h's constants, placements by count. A bound that does not hold
+// writes no record and raises eval_status[2], as k_csi_loop.
+constexpr int kCsiFullBlock = 512;
+enum : uint8_t { kFullFiltered = 0, kFullExhausted = 1, kFullOption = 2, kFullStop = 3 };
+
+template <int BLOCK>
+struct CsiFullShared {
+    uint32_t scratch[4];                         // build_spread_table
+    uint32_t wave_cnt[BLOCK / 64];               // pass 1: stops | non-positive options << 16 of each wave
+    uint32_t stop_pos[kCsiFullNils];
+    uint32_t np_pos[kCsiFullOptions];
+    double np_score[kCsiFullOptions];
+    CsiSpecial sp[kCsiFullSpecials];
+    CsiSegment seg[kCsiFullSpecials + 1];
+    uint32_t seg_filt[kCsiFullSpecials + 1], seg_exh[kCsiFullSpecials + 1];
+    uint32_t n_spec, end_pos, closed;
+    // pass 2: per segment and wave
+    double part_score[kCsiFullSpecials + 1][BLOCK / 64];
+    uint32_t part_pos[kCsiFullSpecials + 1][BLOCK / 64];
+    uint32_t part_cnt[kCsiFullSpecials + 1][BLOCK / 64][4];   // options, non-positive, filtered, exhausted
+    // the Select's outcome
+    int best_pos;
+    uint32_t consumed, n_filtered, n_exhausted, err;
+    double best_score;
+};
+
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_csi_full(BatchArgs A, CsiLoopArgs C, double* ev_score, uint8_t* ev_kind) {
+    __shared__ CsiFullShared<BLOCK> sh;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
+    constexpr int W = BLOCK / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const uint32_t n = A.n_visit;
+    const uint32_t* perm = A.perms;
+    const uint8_t* class_ok = A.tg.class_ok;
+
+    // the spread tables, the counts and the overlay out of dynamic LDS (as k_place<*, true, *>)
+    const uint32_t H = 1u << A.hash_bits;
+    unsigned char* p = dyn_smem;
+    double* spread_tab = nullptr;
+    uint32_t* counts = nullptr;
+    if (A.pset_g_tab) {   // tables beyond the LDS budget: the HBM copy
+        spread_tab = A.pset_g_tab;
+        counts = A.pset_g_cnt;
+    } else {
+        spread_tab = reinterpret_cast<double*>(p);
+        counts = reinterpret_cast<uint32_t*>(p + sizeof(double) * A.tg.pset_tab_total);
+        p += A.pset_lds;
+    }
+    Overlay ov;
+    ov.bits = A.hash_bits;
+    ov.mask = H - 1;
+    ov.keys = reinterpret_cast<uint32_t*>(p); p += 4 * H;
+    ov.k = reinterpret_cast<uint32_t*>(p); p += 4 * H;
+    for (uint32_t i = tid; i < H; i += BLOCK) ov.keys[i] = kEmpty;
+    for (int q = 0; q < A.tg.n_psets; q++)
+        for (int v = tid; v < A.tg.pset_nvals[q]; v += BLOCK) counts[A.tg.pset_cnt_off[q] + v] = A.tg.pset_counts[q][v];
+    __syncthreads();
+
+    uint32_t offset = n ? A.offset0 % n : 0u;
+    uint32_t placed = 0;
+    uint64_t walked = 0;   // positions consumed since the call began
+    uint32_t fold_err = 0;
+
+    for (uint32_t it = 0; n && it < A.count; it++) {
+        if (A.tg.n_psets > 0) build_spread_table<BLOCK>(A.tg, counts, spread_tab, sh.scratch);
+        const uint32_t set = min((uint32_t)C.set_of[it], C.n_sets - 1u);
+        const uint16_t* codes = C.codes + (size_t)set * C.n_rows;
+
+        // ---- 1: classify every position; the first stops and non-positive options in position order
+        uint32_t n_stop = 0, n_np = 0;
+        for (uint32_t base = 0; base < n && n_stop < (uint32_t)kCsiFullNils; base += BLOCK) {
+            const uint32_t j = base + (uint32_t)tid;
+            uint8_t kind = kFullFiltered;
+            double score = 0.0;
+            if (j < n) {
+                uint32_t pos = offset + j;
+                if (pos >= n) pos -= n;
+                const uint32_t row = perm[pos];
+                const uint32_t c = A.soa.rec[row].cls;
+                // FeasibilityWrapper's verdict without CSI: the node reaches the availability checker
+                const bool reach = class_ok[c] != 0 && (!A.tg.node_ok || A.tg.node_ok[row] != 0);
+                const bool unavailable = reach && row < C.n_rows && codes[row] != 0;
+                if (unavailable && !C.escaped) {
+                    const uint8_t cs = c < C.ncls ? C.cls_state[c] : (uint8_t)kCsiClsNever;
+                    if (cs == kCsiClsEligible || (cs == kCsiClsOpen && walked + (uint64_t)j > (uint64_t)C.first[c]))
+                        kind = kFullStop;
+                }
+                if (reach && !unavailable) {
+                    NodeEval ev;
+                    ev.score = 0.0;
+                    eval_node<false>(A.soa, A.tg, class_ok, A.ask, ov, A.penalty_bits, A.log10, spread_tab, row, &ev);
+                    if (ev.status == kOption) {
+                        kind = kFullOption;
+                        score = ev.score;
+                    } else if (ev.status == kExhausted) {
+                        kind = kFullExhausted;
+                    }
+                }
+                ev_kind[j] = kind;
+                ev_score[j] = score;
+            }
+            const bool is_stop = kind == kFullStop;
+            const bool is_np = kind == kFullOption && score <= 0.0;
+            const uint64_t ms = __ballot(is_stop), mn = __ballot(is_np);
+            if (lane == 0) sh.wave_cnt[wid] = (uint32_t)__popcll(ms) | (uint32_t)__popcll(mn) << 16;
+            __syncthreads();
+            uint32_t before = 0, tot = 0;
+#pragma unroll
+            for (int w = 0; w < W; w++) {
+                const uint32_t x = sh.wave_cnt[w];
+                before += w < wid ? x : 0u;
+                tot += x;
+            }
+            const uint32_t rank_s = n_stop + (before & 0xFFFFu) + lanes_below(ms, lane);
+            const uint32_t rank_n = n_np + (before >> 16) + lanes_below(mn, lane);
+            if (is_stop && rank_s < (uint32_t)kCsiFullNils) sh.stop_pos[rank_s] = j;
+            if (is_np && rank_n < (uint32_t)kCsiFullOptions) {
+                sh.np_pos[rank_n] = j;
+                sh.np_score[rank_n] = score;
+            }
+            n_stop += tot & 0xFFFFu;
+            n_np += tot >> 16;
+            __syncthreads();
+        }
+
+        // ---- the specials by position
+        if (tid == 0) {
+            const uint32_t ns = min(n_stop, (uint32_t)kCsiFullNils), nn = min(n_np, (uint32_t)kCsiFullOptions);
+            const bool closed = n_stop >= (uint32_t)kCsiFullNils;
+            const uint32_t end = closed ? sh.stop_pos[kCsiFullNils - 1] + 1u : n;
+            uint32_t a = 0, b = 0, k = 0;
+            for (int t = 0; t < kCsiFullSpecials; t++) {
+                const uint32_t pa = a < ns ? sh.stop_pos[a] : 0xFFFFFFFFu;
+                const uint32_t pb = b < nn && sh.np_pos[b] < end ? sh.np_pos[b] : 0xFFFFFFFFu;
+                if (pa == 0xFFFFFFFFu && pb == 0xFFFFFFFFu) break;
+                if (pa < pb) {
+                    sh.sp[k].pos = pa;
+                    sh.sp[k].kind = kCsiNil;
+                    sh.sp[k].score = 0.0;
+                    a++;
+                } else {
+                    sh.sp[k].pos = pb;
+                    sh.sp[k].kind = kCsiOption;
+                    sh.sp[k].score = sh.np_score[b];
+                    b++;
+                }
+                k++;
+            }
+            sh.n_spec = k;
+            sh.end_pos = end;
+            sh.closed = closed ? 1u : 0u;
+        }
+        __syncthreads();
+
+        // ---- 2: every segment's partials per wave
+        const uint32_t n_spec = sh.n_spec, end_pos = sh.end_pos;
+        const bool closed = sh.closed != 0;
+        const uint32_t n_seg = n_spec + (closed ? 0u : 1u);
+        for (uint32_t g = 0; g < n_seg && g <= (uint32_t)kCsiFullSpecials; g++) {
+            const uint32_t lo = g ? sh.sp[g - 1].pos + 1u : 0u;
+            const uint32_t hi = g < n_spec ? sh.sp[g].pos : end_pos;
+            if (lo >= hi) continue;   // (uniform)
+            double bs = -__builtin_inf();
+            uint32_t bp = 0xFFFFFFFFu;
+            uint32_t c_opt = 0, c_np = 0, c_filt = 0, c_exh = 0;
+            // this lane's positions of [lo, hi): j = tid (mod BLOCK), increasing, so `>` keeps the first maximum
+            for (uint32_t j = lo + (((uint32_t)tid + (uint32_t)BLOCK - lo % (uint32_t)BLOCK) % (uint32_t)BLOCK); j < hi;
+                 j += BLOCK) {
+                const uint8_t kind = ev_kind[j];
+                if (kind == kFullOption) {
+                    const double sc = ev_score[j];
+                    c_opt++;
+                    c_np += sc <= 0.0 ? 1u : 0u;
+                    if (sc > bs) { bs = sc; bp = j; }
+                } else if (kind == kFullExhausted) {
+                    c_exh++;
+                } else {
+                    c_filt++;
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const double os = __shfl_xor(bs, off);
+                const uint32_t op = (uint32_t)__shfl_xor((int)bp, off);
+                if (os > bs || (os == bs && op < bp)) { bs = os; bp = op; }
+                c_opt += (uint32_t)__shfl_xor((int)c_opt, off);
+                c_np += (uint32_t)__shfl_xor((int)c_np, off);
+                c_filt += (uint32_t)__shfl_xor((int)c_filt, off);
+                c_exh += (uint32_t)__shfl_xor((int)c_exh, off);
+            }
+            if (lane == 0) {
+                sh.part_score[g][wid] = bs;
+                sh.part_pos[g][wid] = bp;
+                sh.part_cnt[g][wid][0] = c_opt;
+                sh.part_cnt[g][wid][1] = c_np;
+                sh.part_cnt[g][wid][2] = c_filt;
+                sh.part_cnt[g][wid][3] = c_exh;
+            }
+        }
+        __syncthreads();
+
+        // ---- 3: the segments, and the fold over specials and collapsed segments
+        if (tid == 0) {
+            for (uint32_t g = 0; g <= (uint32_t)kCsiFullSpecials; g++) {
+                CsiSegment sg = {0u, 0u, -1, 0u, 0.0};
+                uint32_t f = 0, x = 0;
+                const uint32_t lo = g && g <= n_spec ? sh.sp[g - 1].pos + 1u : 0u;
+                const uint32_t hi = g < n_spec ? sh.sp[g].pos : end_pos;
+                if (g < n_seg && lo < hi) {
+                    double bs = -__builtin_inf();
+                    uint32_t bp = 0xFFFFFFFFu;
+                    for (int w = 0; w < W; w++) {
+                        const double os = sh.part_score[g][w];
+                        const uint32_t op = sh.part_pos[g][w];
+                        if (os > bs || (os == bs && op < bp)) { bs = os; bp = op; }
+                        sg.options += sh.part_cnt[g][w][0];
+                        sg.nonpos += sh.part_cnt[g][w][1];
+                        f += sh.part_cnt[g][w][2];
+                        x += sh.part_cnt[g][w][3];
+                    }
+                    if (sg.options) { sg.score = bs; sg.id = (int32_t)bp; }
+                }
+                sh.seg[g] = sg;
+                sh.seg_filt[g] = f;
+                sh.seg_exh[g] = x;
+            }
+            CsiLimit L;
+            uint32_t ended_at = 0;
+            const int frc = csi_full_fold(L, sh.seg, sh.sp, n_spec, closed, &ended_at);
+            uint32_t nf = 0, nx = 0;
+            // the segments up to the end, and the stops among the specials consumed (a stop counts as filtered)
+            for (uint32_t g = 0; g <= (uint32_t)kCsiFullSpecials; g++) {
+                const bool seg_in = frc == 0 ? g <= ended_at : g < n_seg;
+                const bool sp_in = g < n_spec && (frc == 0 ? g <= ended_at : true);
+                if (seg_in) { nf += sh.seg_filt[g]; nx += sh.seg_exh[g]; }
+                if (sp_in && g < (uint32_t)kCsiFullSpecials && sh.sp[g].kind == kCsiNil) nf++;
+            }
+            sh.err = frc < 0 ? 1u : 0u;
+            sh.consumed = frc == 0 ? sh.sp[min(ended_at, (uint32_t)kCsiFullSpecials - 1u)].pos + 1u : n;
+            sh.n_filtered = nf;
+            sh.n_exhausted = nx;
+            sh.best_pos = L.best_id;
+            sh.best_score = L.best_score;
+        }
+        __syncthreads();
+        if (sh.err) {   // csi_limit.h's bounds do not hold: no record, the host fails the call
+            fold_err = 1u;
+            break;
+        }
+
+        // ---- 4: the record, the commit
+        const int best_pos = sh.best_pos;
+        const double best_score = sh.best_score;
+        const uint32_t consumed = sh.consumed, n_filtered = sh.n_filtered, n_exhausted = sh.n_exhausted;
+        int win_row = -1;
+        if (best_pos >= 0 && (uint32_t)best_pos < n) {
+            uint32_t pos = offset + (uint32_t)best_pos;
+            if (pos >= n) pos -= n;
+            win_row = (int)perm[pos];
+        }
+        uint32_t no = offset + (consumed % n);
+        if (no >= n) no -= n;
+        if (tid == 0) {
+            emit_placement(A, class_ok, ov, spread_tab, 0u, it, win_row, best_score, consumed, n_filtered, n_exhausted,
+                           no);
+            if (win_row >= 0 && A.commit) commit_overlay(A.soa, A.tg, ov, counts, (uint32_t)win_row);
+        }
+        offset = no;
+        walked += consumed;
+        __syncthreads();
+        if (win_row < 0) break;   // nil option: the loop ends, its record written
+        placed++;
+    }
+    if (tid == 0) {
+        A.eval_status[0] = placed;
+        A.eval_status[1] = offset;
+        A.eval_status[2] = fold_err;
+    }
+    if (A.writeback) writeback_overlay<BLOCK, true, true>(A, ov, H, counts);
+}
+
 }  // namespace pe
 
 // ---- launch wrappers (host) ------------------------------------------------
@@ -6846,5 +7151,32 @@ hipError_t pe_launch_static_gate(const uint8_t* blocked, const uint32_t* coll_tg
 hipError_t pe_launch_md_gate(pe::MdNet* md, const uint32_t* coll_tg, uint32_t n, hipStream_t st) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(pe::k_md_gate, dim3((n + 255) / 256), dim3(256), 0, st, md, coll_tg, n);
+    return hipGetLastError();
+}
+
+// One workgroup; the overlay must hold the launch's placements. ev_score / ev_kind: n_visit entries each, the
+// per-position classes and scores a placement's passes hand on (device memory, no contents expected).
+uint32_t pe_csi_full_threads() { return pe::kCsiFullBlock; }
+
+hipError_t pe_launch_csi_full(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, double* ev_score, uint8_t* ev_kind,
+                              hipStream_t st) {
+    if (!a->perms || a->n_visit == 0 || a->n_visit >= 0x7FFFFFFFu - (uint32_t)pe::kCsiFullBlock || !a->full_out ||
+        !a->eval_status || !c->codes || !c->set_of || !c->cls_state || !c->first || c->n_sets == 0 ||
+        c->n_sets > (uint32_t)pe::kMaxCsiSets || c->n_rows != a->soa.n || a->tg.node_feas || a->packed_overlay ||
+        !ev_score || !ev_kind || a->hash_bits < 0 || a->hash_bits > 30 || ((uint64_t)1 << a->hash_bits) < 2ull * a->count)
+        return hipErrorInvalidValue;
+    if (a->ask.n_dev > 0 && (!a->tg.dev_cls || !a->tg.dev_free)) return hipErrorInvalidValue;   // a device ask reads both
+    if (a->tg.n_psets > 0 && !a->pset_lds && (!a->pset_g_tab || !a->pset_g_cnt)) return hipErrorInvalidValue;
+    const size_t lds = pe_place_lds_bytes(true, a->hash_bits, false, a->pset_lds);
+    if (lds > 96u * 1024u) return hipErrorInvalidValue;   // (max_hash_bits' budget)
+    static bool attr = false;
+    if (!attr && lds > 32u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pe::k_csi_full<pe::kCsiFullBlock>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        if (e != hipSuccess) return e;
+        attr = true;
+    }
+    hipLaunchKernelGGL((pe::k_csi_full<pe::kCsiFullBlock>), dim3(1), dim3(pe::kCsiFullBlock), lds, st, *a, *c, ev_score,
+                       ev_kind);
     return hipGetLastError();
 }

@@ -473,6 +473,22 @@ class _Stack:
         n = min(count, placed.value + 1)
         return [RankedNode.from_c(out[i], self.nodes, self._full_preempted(i, out[i])) for i in range(n)]
 
+    def PlaceCSIFull(self, tg, count: int, alloc_idx=None) -> List[RankedNode]:
+        """pe_place_csi_full: PlaceCSI for a group that runs full passes (node
+        affinities, spreads, or a limit latched to MaxInt32 by a sibling group's
+        Select). Arguments and records as PlaceCSI; on every other group the
+        call is PlaceCSI."""
+        out = (abi.pe_ranked_node * max(1, count))()
+        placed = C.c_uint32(0)
+        idx = None
+        if alloc_idx is not None:
+            if len(alloc_idx) != count:
+                raise ValueError("alloc_idx needs one index per placement")
+            idx = (C.c_uint32 * max(1, count))(*[int(i) for i in alloc_idx])
+        self._check(self._lib.pe_place_csi_full(self._h, self._tg_index(tg), count, idx, out, C.byref(placed)))
+        n = min(count, placed.value + 1)
+        return [RankedNode.from_c(out[i], self.nodes, self._full_preempted(i, out[i])) for i in range(n)]
+
     def PlaceCSIMetrics(self, tg, count: int, alloc_idx=None) -> List[RankedNode]:
         """pe_place_csi_metrics: PlaceCSI with AllocMetric kept. The records are
         PlaceCSI's; with EnableMetrics on, PlaceCSIMaps() then gives each
@@ -507,7 +523,8 @@ class _Stack:
         return int(self._lib.pe_csi_avail_launches(self._h))
 
     def csi_place_ms(self):
-        """(k_csi_first, k_csi_loop) device ms of the last PlaceCSI; PE_CSI_TIME=1 only."""
+        """(k_csi_first, k_csi_loop) device ms of the last PlaceCSI, or (k_csi_first,
+        k_csi_full) of the last PlaceCSIFull of a full-pass group; PE_CSI_TIME=1 only."""
         ms = (C.c_double * 2)()
         self._check(self._lib.pe_csi_place_ms(self._h, ms))
         return float(ms[0]), float(ms[1])

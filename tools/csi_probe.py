@@ -42,6 +42,25 @@ bytes written per call (pe_place_csi_metrics_stats on a third handle created
 with PE_CSI_TIME=1), and whether the records are equal.
 
     python tools/csi_probe.py --place-metrics [--reps 24] [--small] [--out profiles/csi_place_metrics/probe.json]
+
+--place-full: pe_place_csi_full over cluster_c2 with its nodes
+dealt to three datacenters (50 / 30 / 20 %) and a target spread over them in
+the job, counts 1, 8 and 64, alloc indices 0 .. count - 1, 24 repetitions after
+3 warm-up ones, each from pe_reset_plan and a cursor of its own. Per count: the
+call by the host clock, k_csi_first and k_csi_full by HIP events on a handle of
+its own (PE_CSI_TIME=1), the placements a call made, pe_place of the same job
+without its CSI requests on another handle (the full-pass loop without stops:
+a cost reference, not an equal workload), and how many Selects of the
+per-placement sequence (pe_csi_alloc_index, pe_select, pe_commit) pe_select
+hands back on the same inputs; the sequence of a repetition ends at its first
+hand-back, the records are compared up to there. One more leg at count 8
+(measure_whole_list): both jobs with a group constraint that makes the group
+escape its class, so that no node is a stop and every Select of either call
+consumes the whole list. With a library that has no
+pe_place_csi_full (PE_ENGINE_LIB: the parent commit's build) only the pe_place
+leg runs.
+
+    python tools/csi_probe.py --place-full [--reps 24] [--small] [--out profiles/csi_place_full/probe.json]
 """
 import argparse
 import copy
@@ -57,7 +76,7 @@ os.environ["PE_SPECULATE"] = "0"
 sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
 from nomad_amd import synth  # noqa: E402
 from nomad_amd.stack import GenericStack, SelectOptions, Unsupported  # noqa: E402
-from nomad_amd.structs import CSINodePlugin, CSIVolume, CSIVolumeRequest  # noqa: E402
+from nomad_amd.structs import CSINodePlugin, CSIVolume, CSIVolumeRequest, Constraint, Spread, SpreadTarget  # noqa: E402
 
 REQS = [CSIVolumeRequest("data"), CSIVolumeRequest("scratch", per_alloc=True), CSIVolumeRequest("conf", read_only=True)]
 
@@ -293,10 +312,165 @@ def measure_place_metrics(nodes, allocs, job, reps, counts=(1, 8, 64)):
     return out
 
 
+def measure_place_full(nodes, allocs, job, reps, counts=(1, 8, 64)):
+    rng = np.random.Generator(np.random.PCG64(17))
+    for nd in nodes:
+        u = rng.random()
+        nd.datacenter = "dc1" if u < 0.5 else ("dc2" if u < 0.8 else "dc3")
+        nd.compute_class()
+    perm = synth.shuffle(len(nodes), 5)
+    volumes, node_volumes = csi_state(nodes, max(counts) + 1, seed=6)
+    job = copy.deepcopy(job)
+    job.datacenters = ["dc1", "dc2", "dc3"]
+    job.spreads = [Spread("${node.datacenter}", 100, [SpreadTarget("dc1", 50), SpreadTarget("dc2", 30)])]
+    csi = copy.deepcopy(job)
+    csi.task_groups[0].csi_volumes = list(REQS)
+    st_plain = handle(nodes, allocs, job, perm)
+    have_full = hasattr(st_plain._lib, "pe_place_csi_full")
+    hs = [st_plain]
+    if have_full:
+        st_full = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+        st_seq = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+        os.environ["PE_CSI_TIME"] = "1"
+        st_time = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+        del os.environ["PE_CSI_TIME"]
+        hs += [st_full, st_seq, st_time]
+    limit = st_plain.GetCursor()[1]
+    n = len(nodes)
+    for st in hs:   # (the handle is a 64-bit pointer: never call without argtypes)
+        st._lib.pe_flush.restype = ctypes.c_int
+        st._lib.pe_flush.argtypes = [ctypes.c_void_p]
+
+    def stats(v):
+        a = np.asarray(v, dtype=np.float64)
+        return {"n": int(a.size), "median_us": float(np.median(a)), "p10_us": float(np.percentile(a, 10)),
+                "p90_us": float(np.percentile(a, 90))} if a.size else {"n": 0}
+    out = {"nodes": n, "requests": len(REQS), "limit_at_set_nodes": limit, "library_has_pe_place_csi_full": have_full,
+           "counts": {}}
+    for count in counts:
+        idx = list(range(count))
+        t_full, t_plain, first_ms, full_ms, evaluated = [], [], [], [], []
+        handed_back = answered = placed_full = placed_plain = same = compared = 0
+        for rep in range(reps + 3):
+            cursor = (rep * 977 + 13) % n
+            for st in hs:
+                st.ResetPlan()
+                st.SetJob(csi if st is not st_plain else job)
+                st.SetNodes(perm)
+                st.SetCursor(cursor, limit)
+                st._check(st._lib.pe_flush(st._h))
+            t0 = time.perf_counter()
+            plain = st_plain.Place(0, count)
+            dt_plain = (time.perf_counter() - t0) * 1e6
+            if rep >= 3:
+                t_plain.append(dt_plain)
+                placed_plain += sum(1 for r in plain if r.row >= 0)
+            if not have_full:
+                continue
+            t0 = time.perf_counter()
+            recs = st_full.PlaceCSIFull(0, count, alloc_idx=idx)
+            dt_full = (time.perf_counter() - t0) * 1e6
+            seq, back = [], 0
+            for i in range(count):
+                try:
+                    st_seq.CSIAllocIndex(0, idx[i])
+                    r = st_seq.SelectRaw(0)
+                except Unsupported:
+                    back = 1
+                    break
+                seq.append(r)
+                if r.row < 0:
+                    break
+                st_seq.Commit(0, r.row)
+            st_time.PlaceCSIFull(0, count, alloc_idx=idx)
+            ms = st_time.csi_place_ms()
+            if rep < 3:
+                continue
+            t_full.append(dt_full)
+            first_ms.append(ms[0])
+            full_ms.append(ms[1])
+            handed_back += back
+            answered += len(seq)
+            placed_full += sum(1 for r in recs if r.row >= 0)
+            evaluated.append(sum(r.nodes_evaluated for r in recs))
+            compared += len(seq)
+            same += sum(1 for a, b in zip(recs, seq) if (a.row, a.final_score, a.nodes_evaluated, a.new_offset) ==
+                        (b.row, b.final_score, b.nodes_evaluated, b.new_offset))
+        res = {"pe_place_without_csi_us": stats(t_plain), "pe_place_placed_per_call": placed_plain / max(1, len(t_plain))}
+        if have_full:
+            res.update({
+                "pe_place_csi_full_us": stats(t_full), "k_csi_first_us": stats(np.asarray(first_ms) * 1e3),
+                "k_csi_full_us": stats(np.asarray(full_ms) * 1e3), "placed_per_call": placed_full / max(1, len(t_full)),
+                "positions_consumed_per_call": float(np.mean(evaluated)),
+                "ratio_to_pe_place_median": float(np.median(t_full) / np.median(t_plain)),
+                "sequence_selects_answered": int(answered), "sequence_repetitions_handed_back": int(handed_back),
+                "records_compared": int(compared), "records_equal": int(same)})
+        out["counts"][str(count)] = res
+        print("place-full", count, json.dumps(res))
+    if have_full:
+        out["whole_list_count_8"] = measure_whole_list(nodes, allocs, job, csi, perm, volumes, node_volumes, reps)
+        print("place-full whole list", json.dumps(out["whole_list_count_8"]))
+    return out
+
+
+def measure_whole_list(nodes, allocs, job, csi, perm, volumes, node_volumes, reps, count=8):
+    """The same two jobs with a group constraint on node.unique.id that every
+    node passes: the group escapes its class, so no unavailable node is a stop
+    and every Select of pe_place_csi_full consumes the whole list, as every
+    Select of pe_place does: the same number of positions per placement, the
+    unavailable nodes filtered in one and options in the other."""
+    job, csi = copy.deepcopy(job), copy.deepcopy(csi)
+    for j in (job, csi):
+        j.task_groups[0].constraints = list(j.task_groups[0].constraints) + [
+            Constraint("${node.unique.id}", "no-such-node", "!=")]
+    st_plain = handle(nodes, allocs, job, perm)
+    st_full = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    os.environ["PE_CSI_TIME"] = "1"
+    st_time = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    del os.environ["PE_CSI_TIME"]
+    limit, n = st_plain.GetCursor()[1], len(nodes)
+    for st in (st_plain, st_full, st_time):
+        st._lib.pe_flush.restype = ctypes.c_int
+        st._lib.pe_flush.argtypes = [ctypes.c_void_p]
+    t_full, t_plain, full_ms, consumed, placed = [], [], [], [], 0
+    for rep in range(reps + 3):
+        for st in (st_plain, st_full, st_time):
+            st.ResetPlan()
+            st.SetJob(csi if st is not st_plain else job)
+            st.SetNodes(perm)
+            st.SetCursor((rep * 977 + 13) % n, limit)
+            st._check(st._lib.pe_flush(st._h))
+        t0 = time.perf_counter()
+        st_plain.Place(0, count)
+        dt_plain = (time.perf_counter() - t0) * 1e6
+        t0 = time.perf_counter()
+        recs = st_full.PlaceCSIFull(0, count, alloc_idx=list(range(count)))
+        dt_full = (time.perf_counter() - t0) * 1e6
+        st_time.PlaceCSIFull(0, count, alloc_idx=list(range(count)))
+        ms = st_time.csi_place_ms()
+        if rep < 3:
+            continue
+        t_plain.append(dt_plain)
+        t_full.append(dt_full)
+        full_ms.append(ms[1] * 1e3)
+        consumed.append(sum(r.nodes_evaluated for r in recs))
+        placed += sum(1 for r in recs if r.row >= 0)
+
+    def stats(v):
+        a = np.asarray(v, dtype=np.float64)
+        return {"n": int(a.size), "median_us": float(np.median(a)), "p10_us": float(np.percentile(a, 10)),
+                "p90_us": float(np.percentile(a, 90))}
+    return {"count": count, "pe_place_csi_full_us": stats(t_full), "pe_place_without_csi_us": stats(t_plain),
+            "k_csi_full_us": stats(full_ms), "placed_per_call": placed / max(1, len(t_full)),
+            "positions_consumed_per_call": float(np.mean(consumed)),
+            "ratio_to_pe_place_median": float(np.median(t_full) / np.median(t_plain))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--place", action="store_true", help="the pe_place_csi leg (DESIGN.md §40)")
     ap.add_argument("--place-metrics", action="store_true", help="the pe_place_csi_metrics leg (DESIGN.md §41)")
+    ap.add_argument("--place-full", action="store_true", help="the pe_place_csi_full leg (DESIGN.md §43)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--selects", type=int, default=200)
     ap.add_argument("--small", action="store_true", help="1/10 of the node counts (rehearsal)")
@@ -304,6 +478,16 @@ def main():
     a = ap.parse_args()
     scale = 10 if a.small else 1
     res = {"tool": "tools/csi_probe.py", "speculate": 0}
+    if a.place_full:
+        out = a.out if a.out != "profiles/csi/probe.json" else "profiles/csi_place_full/probe.json"
+        nodes, allocs = synth.cluster_c2(10000 // scale, seed=42)
+        res["tool"] += " --place-full"
+        res["cluster_c2"] = measure_place_full(nodes, allocs, synth.job_c2(64), max(a.reps, 24))
+        os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
+        return
     if a.place_metrics:
         out = a.out if a.out != "profiles/csi/probe.json" else "profiles/csi_place_metrics/probe.json"
         nodes, allocs = synth.cluster_c2(10000 // scale, seed=42)
