@@ -1213,6 +1213,38 @@ int pe_csi_limit_fold(const double* scores, const uint8_t* kind, uint32_t n, uin
  * hold. Needs no device. */
 int pe_csi_full_fold(const double* scores, const uint8_t* kind, uint32_t n, int32_t* winner, uint32_t* seen,
                      uint32_t* consumed, uint32_t* ended_nil);
+/* The fp64 scoring math the kernels run (Go 1.16 math.Pow / Exp / Log restated,
+ * ScoreFit, basicResourceDistance, preemptionScore, the score's ordered-integer
+ * key), exposed for tests: item i of `op` evaluated by the function the kernels
+ * call, on the host (device == 0; needs no device) or by a one-lane-per-item
+ * kernel (device != 0; PE_EHIP without a device). out[i] holds the result's
+ * IEEE-754 bits (PE_PROBE_ORDER_KEY: the key). Inputs:
+ *   POW10_UNIT, POW10 (finite y, |y| < 2^63), EXP, LOG (x > 0), POW2, ORDER_KEY:
+ *     xd[n];
+ *   FIT_SCORE: xi[5 n] = (cap_cpu, cap_mem, util_cpu, util_mem, spread), the
+ *     score over binPackingMaxFitScore as the ranking uses it;
+ *   BASIC_DISTANCE: xi[6 n] = (ask cpu, mem, disk, alloc cpu, mem, disk);
+ *   PREEMPTION_SCORE: xi = n + 1 offsets (xi[0] == 0, non-decreasing, at most
+ *     256 apart), then the priorities of the preempted allocs they slice. */
+#define PE_PROBE_POW10_UNIT 0u
+#define PE_PROBE_POW10 1u
+#define PE_PROBE_EXP 2u
+#define PE_PROBE_LOG 3u
+#define PE_PROBE_FIT_SCORE 4u
+#define PE_PROBE_POW2 5u
+#define PE_PROBE_BASIC_DISTANCE 6u
+#define PE_PROBE_ORDER_KEY 7u
+#define PE_PROBE_PREEMPTION_SCORE 8u
+int pe_probe_math(uint32_t op, const double* xd, const int64_t* xi, uint32_t n, uint64_t* out, int device);
+/* Go 1.16 sort.Slice as the Preemptor's kernels run it (less = key[x] < key[y]
+ * over an index list), exposed for tests: array a is keys[off[a] .. off[a + 1])
+ * (off[0] == 0), its identity permutation is sorted and written to perm_out at
+ * the same offsets. idx_width picks the index type of the two the kernels
+ * instantiate: 1 (uint8_t, arrays of at most 255) or 2 (uint16_t, at most
+ * 65535). device == 0 sorts on the host and needs no device; otherwise one lane
+ * per array (PE_EHIP without a device). */
+int pe_probe_go_sort(const double* keys, const uint32_t* off, uint32_t n_arrays, uint32_t idx_width,
+                     uint32_t* perm_out, int device);
 /* Host-side constraint semantics used for pre-resolution (checkConstraint,
  * feasible.go:785-820), exposed for known-answer tests; needs no device.
  * l_state / r_state: 0 nil (unknown ${...} target), 1 found, 2 missing ("", false). */

@@ -13,6 +13,7 @@ u32p = C.POINTER(C.c_uint32)
 u16p = C.POINTER(C.c_uint16)
 i32p = C.POINTER(C.c_int32)
 i64p = C.POINTER(C.c_int64)
+u64p = C.POINTER(C.c_uint64)
 f64p = C.POINTER(C.c_double)
 
 PE_NONE = 0xFFFFFFFF
@@ -281,6 +282,19 @@ def bind_csi_full_fold(lib):
     return lib
 
 
+(PE_PROBE_POW10_UNIT, PE_PROBE_POW10, PE_PROBE_EXP, PE_PROBE_LOG, PE_PROBE_FIT_SCORE, PE_PROBE_POW2,
+ PE_PROBE_BASIC_DISTANCE, PE_PROBE_ORDER_KEY, PE_PROBE_PREEMPTION_SCORE) = range(9)
+
+
+def bind_probes(lib):
+    """pe_probe_math / pe_probe_go_sort: test hooks; device = 0 needs no device."""
+    lib.pe_probe_math.restype = C.c_int
+    lib.pe_probe_math.argtypes = [C.c_uint32, f64p, i64p, C.c_uint32, u64p, C.c_int]
+    lib.pe_probe_go_sort.restype = C.c_int
+    lib.pe_probe_go_sort.argtypes = [f64p, u32p, C.c_uint32, C.c_uint32, u32p, C.c_int]
+    return lib
+
+
 # Entry points declared in include/nomad_pe.h: (name, restype, argtypes)
 def _sigs(prefix, handle):
     H = C.c_void_p
@@ -327,6 +341,7 @@ ENGINE_SYMBOLS = [
     "pe_place_csi", "pe_csi_avail_launches", "pe_csi_place_ms", "pe_csi_limit_fold",
     "pe_place_csi_metrics", "pe_place_csi_maps", "pe_place_csi_metrics_stats", "pe_csi_reason_text",
     "pe_place_csi_full", "pe_csi_full_fold", "pe_csi_full_block",
+    "pe_probe_math", "pe_probe_go_sort",
 ]
 
 

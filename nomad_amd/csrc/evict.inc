@@ -30,14 +30,14 @@ constexpr int kResolveBlock = 1024;
 template <int W>
 struct AMask {
     uint32_t w[W];
-    __device__ __forceinline__ static AMask zero() {
+    __host__ __device__ __forceinline__ static AMask zero() {
         AMask m;
 #pragma unroll
         for (int i = 0; i < W; i++) m.w[i] = 0u;
         return m;
     }
-    __device__ __forceinline__ bool test(uint32_t i) const { return (w[i >> 5] >> (i & 31u)) & 1u; }
-    __device__ __forceinline__ void set(uint32_t i) { w[i >> 5] |= 1u << (i & 31u); }
+    __host__ __device__ __forceinline__ bool test(uint32_t i) const { return (w[i >> 5] >> (i & 31u)) & 1u; }
+    __host__ __device__ __forceinline__ void set(uint32_t i) { w[i >> 5] |= 1u << (i & 31u); }
     __device__ __forceinline__ bool any() const {
         uint32_t x = 0;
 #pragma unroll
@@ -72,7 +72,7 @@ struct EvW {
 };
 
 // math.Pow(x, 2) (Go 1.16 pow.go: yi = 2, yf = 0 -> Frexp mantissa squaring)
-__device__ __forceinline__ double pow2_go(double x) {
+__host__ __device__ __forceinline__ double pow2_go(double x) {
     if (x == 1.0) return 1.0;
     if (x != x) return x;
     if (x == 0.0) return 0.0;
@@ -92,7 +92,7 @@ __device__ __forceinline__ double pow2_go(double x) {
 }
 
 // basicResourceDistance (preemption.go:603-622)
-__device__ __forceinline__ double basic_distance(int64_t ac, int64_t am, int64_t ad, const PreemptAlloc& u) {
+__host__ __device__ __forceinline__ double basic_distance(int64_t ac, int64_t am, int64_t ad, const PreemptAlloc& u) {
     double mc = 0.0, cc = 0.0, dc = 0.0;
     if (am > 0) mc = ((double)am - (double)u.mem) / (double)am;
     if (ac > 0) cc = ((double)ac - (double)u.cpu) / (double)ac;
@@ -113,11 +113,11 @@ __device__ __forceinline__ double basic_distance(int64_t ac, int64_t am, int64_t
 template <class Idx>
 struct KeyLess {
     const double* key;
-    __device__ __forceinline__ bool operator()(Idx x, Idx y) const { return key[x] < key[y]; }
+    __host__ __device__ __forceinline__ bool operator()(Idx x, Idx y) const { return key[x] < key[y]; }
 };
 
 template <class Idx>
-__device__ __noinline__ void go_sort_keyed(Idx* v, int n, const double* key) {
+__host__ __device__ __noinline__ void go_sort_keyed(Idx* v, int n, const double* key) {
     GoSortDev<Idx, KeyLess<Idx>> g{v, KeyLess<Idx>{key}};
     g.sort(n);
 }
@@ -504,7 +504,7 @@ __device__ __noinline__ AMask<W> preempt_for_network(EvictCtx<W>& c, int32_t nee
 
 // netPriority / preemptionScore (rank.go:808-844) over the preempted allocs
 template <int W>
-__device__ __forceinline__ double preemption_score(const EvictCtx<W>& c, const AMask<W>& mask) {
+__host__ __device__ __forceinline__ double preemption_score(const EvictCtx<W>& c, const AMask<W>& mask) {
     int32_t sum = 0;
     double mx = 0.0;
     for (uint32_t i = 0; i < c.m; i++)

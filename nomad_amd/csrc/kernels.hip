@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <type_traits>
 #include <cstring>
+#include <vector>
 #include "engine_types.h"
 #include "csi_limit.h"
 #include "csi_reason.h"
@@ -1836,7 +1837,7 @@ struct ChainShared {
     uint32_t err;                                          // a bounds guard tripped (kChainError)
 };
 
-__device__ __forceinline__ unsigned long long order_key(double x) {
+__host__ __device__ __forceinline__ unsigned long long order_key(double x) {
     const unsigned long long b = (unsigned long long)gm::f2u(x);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
@@ -6214,6 +6215,8 @@ __global__ void __launch_bounds__(BLOCK) k_csi_full(BatchArgs A, CsiLoopArgs C, 
 }
 
 }  // namespace pe
+
+#include "probe.inc"
 
 // ---- launch wrappers (host) ------------------------------------------------
 hipError_t pe_launch_static_gate(const uint8_t* blocked, const uint32_t* coll_tg, uint32_t* gate, uint32_t n,

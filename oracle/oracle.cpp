@@ -42,6 +42,7 @@
 #include <new>
 #include <cfloat>
 #include <algorithm>
+#include <atomic>
 
 namespace {
 
@@ -1010,6 +1011,9 @@ static void tg_net_contrib(const OTaskGroup& tg, int32_t* mbits, int32_t* dyn) {
 // Go 1.16 sort.Slice (sort/zsortfunc.go: quickSort_func with doPivot_func,
 // medianOfThree_func, heapSort_func, insertionSort_func). Not stable: the
 // order of equal elements is part of the reference's behaviour.
+// heapSort_func runs only past the depth limit: the counters let a test prove
+// that its input got there (oracle_sort_heap_stats).
+static std::atomic<uint64_t> g_heap_calls{0}, g_heap_elems{0}, g_heap_ties{0};
 template <class T, class Less>
 struct GoSort {
     std::vector<T>& d;
@@ -1033,8 +1037,12 @@ struct GoSort {
     }
     void heap(int a, int b) {
         int first = a, lo = 0, hi = b - a;
+        g_heap_calls.fetch_add(1, std::memory_order_relaxed);
+        g_heap_elems.fetch_add((uint64_t)hi, std::memory_order_relaxed);
         for (int i = (hi - 1) / 2; i >= 0; i--) sift(i, hi, first);
         for (int i = hi - 1; i >= 0; i--) { S(first, first + i); sift(lo, i, first); }
+        for (int i = a; i + 1 < b; i++)   // equal neighbours: their order was heapSort's to choose
+            if (!L(i, i + 1) && !L(i + 1, i)) g_heap_ties.fetch_add(1, std::memory_order_relaxed);
     }
     void median3(int m1, int m0, int m2) {
         if (L(m1, m0)) S(m1, m0);
@@ -2543,6 +2551,62 @@ double oracle_go_log(double x) { return gomath::log(x); }
 double oracle_score_fit(int algo, int64_t cpu, int64_t mem, int64_t rcpu, int64_t rmem, int64_t ucpu, int64_t umem) {
     ONode n; n.cpu = cpu; n.mem = mem; n.rcpu = rcpu; n.rmem = rmem;
     return BinPackIterator::score_fit(algo == PE_ALGO_SPREAD, n, ucpu, umem);
+}
+
+double oracle_basic_distance(int64_t ask_cpu, int64_t ask_mem, int64_t ask_disk, int64_t cpu, int64_t mem,
+                             int64_t disk) {
+    return basic_distance(CRes{ask_cpu, ask_mem, ask_disk}, CRes{cpu, mem, disk});
+}
+
+double oracle_preemption_score(const int32_t* priorities, uint32_t n) {
+    std::vector<OAlloc> allocs((size_t)n);
+    std::vector<const OAlloc*> ptrs;
+    for (uint32_t i = 0; i < n; i++) { allocs[i].priority = priorities[i]; ptrs.push_back(&allocs[i]); }
+    return preemption_score(ptrs);
+}
+
+void oracle_go_sort(const double* keys, uint32_t n, uint32_t* perm_out) {
+    std::vector<uint32_t> v((size_t)n);
+    for (uint32_t i = 0; i < n; i++) v[i] = i;
+    go_sort_slice(v, [&](uint32_t x, uint32_t y) { return keys[x] < keys[y]; });
+    for (uint32_t i = 0; i < n; i++) perm_out[i] = v[i];
+}
+
+void oracle_sort_heap_stats(uint64_t* calls, uint64_t* elems, uint64_t* ties) {
+    if (calls) *calls = g_heap_calls.load(std::memory_order_relaxed);
+    if (elems) *elems = g_heap_elems.load(std::memory_order_relaxed);
+    if (ties) *ties = g_heap_ties.load(std::memory_order_relaxed);
+}
+
+void oracle_sort_heap_reset(void) {
+    g_heap_calls.store(0, std::memory_order_relaxed);
+    g_heap_elems.store(0, std::memory_order_relaxed);
+    g_heap_ties.store(0, std::memory_order_relaxed);
+}
+
+// M. D. McIlroy, "A Killer Adversary for Quicksort" (1999), against GoSort:
+// every item starts as "gas" (larger than any fixed value); a comparison of
+// two gas items freezes one of them to the next rank, preferably the one last
+// seen against a fixed item (the pivot candidate), so each pivot ends among
+// the smallest of its range. The frozen values are the input that replays the
+// same comparisons.
+void oracle_sort_killer(uint32_t n, double* keys_out) {
+    const int gas = (int)n;
+    std::vector<int> val((size_t)n, gas);
+    int nsolid = 0;
+    uint32_t candidate = 0;
+    std::vector<uint32_t> v((size_t)n);
+    for (uint32_t i = 0; i < n; i++) v[i] = i;
+    go_sort_slice(v, [&](uint32_t x, uint32_t y) {
+        if (val[x] == gas && val[y] == gas) {
+            if (x == candidate) val[x] = nsolid++;
+            else val[y] = nsolid++;
+        }
+        if (val[x] == gas) candidate = x;
+        else if (val[y] == gas) candidate = y;
+        return val[x] < val[y];
+    });
+    for (uint32_t i = 0; i < n; i++) keys_out[i] = (double)val[i];
 }
 
 int oracle_check_constraint(const char* op, const char* l, int ls, const char* r, int rs) {

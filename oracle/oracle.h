@@ -47,6 +47,22 @@ double oracle_go_log(double x);
 /* funcs.go:237-279: algo 0 binpack / 1 spread; returns the raw fit score in [0,18] */
 double oracle_score_fit(int algo, int64_t cpu, int64_t mem, int64_t reserved_cpu,
                         int64_t reserved_mem, int64_t used_cpu, int64_t used_mem);
+/* basicResourceDistance (preemption.go:603-622) and preemptionScore over the
+ * priorities of a preempted set (rank.go:808-844) */
+double oracle_basic_distance(int64_t ask_cpu, int64_t ask_mem, int64_t ask_disk, int64_t cpu, int64_t mem,
+                             int64_t disk);
+double oracle_preemption_score(const int32_t* priorities, uint32_t n);
+/* Go 1.16 sort.Slice (GoSort) of the identity permutation with
+ * less = keys[x] < keys[y]. */
+void oracle_go_sort(const double* keys, uint32_t n, uint32_t* perm_out);
+/* heapSort_func calls of every GoSort in this process since the last reset, the
+ * elements they sorted, and the pairs of equal neighbours in the ranges they
+ * left (NaN keys count as equal to everything). */
+void oracle_sort_heap_stats(uint64_t* calls, uint64_t* elems, uint64_t* ties);
+void oracle_sort_heap_reset(void);
+/* McIlroy's adversary run against GoSort: n keys that drive it past its depth
+ * limit where such an input exists. */
+void oracle_sort_killer(uint32_t n, double* keys_out);
 /* feasible.go:785: l_state/r_state: 0 = nil (unknown target), 1 = found, 2 = ("", false) */
 int oracle_check_constraint(const char* op, const char* l, int l_state, const char* r, int r_state);
 /* select.go: LimitIterator(limit, threshold, maxSkip) + MaxScoreIterator over a

@@ -52,6 +52,18 @@ def load():
         lib.oracle_limit_iter.restype = C.c_int
         lib.oracle_limit_iter.argtypes = [abi.f64p, C.c_int, C.c_int, C.c_double, C.c_int,
                                           abi.i32p, abi.i32p, abi.i32p]
+        lib.oracle_basic_distance.restype = C.c_double
+        lib.oracle_basic_distance.argtypes = [C.c_int64] * 6
+        lib.oracle_preemption_score.restype = C.c_double
+        lib.oracle_preemption_score.argtypes = [abi.i32p, C.c_uint32]
+        lib.oracle_go_sort.restype = None
+        lib.oracle_go_sort.argtypes = [abi.f64p, C.c_uint32, abi.u32p]
+        lib.oracle_sort_heap_stats.restype = None
+        lib.oracle_sort_heap_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
+        lib.oracle_sort_heap_reset.restype = None
+        lib.oracle_sort_heap_reset.argtypes = []
+        lib.oracle_sort_killer.restype = None
+        lib.oracle_sort_killer.argtypes = [C.c_uint32, abi.f64p]
         _lib = lib
     return _lib
 
@@ -76,6 +88,50 @@ def go_pow(x, y):
 
 def score_fit(algo, cpu, mem, rcpu, rmem, ucpu, umem):
     return load().oracle_score_fit(algo, cpu, mem, rcpu, rmem, ucpu, umem)
+
+
+def go_exp(x):
+    return load().oracle_go_exp(x)
+
+
+def go_log(x):
+    return load().oracle_go_log(x)
+
+
+def basic_distance(ask_cpu, ask_mem, ask_disk, cpu, mem, disk):
+    return load().oracle_basic_distance(ask_cpu, ask_mem, ask_disk, cpu, mem, disk)
+
+
+def preemption_score(priorities):
+    p = np.ascontiguousarray(np.asarray(priorities, dtype=np.int32))
+    return load().oracle_preemption_score(p.ctypes.data_as(abi.i32p), len(p))
+
+
+def go_sort(keys):
+    """Go 1.16 sort.Slice of range(len(keys)) by keys[x] < keys[y] (GoSort)."""
+    k = np.ascontiguousarray(np.asarray(keys, dtype=np.float64))
+    perm = np.zeros(max(1, len(k)), dtype=np.uint32)
+    load().oracle_go_sort(k.ctypes.data_as(abi.f64p), len(k), perm.ctypes.data_as(abi.u32p))
+    return perm[:len(k)]
+
+
+def sort_heap_stats():
+    """(heapSort_func calls, elements they sorted, equal neighbours they left) of
+    this process's GoSorts since the last reset."""
+    calls, elems, ties = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    load().oracle_sort_heap_stats(C.byref(calls), C.byref(elems), C.byref(ties))
+    return calls.value, elems.value, ties.value
+
+
+def sort_heap_reset():
+    load().oracle_sort_heap_reset()
+
+
+def sort_killer(n):
+    """McIlroy's adversary against GoSort: n keys (ranks, as float64)."""
+    k = np.zeros(max(1, n), dtype=np.float64)
+    load().oracle_sort_killer(n, k.ctypes.data_as(abi.f64p))
+    return k[:n]
 
 
 def check_constraint(op, l, r):

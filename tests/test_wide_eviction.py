@@ -1,7 +1,9 @@
 """Eviction past the narrow width (evict.inc): nodes holding
-more than 32 allocs, priority groups longer than 12 (Go 1.16's sort.Slice in
-full: quickSort_func, the ninther past 40 elements, heapSort past the depth
-limit), more than PE_MAX_PREEMPT preempted allocs (pe_preempted_of) and
+more than 32 allocs, priority groups longer than 12 (Go 1.16's sort.Slice
+past its insertion sort: quickSort_func and the ninther past 40 elements;
+these seeded sizes never exhaust the depth limit, heapSort_func is reached by
+tests/test_go_sort.py and tests/test_heapsort_preemption.py), more than
+PE_MAX_PREEMPT preempted allocs (pe_preempted_of) and
 ProposedAllocs lists longer than 64 (a launch flags the node and the engine
 reruns it wider). PreemptForTaskGroup walks every alloc of the node
 (scheduler/preemption.go:146-267) and sorts groups of any length
