@@ -1182,6 +1182,37 @@ int pe_place_csi_maps(const pe_stack* s, const pe_metric_count** counts, const u
  * consumed positions). PE_ESTATE without PE_CSI_TIME=1 or when
  * pe_place_csi_maps would answer so. */
 int pe_place_csi_metrics_stats(const pe_stack* s, double* us4, uint64_t* log_bytes);
+/* pe_place_csi_full with AllocMetric kept: arguments, records and contract are
+ * pe_place_csi_full's, the maps come back through pe_place_csi_maps (same
+ * store, layout and generation rule as after pe_place_csi_metrics) and the
+ * split through pe_place_csi_metrics_stats. A caller that keeps AllocMetric
+ * calls this one entry for every CSI group:
+ *  - pe_set_metrics off: the call is pe_place_csi_full, no further launch, and
+ *    pe_place_csi_maps answers PE_ESTATE;
+ *  - on, a group that runs no full passes under an unlatched limit: the call is
+ *    pe_place_csi_metrics (a group without CSI requests is refused there);
+ *  - on, a group with node affinities or spreads, or a latched limit: the
+ *    records, cursor, limit, plan, memo, alloc index, property-set counts and
+ *    every later observable state are pe_place_csi_full's with metrics off, bit
+ *    for bit: the same kernel places (k_csi_full's metrics form), and beside it
+ *    stores one trace log byte per classified position at (positions consumed
+ *    so far) + (relative position), into mapped page-locked memory. A Select
+ *    here may consume the whole list, so the log of one call holds up to
+ *    count * (visit list length) bytes. The maps cost one host walk over the
+ *    consumed windows (any length, wrapping) and one batched trace with every
+ *    record's own spread tables: two stream synchronisations per call, as
+ *    pe_place_csi_metrics. pe_last_metrics* answers PE_ESTATE afterwards.
+ * pe_set_metrics must be on from the job's first Select (see above).
+ * PE_EUNSUPPORTED, all before anything changes (cursor, limit, memo, its
+ * metrics shadow, plan and alloc index untouched): pe_place_csi_full's list
+ * without its pe_set_metrics row (distinct_property, spread values cleared by
+ * plan stops, several devices, a system or preempting stack, non-uniform
+ * classes, group networks on multi-device nodes, more than PE_MAX_CSI_SETS
+ * record sets, a count beyond the overlay) and pe_place_csi_metrics' metrics-on
+ * rows (static port asks, reserved cores, two task groups of one name,
+ * count * (visit list length) above 2^24). */
+int pe_place_csi_full_metrics(pe_stack* s, uint32_t tg_index, uint32_t count, const uint32_t* alloc_idx,
+                              pe_ranked_node* out, uint32_t* placed);
 /* The reason text CSIVolumeChecker.Feasible records (feasible.go:19-26) for
  * `reason` (PE_CSI_*): stateless, needs no device. `volume` is the request's
  * source after the per_alloc suffix (reasons 1, 5, 6, 7), `plugin` the volume's

@@ -254,6 +254,10 @@ def bind_csi(lib):
     lib.pe_place_csi_full.restype = C.c_int
     lib.pe_place_csi_full.argtypes = [H, C.c_uint32, C.c_uint32, u32p, C.POINTER(pe_ranked_node), u32p]
     bind_csi_full_fold(lib)
+    if not hasattr(lib, "pe_place_csi_full_metrics"):   # (an A/B library from before its metrics form)
+        return lib
+    lib.pe_place_csi_full_metrics.restype = C.c_int
+    lib.pe_place_csi_full_metrics.argtypes = [H, C.c_uint32, C.c_uint32, u32p, C.POINTER(pe_ranked_node), u32p]
     return lib
 
 
@@ -340,7 +344,7 @@ ENGINE_SYMBOLS = [
     "pe_inplace_update_spread", "pe_inplace_spread_ms", "pe_inplace_update_csi",
     "pe_place_csi", "pe_csi_avail_launches", "pe_csi_place_ms", "pe_csi_limit_fold",
     "pe_place_csi_metrics", "pe_place_csi_maps", "pe_place_csi_metrics_stats", "pe_csi_reason_text",
-    "pe_place_csi_full", "pe_csi_full_fold", "pe_csi_full_block",
+    "pe_place_csi_full", "pe_csi_full_fold", "pe_csi_full_block", "pe_place_csi_full_metrics",
     "pe_probe_math", "pe_probe_go_sort",
 ]
 

@@ -11006,11 +11006,14 @@ int pe_place(pe_stack* s, uint32_t tgi, uint32_t count, pe_ranked_node* out, uin
 // F[c], and k_csi_loop, which answers every Select including those pe_select
 // hands back (a stop while LimitIterator holds skipped options).
 static int csi_place_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec, const pe_ranked_node* recs,
-                          const uint32_t* alloc_idx, const uint8_t* set_of, const CsiRecSet* sets, double t_loop0);
+                          const uint32_t* alloc_idx, const uint8_t* set_of, const CsiRecSet* sets, double t_loop0,
+                          const char* kernel);
 
-// `metrics` (pe_place_csi_metrics with AllocMetric on): k_csi_loop<true> logs the
-// checker's verdict per consumed position, and the records' maps follow from
-// the host walk and one batched trace against the checkpoint (csi_place_maps).
+// `metrics` (pe_place_csi_metrics, pe_place_csi_full_metrics with AllocMetric on):
+// the loop's kernel logs the checker's verdict per consumed position, and the
+// records' maps follow from the host walk and one batched trace against the
+// checkpoint (csi_place_maps). The kernel places as without metrics: the log
+// is its only further store.
 // `full` (pe_place_csi_full): the group runs full passes (affinities, spreads or
 // a latched limit); k_csi_full answers the Selects, the limit is latched as
 // Select latches it, and the spread counts are written back with the overlay.
@@ -11022,22 +11025,23 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
     if (metrics) {
         // what the batched trace of a speculative run does not rebuild (spec_eligible's rows)
         const TgPlan& gm = *s->tgs[tgi];
+        const std::string fn = full ? "pe_place_csi_full_metrics" : "pe_place_csi_metrics";
         if (has_static(gm))
-            return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: static port asks (the reason texts read port mirrors "
+            return s->fail(PE_EUNSUPPORTED, fn + ": static port asks (the reason texts read port mirrors "
                                             "that hold the call's end state)");
         if (tg_md(s, gm))
-            return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: group networks on multi-device nodes (the port "
+            return s->fail(PE_EUNSUPPORTED, fn + ": group networks on multi-device nodes (the port "
                                             "texts come from per-Select host records)");
         if (gm.ask.cores > 0)
-            return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: reserved cores (the trace reads the cores in use "
+            return s->fail(PE_EUNSUPPORTED, fn + ": reserved cores (the trace reads the cores in use "
                                             "after the call's placements)");
         for (size_t k = 0; k < s->tgs.size(); k++)
             if (k != tgi && s->tgs[k]->name == gm.name)
-                return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: two task groups of one name (the checkpoint "
+                return s->fail(PE_EUNSUPPORTED, fn + ": two task groups of one name (the checkpoint "
                                                 "holds one group's collision counts)");
         // one log byte per position the call can consume, compared in 64 bits
         if ((uint64_t)count * (uint64_t)s->visit.size() > pe::kCsiLogCap)
-            return s->fail(PE_EUNSUPPORTED, "pe_place_csi_metrics: count times the visit list's length exceeds the "
+            return s->fail(PE_EUNSUPPORTED, fn + ": count times the visit list's length exceeds the "
                                             "trace log of one call (2^24 positions; split the loop)");
     }
     if (s->cfg.stack_kind != PE_STACK_GENERIC)
@@ -11180,7 +11184,8 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
         if (!d_log) return s->fail(PE_EHIP, "mapped result buffers unavailable");
     }
     if (full)
-        HIP_TRY_STATE(s, pe_launch_csi_full(&A, &C, g.csi_full_score.as<double>(), g.csi_full_kind.as<uint8_t>(), s->stream));
+        HIP_TRY_STATE(s, pe_launch_csi_full(&A, &C, g.csi_full_score.as<double>(), g.csi_full_kind.as<uint8_t>(), s->stream,
+                                            d_log, log_cap));
     else
         HIP_TRY_STATE(s, pe_launch_csi_loop(&A, &C, s->stream, d_log, log_cap));
     if (timed) {
@@ -11214,7 +11219,8 @@ static int place_csi_one(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
     }
     if (placed) *placed = p;
     if (metrics) {
-        rc = csi_place_maps(s, g, start % m, got, out, alloc_idx, set_of.data(), sets.data(), t_loop0);
+        rc = csi_place_maps(s, g, start % m, got, out, alloc_idx, set_of.data(), sets.data(), t_loop0,
+                            full ? "k_csi_full" : "k_csi_loop");
         if (rc) return rc;
     }
     if (g.ask.cores > 0)
@@ -11265,7 +11271,9 @@ uint32_t pe_csi_full_block(void) { return pe_csi_full_threads(); }
 // node_feas null and node_ok the column without CSI (the folded bytes belong to
 // one alloc index).
 static int csi_place_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec, const pe_ranked_node* recs,
-                          const uint32_t* alloc_idx, const uint8_t* set_of, const CsiRecSet* sets, double t_loop0) {
+                          const uint32_t* alloc_idx, const uint8_t* set_of, const CsiRecSet* sets, double t_loop0,
+                          const char* kernel) {
+    const std::string kn = kernel;   // the kernel that ran, for the texts
     const bool timed = s->tun.csi_time;   // PE_CSI_TIME=1: the call's split (pe_place_csi_metrics_stats)
     const double t0 = timed ? now_us() : 0.0;
     pe_stack::CsiMaps& M = s->csi_m;
@@ -11285,19 +11293,19 @@ static int csi_place_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec
     for (uint32_t k = 0; k < n_rec; k++) {
         const uint32_t ev = recs[k].nodes_evaluated;
         if (walked + ev > (uint64_t)s->h_csi_log.bytes)
-            return s->fail(PE_EINTERNAL, "k_csi_loop: the records consumed more positions than the trace log holds");
+            return s->fail(PE_EINTERNAL, kn + ": the records consumed more positions than the trace log holds");
         W.log = log + walked;
         W.hits.clear();
         const size_t x0 = R.xrows.size();
         metrics_walk(s, g, s->visit, off, ev, acc[k], R.xrows, nullptr, nullptr, nullptr, &W);
-        if (W.bad) return s->fail(PE_EINTERNAL, "k_csi_loop: the trace log differs from the host walk");
+        if (W.bad) return s->fail(PE_EINTERNAL, kn + ": the trace log differs from the host walk");
         const uint32_t idx = alloc_idx ? alloc_idx[k] : g.csi_idx;
         for (const auto& h : W.hits) {
             const uint32_t q = pe::csi_log_request(h.second), reason = pe::csi_log_reason(h.second);
             uint32_t key;
             if (!csi_reason_key(s, g, q, reason, idx, q < g.csi_reqs.size() ? sets[set_of[k]].req[q].plugin : PE_NONE,
                                 h.first, &key))
-                return s->fail(PE_EINTERNAL, "k_csi_loop: a trace log byte names no request of the group or no reason");
+                return s->fail(PE_EINTERNAL, kn + ": a trace log byte names no request of the group or no reason");
             acc[k].filter(s, h.first, key);
         }
         R.rsrc[k] = (uint32_t)x0;
@@ -11347,6 +11355,26 @@ int pe_place_csi_metrics(pe_stack* s, uint32_t tgi, uint32_t count, const uint32
     CsiScope csi_scope_(s);
     s->pre_overflow.clear();
     return place_csi_one(s, tgi, count, alloc_idx, out, placed, true);
+}
+
+// pe_place_csi_full with AllocMetric kept: k_csi_full<*, true> places as
+// k_csi_full<*, false> does and logs the checker's verdict per classified
+// position; the maps are csi_place_maps' over windows of any length, in the
+// store pe_place_csi_maps reads. AllocMetric off: the call is pe_place_csi_full.
+// On, a group that runs no full passes under an unlatched limit (and whatever
+// pe_place_csi_metrics forwards or refuses itself): pe_place_csi_metrics.
+int pe_place_csi_full_metrics(pe_stack* s, uint32_t tgi, uint32_t count, const uint32_t* alloc_idx,
+                              pe_ranked_node* out, uint32_t* placed) {
+    if (!s || (!out && count)) return PE_EINVAL;
+    if (!s->metrics_on) return pe_place_csi_full(s, tgi, count, alloc_idx, out, placed);
+    if (!s->have_job || tgi >= s->tgs.size() || !csi_active(*s->tgs[tgi]) ||
+        (!tg_full_scan(s, *s->tgs[tgi]) && s->limit < 0x7FFFFFFFu))
+        return pe_place_csi_metrics(s, tgi, count, alloc_idx, out, placed);
+    if (placed) *placed = 0;
+    PE_FLUSH_RESET(s);
+    CsiScope csi_scope_(s);
+    s->pre_overflow.clear();
+    return place_csi_one(s, tgi, count, alloc_idx, out, placed, true, true);
 }
 
 int pe_place_csi_maps(const pe_stack* s, const pe_metric_count** counts, const uint32_t** counts_off,

@@ -5934,6 +5934,12 @@ __global__ void __launch_bounds__(256) k_sysg_scatter(SysCompactArgs A) {
 // Every loop is bounded without the data: positions by n, specials and segments
 // by csi_limit.h's constants, placements by count. A bound that does not hold
 // writes no record and raises eval_status[2], as k_csi_loop.
+// kMetrics (pe_place_csi_full_metrics): k_csi_loop<true>'s trace log, one byte per
+// consumed position of the call at index walked + j (csi_reason.h). The length a
+// Select consumes is known after the fold only, so pass 1 stores the byte of
+// every position it classifies; the bytes past `consumed` are stored again by
+// the next placement, whose log starts at walked + consumed, behind the barriers
+// between placements, or belong to no record. walked + j < count * n_visit.
 constexpr int kCsiFullBlock = 512;
 enum : uint8_t { kFullFiltered = 0, kFullExhausted = 1, kFullOption = 2, kFullStop = 3 };
 
@@ -5958,8 +5964,9 @@ struct CsiFullShared {
     double best_score;
 };
 
-template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_csi_full(BatchArgs A, CsiLoopArgs C, double* ev_score, uint8_t* ev_kind) {
+template <int BLOCK, bool kMetrics>
+__global__ void __launch_bounds__(BLOCK) k_csi_full(BatchArgs A, CsiLoopArgs C, double* ev_score, uint8_t* ev_kind,
+                                                    uint8_t* log, uint32_t log_cap) {
     __shared__ CsiFullShared<BLOCK> sh;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
     constexpr int W = BLOCK / 64;
@@ -6033,6 +6040,11 @@ __global__ void __launch_bounds__(BLOCK) k_csi_full(BatchArgs A, CsiLoopArgs C, 
                 }
                 ev_kind[j] = kind;
                 ev_score[j] = score;
+                if constexpr (kMetrics) {
+                    const uint64_t at = walked + (uint64_t)j;
+                    if (at < (uint64_t)log_cap)
+                        log[at] = csi_log_pack(unavailable ? (uint32_t)codes[row] : 0u, kind == kFullStop);
+                }
             }
             const bool is_stop = kind == kFullStop;
             const bool is_np = kind == kFullOption && score <= 0.0;
@@ -7161,8 +7173,9 @@ hipError_t pe_launch_md_gate(pe::MdNet* md, const uint32_t* coll_tg, uint32_t n,
 // per-position classes and scores a placement's passes hand on (device memory, no contents expected).
 uint32_t pe_csi_full_threads() { return pe::kCsiFullBlock; }
 
+// log (or null): pe_place_csi_full_metrics' trace log (k_csi_full<*, true>), as pe_launch_csi_loop's.
 hipError_t pe_launch_csi_full(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, double* ev_score, uint8_t* ev_kind,
-                              hipStream_t st) {
+                              hipStream_t st, uint8_t* log, uint32_t log_cap) {
     if (!a->perms || a->n_visit == 0 || a->n_visit >= 0x7FFFFFFFu - (uint32_t)pe::kCsiFullBlock || !a->full_out ||
         !a->eval_status || !c->codes || !c->set_of || !c->cls_state || !c->first || c->n_sets == 0 ||
         c->n_sets > (uint32_t)pe::kMaxCsiSets || c->n_rows != a->soa.n || a->tg.node_feas || a->packed_overlay ||
@@ -7170,16 +7183,26 @@ hipError_t pe_launch_csi_full(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, 
         return hipErrorInvalidValue;
     if (a->ask.n_dev > 0 && (!a->tg.dev_cls || !a->tg.dev_free)) return hipErrorInvalidValue;   // a device ask reads both
     if (a->tg.n_psets > 0 && !a->pset_lds && (!a->pset_g_tab || !a->pset_g_cnt)) return hipErrorInvalidValue;
+    // the trace log holds every position the call can consume (a Select consumes at most n_visit)
+    if (log && ((uint64_t)a->count * a->n_visit > (uint64_t)log_cap || (uint64_t)log_cap > pe::kCsiLogCap))
+        return hipErrorInvalidValue;
     const size_t lds = pe_place_lds_bytes(true, a->hash_bits, false, a->pset_lds);
     if (lds > 96u * 1024u) return hipErrorInvalidValue;   // (max_hash_bits' budget)
-    static bool attr = false;
-    if (!attr && lds > 32u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pe::k_csi_full<pe::kCsiFullBlock>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    static bool attr[2] = {false, false};   // per instantiation
+    const int mi = log ? 1 : 0;
+    if (!attr[mi] && lds > 32u * 1024u) {
+        // (the plain form is named first here and below: it is instantiated first and keeps its place in the code object)
+        const void* fn = !log ? reinterpret_cast<const void*>(&pe::k_csi_full<pe::kCsiFullBlock, false>)
+                              : reinterpret_cast<const void*>(&pe::k_csi_full<pe::kCsiFullBlock, true>);
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
         if (e != hipSuccess) return e;
-        attr = true;
+        attr[mi] = true;
     }
-    hipLaunchKernelGGL((pe::k_csi_full<pe::kCsiFullBlock>), dim3(1), dim3(pe::kCsiFullBlock), lds, st, *a, *c, ev_score,
-                       ev_kind);
+    if (!log)
+        hipLaunchKernelGGL((pe::k_csi_full<pe::kCsiFullBlock, false>), dim3(1), dim3(pe::kCsiFullBlock), lds, st, *a, *c,
+                           ev_score, ev_kind, (uint8_t*)nullptr, 0u);
+    else
+        hipLaunchKernelGGL((pe::k_csi_full<pe::kCsiFullBlock, true>), dim3(1), dim3(pe::kCsiFullBlock), lds, st, *a, *c,
+                           ev_score, ev_kind, log, log_cap);
     return hipGetLastError();
 }

@@ -74,10 +74,11 @@ hipError_t pe_launch_csi_first(const pe::BatchArgs* a, const pe::CsiLoopArgs* c,
 // page-locked memory of log_cap >= count * n_visit bytes
 hipError_t pe_launch_csi_loop(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st,
                               uint8_t* log = nullptr, uint32_t log_cap = 0);
-// pe_place_csi_full's loop (k_csi_full): ev_score / ev_kind hold n_visit entries each
+// pe_place_csi_full's loop (k_csi_full): ev_score / ev_kind hold n_visit entries each.
+// log (or null): the trace log of pe_place_csi_full_metrics (k_csi_full<*, true>), as pe_launch_csi_loop's
 uint32_t pe_csi_full_threads();
 hipError_t pe_launch_csi_full(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, double* ev_score, uint8_t* ev_kind,
-                              hipStream_t st);
+                              hipStream_t st, uint8_t* log = nullptr, uint32_t log_cap = 0);
 size_t pe_fold_feas_max_classes();
 hipError_t pe_launch_fold_feas_staged(const pe::NodeSoA* s, const unsigned char* class_src, uint8_t* class_dst,
                                       uint32_t ncls, const uint8_t* node_ok, uint8_t* feas, hipStream_t st);

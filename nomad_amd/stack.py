@@ -504,9 +504,26 @@ class _Stack:
         n = min(count, placed.value + 1)
         return [RankedNode.from_c(out[i], self.nodes, self._full_preempted(i, out[i])) for i in range(n)]
 
+    def PlaceCSIFullMetrics(self, tg, count: int, alloc_idx=None) -> List[RankedNode]:
+        """pe_place_csi_full_metrics: PlaceCSIFull with AllocMetric kept. The
+        records are PlaceCSIFull's; with EnableMetrics on, PlaceCSIMaps() then
+        gives each record's maps, the failed Select's included. A group that
+        runs no full passes: PlaceCSIMetrics; metrics off: PlaceCSIFull."""
+        out = (abi.pe_ranked_node * max(1, count))()
+        placed = C.c_uint32(0)
+        idx = None
+        if alloc_idx is not None:
+            if len(alloc_idx) != count:
+                raise ValueError("alloc_idx needs one index per placement")
+            idx = (C.c_uint32 * max(1, count))(*[int(i) for i in alloc_idx])
+        self._check(self._lib.pe_place_csi_full_metrics(self._h, self._tg_index(tg), count, idx, out,
+                                                        C.byref(placed)))
+        n = min(count, placed.value + 1)
+        return [RankedNode.from_c(out[i], self.nodes, self._full_preempted(i, out[i])) for i in range(n)]
+
     def PlaceCSIMaps(self) -> List[Dict]:
-        """pe_place_csi_maps: the maps of the last PlaceCSIMetrics' records, one
-        dict per record in LastMetrics' shape."""
+        """pe_place_csi_maps: the maps of the last PlaceCSIMetrics' or
+        PlaceCSIFullMetrics' records, one dict per record in LastMetrics' shape."""
         c, sc = C.POINTER(abi.pe_metric_count)(), C.POINTER(abi.pe_metric_score)()
         co, so, n = abi.u32p(), abi.u32p(), C.c_uint32(0)
         self._check(self._lib.pe_place_csi_maps(self._h, C.byref(c), C.byref(co), C.byref(sc), C.byref(so),

@@ -61,6 +61,17 @@ pe_place_csi_full (PE_ENGINE_LIB: the parent commit's build) only the pe_place
 leg runs.
 
     python tools/csi_probe.py --place-full [--reps 24] [--small] [--out profiles/csi_place_full/probe.json]
+
+--place-full-metrics: pe_place_csi_full_metrics with AllocMetric
+on against pe_place_csi_full with it off, on two handles of one build that
+alternate, over --place-full's setup (counts 1, 8 and 64, 24 repetitions after
+3 warm-up ones, each from pe_reset_plan and a cursor of its own). Per count:
+both calls' host-clock time, the metrics call's split into loop, host walk,
+trace and maps and the trace log bytes per call (pe_place_csi_metrics_stats on
+a third handle created with PE_CSI_TIME=1), and whether the two handles'
+records are equal. The same for --place-full's whole-list leg at count 8.
+
+    python tools/csi_probe.py --place-full-metrics [--reps 24] [--small] [--out profiles/csi_place_full_metrics/probe.json]
 """
 import argparse
 import copy
@@ -466,11 +477,109 @@ def measure_whole_list(nodes, allocs, job, csi, perm, volumes, node_volumes, rep
             "ratio_to_pe_place_median": float(np.median(t_full) / np.median(t_plain))}
 
 
+def full_metrics_leg(nodes, allocs, csi, perm, volumes, node_volumes, reps, count):
+    """One count of --place-full-metrics: metrics on against metrics off, alternating."""
+    st_met = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    st_met.EnableMetrics(True)
+    st_off = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    os.environ["PE_CSI_TIME"] = "1"     # read at create: only st_time reads the clock inside the call
+    st_time = handle(nodes, allocs, csi, perm, volumes, node_volumes)
+    del os.environ["PE_CSI_TIME"]
+    st_time.EnableMetrics(True)
+    limit, n = st_met.GetCursor()[1], len(nodes)
+    for st in (st_met, st_off, st_time):   # (the handle is a 64-bit pointer: never call without argtypes)
+        st._lib.pe_flush.restype = ctypes.c_int
+        st._lib.pe_flush.argtypes = [ctypes.c_void_p]
+
+    def stats(v):
+        a = np.asarray(v, dtype=np.float64)
+        return {"n": int(a.size), "median_us": float(np.median(a)), "p10_us": float(np.percentile(a, 10)),
+                "p90_us": float(np.percentile(a, 90))} if a.size else {"n": 0}
+    idx = list(range(count))
+    t_met, t_off, log_bytes, consumed, scored = [], [], [], [], []
+    split = {"loop": [], "walk": [], "trace": [], "maps": []}
+    placed = same = compared = csi_filtered = 0
+    for rep in range(reps + 3):
+        cursor = (rep * 977 + 13) % n
+        for st in (st_met, st_off, st_time):
+            st.ResetPlan()
+            st.SetJob(csi)
+            st.SetNodes(perm)
+            st.SetCursor(cursor, limit)
+            st._check(st._lib.pe_flush(st._h))
+        t0 = time.perf_counter()
+        recs = st_met.PlaceCSIFullMetrics(0, count, alloc_idx=idx)
+        dt_met = (time.perf_counter() - t0) * 1e6
+        maps = st_met.PlaceCSIMaps()
+        t0 = time.perf_counter()
+        plain = st_off.PlaceCSIFull(0, count, alloc_idx=idx)
+        dt_off = (time.perf_counter() - t0) * 1e6
+        st_time.PlaceCSIFullMetrics(0, count, alloc_idx=idx)
+        us, nb = st_time.place_csi_metrics_stats()
+        if rep < 3:
+            continue
+        t_met.append(dt_met)
+        t_off.append(dt_off)
+        log_bytes.append(nb)
+        for k, v in zip(("loop", "walk", "trace", "maps"), us):
+            split[k].append(v)
+        placed += sum(1 for r in recs if r.row >= 0)
+        consumed.append(sum(r.nodes_evaluated for r in recs))
+        compared += max(len(plain), len(recs))
+        same += sum(1 for a, b in zip(recs, plain)
+                    if (a.row, a.final_score, list(a.scores), a.nodes_evaluated, a.nodes_filtered, a.nodes_exhausted,
+                        a.new_offset) ==
+                    (b.row, b.final_score, list(b.scores), b.nodes_evaluated, b.nodes_filtered, b.nodes_exhausted,
+                     b.new_offset))
+        assert len(maps) == len(recs)
+        csi_filtered += sum(c for m in maps for k, c in m["ConstraintFiltered"].items()
+                            if k.startswith(("CSI ", "missing CSI ")))
+        scored.append(sum(len(m["ScoreMetaData"]) for m in maps))
+    for st in (st_met, st_off, st_time):
+        st.close()
+    return {"count": count,
+            "pe_place_csi_full_metrics_on_us": stats(t_met), "pe_place_csi_full_metrics_off_us": stats(t_off),
+            "ratio_on_to_off_median": float(np.median(t_met) / np.median(t_off)),
+            "split_us": {k: stats(v) for k, v in split.items()},
+            "log_bytes_per_call": {"median": float(np.median(log_bytes)), "min": int(np.min(log_bytes)),
+                                   "max": int(np.max(log_bytes))},
+            "positions_consumed_per_call": float(np.mean(consumed)), "placed_per_call": placed / max(1, len(t_met)),
+            "records_compared": int(compared), "records_equal": int(same),
+            "csi_filter_entries": int(csi_filtered), "score_items_per_call": float(np.mean(scored))}
+
+
+def measure_place_full_metrics(nodes, allocs, job, reps, counts=(1, 8, 64)):
+    """--place-full's setup (three datacenters, a target spread at job level); the
+    whole-list leg adds the group constraint that makes the group escape its class."""
+    rng = np.random.Generator(np.random.PCG64(17))
+    for nd in nodes:
+        u = rng.random()
+        nd.datacenter = "dc1" if u < 0.5 else ("dc2" if u < 0.8 else "dc3")
+        nd.compute_class()
+    perm = synth.shuffle(len(nodes), 5)
+    volumes, node_volumes = csi_state(nodes, max(counts) + 1, seed=6)
+    csi = copy.deepcopy(job)
+    csi.datacenters = ["dc1", "dc2", "dc3"]
+    csi.spreads = [Spread("${node.datacenter}", 100, [SpreadTarget("dc1", 50), SpreadTarget("dc2", 30)])]
+    csi.task_groups[0].csi_volumes = list(REQS)
+    out = {"nodes": len(nodes), "requests": len(REQS), "counts": {}}
+    for count in counts:
+        out["counts"][str(count)] = full_metrics_leg(nodes, allocs, csi, perm, volumes, node_volumes, reps, count)
+        print("place-full-metrics", count, json.dumps(out["counts"][str(count)]))
+    whole = copy.deepcopy(csi)
+    whole.task_groups[0].constraints = list(whole.task_groups[0].constraints) + [
+        Constraint("${node.unique.id}", "no-such-node", "!=")]
+    out["whole_list_count_8"] = full_metrics_leg(nodes, allocs, whole, perm, volumes, node_volumes, reps, 8)
+    print("place-full-metrics whole list", json.dumps(out["whole_list_count_8"]))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--place", action="store_true", help="the pe_place_csi leg (DESIGN.md §40)")
     ap.add_argument("--place-metrics", action="store_true", help="the pe_place_csi_metrics leg (DESIGN.md §41)")
     ap.add_argument("--place-full", action="store_true", help="the pe_place_csi_full leg (DESIGN.md §43)")
+    ap.add_argument("--place-full-metrics", action="store_true", help="the pe_place_csi_full_metrics leg (DESIGN.md §45)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--selects", type=int, default=200)
     ap.add_argument("--small", action="store_true", help="1/10 of the node counts (rehearsal)")
@@ -478,6 +587,16 @@ def main():
     a = ap.parse_args()
     scale = 10 if a.small else 1
     res = {"tool": "tools/csi_probe.py", "speculate": 0}
+    if a.place_full_metrics:
+        out = a.out if a.out != "profiles/csi/probe.json" else "profiles/csi_place_full_metrics/probe.json"
+        nodes, allocs = synth.cluster_c2(10000 // scale, seed=42)
+        res["tool"] += " --place-full-metrics"
+        res["cluster_c2"] = measure_place_full_metrics(nodes, allocs, synth.job_c2(64), max(a.reps, 24))
+        os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+            f.write("\n")
+        return
     if a.place_full:
         out = a.out if a.out != "profiles/csi/probe.json" else "profiles/csi_place_full/probe.json"
         nodes, allocs = synth.cluster_c2(10000 // scale, seed=42)
