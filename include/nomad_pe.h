@@ -439,6 +439,53 @@ int pe_plan_stop(pe_stack* s, const uint32_t* allocs, uint32_t n);
  * the alloc's node when it is this alloc (generic_sched.go:644, util.go:756,
  * 1043); otherwise nothing happens. */
 int pe_plan_pop_update(pe_stack* s, uint32_t alloc);
+/* computePlacements' loop over its `destructive` list (generic_sched.go:493-649)
+ * for `n` updates of task group `tg_index`: allocs[i] is the alloc-table row of
+ * update i's previous allocation. In list order, for i in [0, n):
+ * AppendStoppedAlloc(allocs[i]) (:543-547), a plain Select of the group on the
+ * current SetNodes list from the current cursor (:552), AppendAlloc on the
+ * option's node (:627); on nil PopUpdate(allocs[i]) (:639-645) and the loop
+ * ends (:521-525). out[0..*placed) are the placements; when *placed < n,
+ * out[*placed] is the nil Select's record, as pe_place writes it.
+ *
+ * One upload of the stop list, one launch of the loop kernel (k_destructive)
+ * and one synchronisation whatever `n`. Records and every later observable
+ * state equal those of the per-call sequence pe_plan_stop(&allocs[i], 1),
+ * pe_select(tg, NULL), then pe_commit, or pe_plan_pop_update(allocs[i]) and a
+ * break: node records, the job's and the group's collision counts, device free
+ * counts, dynamic ports and bandwidth; the stop flags, NodeUpdate with its
+ * order, the plan; the cursor, the limit, the EvalEligibility memo and its
+ * log. An alloc that is terminal, or already stopped or preempted in the plan,
+ * contributes its NodeUpdate entry and no resource change, as pe_plan_stop
+ * treats it. What pe_plan_stop invalidates per stop (static-port gates, the
+ * property sets) is invalidated once, at the end of the call.
+ *
+ * Penalty and preferred nodes are out of scope: getSelectOptions (:695-716)
+ * gives a penalty set only when the previous alloc failed or carries reschedule
+ * events, and a preferred node only with a sticky disk. The caller sends those
+ * updates through the per-call sequence, and the batched call through each
+ * maximal run of the rest.
+ *
+ * PE_EINVAL (nothing changed): tg_index or an alloc row out of range, an alloc
+ * listed twice. PE_ESTATE: not a generic stack, no job, no node list. n == 0:
+ * PE_OK with *placed == 0. PE_EUNSUPPORTED, checked before anything changes
+ * (cursor, limit, memo, plan and NodeUpdate untouched; the per-call sequence
+ * answers instead): a group that runs full passes (node affinities, spreads,
+ * distinct_property, or a limit a sibling group's Select latched to MaxInt32);
+ * pe_set_metrics on; a preempting stack; a handle over several devices; a
+ * reserved-cores ask, or a listed alloc that holds reserved cores; static port
+ * asks in the group; a task network on a snapshot with multi-device nodes; a
+ * group with CSI requests; two task groups of one name; the group's own
+ * unsupported reason; n beyond what the overlay of one launch holds.
+ * PE_EINTERNAL: a bounds guard of the kernel tripped (the updates before it
+ * stand, as *placed and the mirrors say). */
+int pe_place_destructive(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                         uint32_t* placed);
+/* Measurement aid: what the last pe_place_destructive issued. out3[0] kernel
+ * launches (the loop, and a copy launch when the SetNodes list was not on the
+ * device yet), [1] stream synchronisations, [2] uploads (the stop list, and
+ * that list). */
+int pe_place_destructive_stats(const pe_stack* s, uint64_t* out3);
 /* inplaceUpdate (util.go:692-806) for `n` snapshot allocs (alloc-table rows) against task group
  * `tg_index`, in list order. For each: AppendStoppedAlloc, SetNodes([its node]), Select(tg),
  * PopUpdate; when the Select returns an option, the updated alloc replaces the old one

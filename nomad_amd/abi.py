@@ -230,6 +230,11 @@ def bind_csi(lib):
     lib.pe_csi_check.argtypes = [H, C.c_uint32, u16p]
     lib.pe_csi_last_ms.restype = C.c_double
     lib.pe_csi_last_ms.argtypes = [H]
+    if hasattr(lib, "pe_place_destructive"):   # (absent in an A/B library from before it)
+        lib.pe_place_destructive.restype = C.c_int
+        lib.pe_place_destructive.argtypes = [H, C.c_uint32, u32p, C.c_uint32, C.POINTER(pe_ranked_node), u32p]
+        lib.pe_place_destructive_stats.restype = C.c_int
+        lib.pe_place_destructive_stats.argtypes = [H, u64p]
     if not hasattr(lib, "pe_place_csi"):   # present or absent behind one ABI version (an A/B library)
         return lib
     lib.pe_place_csi.restype = C.c_int
@@ -346,6 +351,7 @@ ENGINE_SYMBOLS = [
     "pe_place_csi_metrics", "pe_place_csi_maps", "pe_place_csi_metrics_stats", "pe_csi_reason_text",
     "pe_place_csi_full", "pe_csi_full_fold", "pe_csi_full_block", "pe_place_csi_full_metrics",
     "pe_probe_math", "pe_probe_go_sort",
+    "pe_place_destructive", "pe_place_destructive_stats",
 ]
 
 

@@ -988,6 +988,7 @@ struct pe_stack {
     std::vector<uint32_t> sys_log;     // its log
     uint32_t sys_taken = 0;            // log entries taken over
     uint64_t spec_stats[4] = {0, 0, 0, 0};   // runs, Selects served, rollbacks, records computed
+    uint64_t destructive_stats[3] = {0, 0, 0};   // the last pe_place_destructive: launches, synchronisations, uploads
     uint64_t wide_launches[2] = {0, 0};      // armed chain launches: with the k_phase pair, with one k_phases
     DevMem ck_rec, ck_coll_job, ck_coll_tg, ck_dev_free, ck_pset[pe::kMaxPsets];
     DevMem d_commit_rows, d_commit_offers;
@@ -11261,6 +11262,189 @@ int pe_place_csi_full(pe_stack* s, uint32_t tgi, uint32_t count, const uint32_t*
 }
 
 uint32_t pe_csi_full_block(void) { return pe_csi_full_threads(); }
+
+// ---- pe_place_destructive: computePlacements' destructive-update loop -----------
+// generic_sched.go:543-645 per update: AppendStoppedAlloc(prev), Select(tg),
+// AppendAlloc on an option; on nil PopUpdate(prev) and the group's loop ends.
+// One stop list upload, one k_destructive launch, one synchronisation. The host
+// decides from its mirrors what each stop changes (apply_stop_delta's rule for
+// the resources, build_collisions' for the counts), the kernel applies it
+// before that update's Select, and the mirrors are replayed from the records,
+// so that a later build_job_counts reproduces the device columns.
+static int place_destructive_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                                 uint32_t* placed) {
+    const std::string fn = "pe_place_destructive: ";
+    if (s->cfg.stack_kind != PE_STACK_GENERIC) return s->fail(PE_ESTATE, fn + "not a generic stack");
+    if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
+    if (!s->have_job) return s->fail(PE_ESTATE, "pe_set_job not called");
+    if (tgi >= s->tgs.size()) return s->fail(PE_EINVAL, "task group index out of range");
+    for (uint32_t i = 0; i < n; i++)
+        if (allocs[i] >= s->allocs.size()) return s->fail(PE_EINVAL, "alloc index out of range");
+    {
+        std::vector<uint32_t> sorted(allocs, allocs + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return s->fail(PE_EINVAL, fn + "an alloc listed twice");
+    }
+    if (s->visit.empty()) return s->fail(PE_ESTATE, fn + "no node list (pe_set_nodes)");
+    if (!n) return PE_OK;
+    // refusals, all before anything changes
+    TgPlan& g = *s->tgs[tgi];
+    if (!g.unsupported.empty()) return s->fail(PE_EUNSUPPORTED, g.unsupported);
+    if (tg_full_scan(s, g))
+        return s->fail(PE_EUNSUPPORTED, fn + "a group that runs full passes (node affinities or spreads; with stops "
+                                             "the property-set counts are rebuilt per commit)");
+    if (s->limit >= 0x7FFFFFFFu)
+        return s->fail(PE_EUNSUPPORTED, fn + "a limit latched to MaxInt32 by a sibling group's Select");
+    if (s->metrics_on) return s->fail(PE_EUNSUPPORTED, fn + "pe_set_metrics on");
+    if (s->cfg.preempt)
+        return s->fail(PE_EUNSUPPORTED, fn + "a preempting stack (the loop retries a nil Select with Preempt)");
+    if (!s->kids.empty()) return s->fail(PE_EUNSUPPORTED, fn + "a handle over several devices");
+    if (g.ask.cores > 0) return s->fail(PE_EUNSUPPORTED, fn + "a reserved-cores ask");
+    for (uint32_t i = 0; i < n; i++) {
+        const HostAlloc& a = s->allocs[allocs[i]];
+        if (a.cores[0] | a.cores[1] | a.cores[2] | a.cores[3] || a.cores_beyond)
+            return s->fail(PE_EUNSUPPORTED, fn + "a listed alloc holds reserved cores");
+    }
+    if (has_static(g)) return s->fail(PE_EUNSUPPORTED, fn + "static port asks in the group (a stop frees ports the gates were built with)");
+    if (tg_md(s, g)) return s->fail(PE_EUNSUPPORTED, fn + "a task network on a snapshot with multi-device nodes");
+    if (g.has_csi && !g.csi_reqs.empty())
+        return s->fail(PE_EUNSUPPORTED, fn + "a group with CSI requests");
+    for (size_t k = 0; k < s->tgs.size(); k++)
+        if (k != tgi && s->tgs[k]->name == g.name)
+            return s->fail(PE_EUNSUPPORTED, fn + "two task groups of one name (a stop moves the sibling's collision counts too)");
+    const int hash_bits = hash_bits_for(n, false, 0);
+    if (((uint64_t)1 << hash_bits) < 2ull * n)
+        return s->fail(PE_EUNSUPPORTED, fn + "n exceeds what the overlay of one launch holds");
+    int rc = spec_flush(s);
+    if (rc) return rc;
+    HIP_TRY(s, hipSetDevice(s->device));
+    rc = prepare_tg(s, tgi, s->visit, s->offset);
+    if (rc) return rc;
+    if (!g.psets.empty() || g.psets_dynamic)
+        return s->fail(PE_EUNSUPPORTED, fn + "a group that runs full passes (distinct_property)");
+    if (g.md_on) return s->fail(PE_EUNSUPPORTED, fn + "a task network on a snapshot with multi-device nodes");
+    // ---- nothing is refused from here on ----
+    s->gen++;
+    s->metrics_valid = false;
+    uint64_t* stats = s->destructive_stats;
+    stats[0] = stats[1] = stats[2] = 0;
+    const uint32_t m = (uint32_t)s->visit.size();
+    const uint32_t start = s->offset % m;
+    if (s->stop_count.size() != s->allocs.size()) s->stop_count.assign(s->allocs.size(), 0);
+    // what each stop changes, from the mirrors (the listed allocs are distinct:
+    // no update of the call changes another's answer)
+    std::vector<uint32_t> stops((size_t)pe::kDsWords * n);
+    bool other_group = false, any_live = false;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t ai = allocs[i];
+        const HostAlloc& a = s->allocs[ai];
+        const uint32_t slot = s->alloc_slot[ai];
+        const bool fresh = s->stop_count[ai] == 0;   // an alloc already in NodeUpdate adds its entry alone
+        uint32_t f = 0;
+        if (fresh && !a.terminal && slot != PE_NONE && s->h_preempted[slot] == 0) f |= pe::kDsLive;
+        if (fresh && !a.terminal && a.job == s->job_id) {
+            f |= pe::kDsJob;
+            if (a.tg == g.name) f |= pe::kDsTg;
+            else other_group = true;
+        }
+        any_live = any_live || (f & pe::kDsLive);
+        stops[pe::kDsWords * i] = slot;
+        stops[pe::kDsWords * i + 1] = a.row;
+        stops[pe::kDsWords * i + 2] = f;
+    }
+    {
+        const int frc = flush_fold(s);   // the class table reaches the device with the group's fold
+        if (frc) return frc;
+    }
+    pe::DestructiveArgs D;
+    std::memset(&D, 0, sizeof(D));
+    D.stops = reinterpret_cast<const uint32_t*>(stage_only(s, stops));
+    stats[2]++;
+    if (!D.stops) {   // the staging ring does not take it: a copy of its own
+        HIP_TRY(s, upload_s(s, s->d_stop_slots, stops));
+        D.stops = s->d_stop_slots.as<uint32_t>();
+        stats[0]++;
+    }
+    D.palloc = s->d_palloc.as<pe::PreemptAlloc>();
+    D.n_slots = (uint32_t)s->h_palloc.size();
+    D.preempted = s->d_preempted.as<uint8_t>();
+    D.dev_free = s->dev_packable ? s->d_dev_free.as<uint32_t>() : nullptr;
+    D.own_existing = s->d_own_existing.as<uint32_t>();
+    pe::BatchArgs A = batch_args(s, g);
+    A.hash_bits = hash_bits;
+    A.packed_overlay = packed_kbits(s, 1u << hash_bits, false);
+    if (!(s->d_visit_is_visit)) {   // the first call after SetNodes carries the list
+        stats[0]++;
+        stats[2]++;
+    }
+    HIP_TRY(s, upload_visit(s, s->visit));
+    A.perms = s->d_visit.as<uint32_t>();
+    A.n_visit = m;
+    A.count = n;
+    A.offset0 = start;
+    A.commit = 1;
+    A.writeback = 1;
+    HIP_TRY(s, s->h_place_out.ensure(sizeof(pe_ranked_node) * (size_t)n));
+    HIP_TRY(s, s->h_place_status.ensure(16));
+    A.full_out = s->h_place_out.dev<pe_ranked_node>();
+    A.eval_status = s->h_place_status.dev<uint32_t>();
+    if (!A.full_out || !A.eval_status) return s->fail(PE_EHIP, "mapped result buffers unavailable");
+    HIP_TRY_STATE(s, pe_launch_destructive(&A, &D, s->stream));
+    stats[0]++;
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    stats[1]++;
+    uint32_t st3[3];
+    std::memcpy(st3, const_cast<const uint32_t*>(s->h_place_status.as<uint32_t>()), sizeof(st3));
+    const uint32_t p = std::min(st3[0], n), got = std::min(n, p + 1);
+    // the host mirrors, in list order, as the per-call sequence leaves them
+    // (a tripped guard: the updates before it are in HBM and are replayed too;
+    // the nil Select's update leaves nothing: AppendStoppedAlloc, then PopUpdate)
+    const pe_ranked_node* recs = s->h_place_out.as<pe_ranked_node>();
+    for (uint32_t i = 0; i < p; i++)
+        if (recs[i].row < 0 || (size_t)recs[i].row >= s->nodes.size())
+            return s->fail(PE_EINTERNAL, "k_destructive: a placement's row out of range");
+    if (!st3[2]) std::memcpy(out, recs, sizeof(pe_ranked_node) * got);
+    auto& plan = plan_of(s);
+    for (uint32_t i = 0; i < p; i++) {
+        const uint32_t ai = allocs[i], row = s->allocs[ai].row;
+        s->node_update[row].push_back(ai);
+        s->stop_count[ai]++;
+        if (stops[pe::kDsWords * i + 2] & pe::kDsLive) s->h_preempted[s->alloc_slot[ai]] = 2;
+        plan.emplace_back(g.name, (uint32_t)recs[i].row);
+    }
+    s->offer_row = -1;
+    s->offset = st3[1] % m;
+    if (any_live) invalidate_static(s);   // the stopped allocs' ports
+    for (auto& t : s->tgs) t->psets_built = false;   // the job's stopped allocs feed the property sets
+    if (p) invalidate_job_distinct(s, tgi);
+    if (st3[2]) return s->fail(PE_EINTERNAL, "k_destructive: a bounds guard tripped (a stop's slot or row out of range)");
+    // the eligibility span of each Select's consumed window
+    uint32_t cur = start;
+    for (uint32_t i = 0; i < got; i++) {
+        elig_log_span(s, tgi, cur, out[i].nodes_evaluated);
+        cur = out[i].new_offset;
+    }
+    if (placed) *placed = p;
+    // a listed alloc of another group of the job: that group's column follows from the mirrors
+    if (other_group) return build_job_counts(s);
+    return PE_OK;
+}
+
+int pe_place_destructive(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                         uint32_t* placed) {
+    if (!s || (n && (!allocs || !out))) return PE_EINVAL;
+    if (placed) *placed = 0;
+    PE_FLUSH_RESET(s);
+    s->pre_overflow.clear();
+    return place_destructive_one(s, tgi, allocs, n, out, placed);
+}
+
+int pe_place_destructive_stats(const pe_stack* s, uint64_t* out3) {
+    if (!s || !out3) return PE_EINVAL;
+    for (int i = 0; i < 3; i++) out3[i] = s->destructive_stats[i];
+    return PE_OK;
+}
 
 // The maps of pe_place_csi_metrics' records, after the loop's synchronisation:
 // record k's window [its start, + nodes_evaluated) is walked on the host against

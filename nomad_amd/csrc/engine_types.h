@@ -411,6 +411,27 @@ struct CsiLoopArgs {
     uint32_t* first;               // [ncls] F[c]: the deciding position from the call's cursor, ~0u none
 };
 
+// k_destructive (pe_place_destructive): the stop of each update, applied by the
+// loop's own wave before that update's Select. The host resolves what the
+// mirrors decide into three flags per update (apply_stop_delta's and
+// build_collisions' rules); the alloc's resources are read from the resident
+// per-node CSR by slot.
+struct PreemptAlloc;
+enum : uint32_t {
+    kDsLive = 1u,   // the alloc holds resources on its node (not terminal, not stopped or preempted in the plan)
+    kDsJob = 2u,    // it counts in the job's collision column (and in own_existing)
+    kDsTg = 4u,     // ... and in the task group's
+};
+constexpr uint32_t kDsWords = 3;   // words per update: CSR slot, node row, flags
+struct DestructiveArgs {
+    const uint32_t* stops;         // [count][kDsWords]
+    const PreemptAlloc* palloc;    // [n_slots] the snapshot's non-terminal allocs (per-node CSR)
+    uint32_t n_slots;
+    uint8_t* preempted;            // [n_slots] 2 = stopped in the plan
+    uint32_t* dev_free;            // [n] or null: the snapshot is not packable
+    uint32_t* own_existing;        // [n] or null
+};
+
 // Full-scan Select reduction record (one per workgroup, and per GPU shard).
 // With limit >= options the LimitIterator returns every option, the first
 // kMaxSkip non-positive ones (in visit order) moved to the end; MaxScore then

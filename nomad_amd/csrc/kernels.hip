@@ -4903,6 +4903,277 @@ __global__ void __launch_bounds__(256) k_md_gate(MdNet* md, const uint32_t* coll
 
 #include "evict.inc"
 
+// ---- pe_place_destructive: computePlacements' destructive-update loop ----------
+// Per update (generic_sched.go:543-645): AppendStoppedAlloc of the previous
+// alloc, Select, AppendAlloc on an option; on nil PopUpdate and the loop ends.
+// k_window's shape (one wave, 64 positions per chunk, the 128-position register
+// ring kept across Selects, the same ballot closed form, the launch's
+// placements in the LDS overlay, written back at the end). New is what happens
+// before each Select: one lane applies the stop to the HBM columns with plain
+// loads and stores (k_plan_stop's arithmetic; one wave owns the launch, so no
+// atomics), the wave fences at workgroup scope so that its next load_node sees
+// them, and the ring is cut at the first cached position that holds the stopped
+// row, wherever it lies ahead of the cursor.
+// Stops stay out of the overlay: its k x ask model holds because every
+// placement is the same ask. A stop on a row that already holds placements of
+// the launch first folds the row's overlay entry into HBM (the entry stays with
+// count 0), so the stop meets the node as the per-call sequence's stop does:
+// the device offers of the row's later placements are then assigned from the
+// counts the stop returned to, in the sequence's order.
+// Every loop is bounded without the data: chunks by n + skew, updates by count.
+// A slot or row of the stop list out of range raises eval_status[2] and ends
+// the call before anything is indexed with it.
+__device__ __forceinline__ void ds_fold_row(const BatchArgs& A, const Overlay& ov, uint32_t row) {
+    const int h = ov_slot(ov, row);
+    if (h < 0) return;
+    const uint32_t e = ov.keys[h];
+    const uint32_t k = ov.k ? ov.k[h] : e & ov.kmask;
+    if (!k) return;
+    NodeRec& r = A.soa.rec[row];
+    r.used_cpu += (int64_t)k * A.ask.cpu;
+    r.used_mem += (int64_t)k * A.ask.mem;
+    r.used_disk += (int64_t)k * A.ask.disk;
+    r.used_mbits += (int32_t)k * A.ask.commit_mbits;
+    r.used_dyn += (int32_t)k * A.ask.commit_dyn;
+    A.soa.coll_job[row] += k;
+    A.tg.coll_tg[row] += k;
+    if (A.ask.n_dev > 0) A.tg.dev_free[row] = dev_after(A.ask, A.tg.dev_cls[r.cls], A.tg.dev_free[row], k);
+    if (ov.k) ov.k[h] = 0;
+    else ov.keys[h] = e & ~ov.kmask;
+}
+
+// AppendStoppedAlloc (sign +1) / PopUpdate (sign -1, the same steps in reverse order) of one update (one lane).
+__device__ __forceinline__ void ds_stop(const BatchArgs& A, const DestructiveArgs& D, uint32_t slot, uint32_t row,
+                                        uint32_t flags, int sign) {
+    const auto resources = [&]() {
+        if (!(flags & kDsLive)) return;
+        const PreemptAlloc x = D.palloc[slot];
+        NodeRec& r = A.soa.rec[row];
+        r.used_cpu -= sign * x.cpu;
+        r.used_mem -= sign * x.mem;
+        r.used_disk -= sign * x.disk;
+        r.used_mbits -= sign * x.mbits;
+        r.used_dyn -= sign * x.dyn;
+        if (D.dev_free) {
+            uint32_t d = 0;
+            for (int k = 0; k < 4 && k < (int)x.n_dev; k++) d += byte_of(x.dev_c, k) << (8 * byte_of(x.dev_g, k));
+            D.dev_free[row] += sign > 0 ? d : 0u - d;
+        }
+    };
+    const auto counts = [&]() {
+        const uint32_t one = sign > 0 ? 0xFFFFFFFFu : 1u;   // -1 / +1
+        if (flags & kDsJob) {
+            A.soa.coll_job[row] += one;
+            if (D.own_existing) D.own_existing[row] += one;
+        }
+        if (flags & kDsTg) A.tg.coll_tg[row] += one;
+    };
+    if (sign > 0) {
+        resources();
+        counts();
+        if (flags & kDsLive) D.preempted[slot] = 2;
+    } else {
+        if (flags & kDsLive) D.preempted[slot] = 0;
+        counts();
+        resources();
+    }
+}
+
+// The stop's (or its undo's) stores become visible to every lane's next loads
+// of the node columns: one CU's vector L1 serves the whole workgroup, so a
+// release / acquire pair at workgroup scope (a wait for the stores, no cache
+// maintenance) around the wave's ordering point is all it takes.
+__device__ __forceinline__ void ds_publish() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    wave_sync();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// Cut the cached window [0, have) at the first cached position that holds `row`.
+__device__ __forceinline__ uint32_t ds_cut(uint32_t row, uint32_t rb, uint32_t have, uint32_t rw0, uint32_t rw1,
+                                           int lane) {
+    if (!have) return have;
+    const uint32_t j0 = ((uint32_t)lane - rb) & 127u, j1 = (64u + (uint32_t)lane - rb) & 127u;
+    const bool bad0 = j0 < have && rw0 == row;
+    const bool bad1 = j1 < have && rw1 == row;
+    if (__ballot(bad0 || bad1)) {
+        uint32_t cut = min(bad0 ? j0 : 128u, bad1 ? j1 : 128u);
+        for (int off = 32; off > 0; off >>= 1) cut = min(cut, (uint32_t)__shfl_xor((int)cut, off));
+        if (cut < have) have = cut;
+    }
+    return have;
+}
+
+__global__ void __launch_bounds__(64) k_destructive(BatchArgs A, DestructiveArgs D) {
+    __shared__ double aside_score[kMaxSkip];
+    __shared__ int aside_pos[kMaxSkip];
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
+    const int lane = threadIdx.x;
+    const uint32_t n = A.n_visit;
+    const uint32_t* perm = A.perms;
+    const uint8_t* class_ok = A.tg.class_ok;
+    const uint32_t H = 1u << A.hash_bits;
+    Overlay ov;
+    ov.bits = A.hash_bits;
+    ov.mask = H - 1;
+    ov.keys = reinterpret_cast<uint32_t*>(dyn_smem);
+    ov.k = A.packed_overlay ? nullptr : ov.keys + H;
+    ov.kshift = A.packed_overlay;
+    ov.kmask = A.packed_overlay ? (1u << A.packed_overlay) - 1u : 0u;
+    for (uint32_t i = lane; i < H; i += 64) ov.keys[i] = kEmpty;
+    __syncthreads();
+
+    uint32_t offset = n ? A.offset0 % n : 0u;
+    uint32_t placed = 0;
+    int st0 = kFiltered, st1 = kFiltered;
+    double sc0 = 0.0, sc1 = 0.0;
+    uint32_t rw0 = kEmpty, rw1 = kEmpty;
+    uint32_t rb = 0;     // ring index of the cursor
+    uint32_t have = 0;   // relative positions [0, have) are cached (have <= min(n, 128) at loop top)
+    uint32_t guard = 0;
+
+    for (uint32_t it = 0; n && it < A.count; it++) {
+        // ---- AppendStoppedAlloc(allocs[it]) ----
+        const uint32_t s_slot = D.stops[kDsWords * it], s_row = D.stops[kDsWords * it + 1];
+        const uint32_t s_flags = D.stops[kDsWords * it + 2];
+        if (s_flags) {
+            if (s_row >= A.soa.n || ((s_flags & kDsLive) && s_slot >= D.n_slots)) {
+                guard = 1u;
+                break;
+            }
+            if (lane == 0) {
+                ds_fold_row(A, ov, s_row);
+                ds_stop(A, D, s_slot, s_row, s_flags, +1);
+            }
+            ds_publish();
+            have = ds_cut(s_row, rb, have, rw0, rw1, lane);
+        }
+
+        // ---- Select: k_window's pull ----
+        uint32_t r = 0, a = 0;
+        double best_score = -__builtin_inf();
+        int best_pos = -1;
+        uint32_t n_filtered = 0, n_exhausted = 0;
+        uint32_t consumed = n;
+        bool stopped = false;
+        double lbest_s = -__builtin_inf();
+        int lbest_p = -1;
+        const uint32_t skew = rb & 63u;
+        for (uint32_t k = 0; 64u * k < n + skew; k++) {
+            const int j = (int)(64u * k + (uint32_t)lane) - (int)skew;   // relative visit position
+            const bool valid = j >= 0 && (uint32_t)j < n;
+            const bool s1 = (((rb >> 6) + k) & 1u) != 0;
+            int st = s1 ? st1 : st0;
+            double sc = s1 ? sc1 : sc0;
+            const bool need = valid && (uint32_t)j >= have;
+            if (__ballot(need)) {
+                // as k_window: this chunk and the next one, all loads first
+                const uint32_t j2 = (uint32_t)(j + 64);
+                const bool need2 = j2 < n;
+                uint32_t p1 = need ? offset + (uint32_t)j : 0u;
+                uint32_t p2 = need2 ? offset + j2 : 0u;
+                if (p1 >= n) p1 -= n;
+                if (p2 >= n) p2 -= n;
+                const uint32_t row1 = perm[p1], row2 = perm[p2];
+                NodeIn in1, in2;
+                load_node(A.soa, A.tg, row1, in1);
+                load_node(A.soa, A.tg, row2, in2);
+                const uint32_t dk1 = ov_count(ov, row1), dk2 = ov_count(ov, row2);
+                NodeEval e1, e2;
+                e1.score = 0.0;
+                e2.score = 0.0;
+                eval_loaded<false, false>(A.soa, A.tg, class_ok, A.ask, dk1, A.penalty_bits, A.log10, nullptr, row1,
+                                          in1, &e1);
+                eval_loaded<false, false>(A.soa, A.tg, class_ok, A.ask, dk2, A.penalty_bits, A.log10, nullptr, row2,
+                                          in2, &e2);
+                if (need) {
+                    st = e1.status;
+                    sc = e1.score;
+                    if (s1) { st1 = st; sc1 = sc; rw1 = row1; } else { st0 = st; sc0 = sc; rw0 = row1; }
+                }
+                if (need2) {
+                    if (s1) { st0 = e2.status; sc0 = e2.score; rw0 = row2; }
+                    else { st1 = e2.status; sc1 = e2.score; rw1 = row2; }
+                }
+                have = min(64u * (k + 2) - skew, n);
+            }
+
+            const bool is_opt = valid && st == kOption;
+            const bool is_np = is_opt && sc <= 0.0;
+            uint32_t np_tot;
+            const uint32_t np_before = a + block_prefix<64>(is_np, nullptr, &np_tot);
+            const bool aside = is_np && np_before < (uint32_t)kMaxSkip;
+            const bool ret = is_opt && !aside;
+            uint32_t ret_tot;
+            const uint32_t ret_before = r + block_prefix<64>(ret, nullptr, &ret_tot);
+            const uint64_t sm = __ballot(ret && ret_before == A.limit - 1u);
+            const int stop_lane = sm ? (int)__ffsll((long long)sm) - 1 : 64;
+            const bool pulled = valid && lane <= stop_lane;
+            if (aside && pulled) {
+                aside_score[np_before] = sc;
+                aside_pos[np_before] = j;
+            }
+            if (ret && ret_before < A.limit && sc > lbest_s) { lbest_s = sc; lbest_p = j; }
+            n_filtered += (uint32_t)__popcll(__ballot(pulled && st == kFiltered));
+            n_exhausted += (uint32_t)__popcll(__ballot(pulled && st == kExhausted));
+            a += (uint32_t)__popcll(__ballot(aside && pulled));
+            if (sm) {
+                consumed = 64u * k + (uint32_t)stop_lane - skew + 1u;
+                r = A.limit;
+                stopped = true;
+                break;
+            }
+            r += ret_tot;
+        }
+        {
+            double cs;
+            int cp;
+            block_argmax<64>(lbest_p >= 0, lbest_s, lbest_p, nullptr, nullptr, &cs, &cp);
+            if (cp != 0x7FFFFFFF) { best_score = cs; best_pos = cp; }
+        }
+        wave_sync();   // the set-aside options in LDS
+        if (!stopped) {
+            const uint32_t take = min(a, A.limit - r);
+            for (uint32_t i = 0; i < take; i++) {
+                if (aside_score[i] > best_score) { best_score = aside_score[i]; best_pos = aside_pos[i]; }
+            }
+        }
+        int win_row = -1;
+        if (best_pos >= 0) {
+            uint32_t pos = offset + (uint32_t)best_pos;
+            if (pos >= n) pos -= n;
+            win_row = (int)perm[pos];
+        }
+        uint32_t no = offset + (consumed % n);
+        if (no >= n) no -= n;
+        if (lane == 0) {
+            emit_placement<false>(A, class_ok, ov, nullptr, 0u, it, win_row, best_score, consumed, n_filtered,
+                                  n_exhausted, no);
+            if (win_row >= 0) ov_add(ov, (uint32_t)win_row);
+            else if (s_flags) ds_stop(A, D, s_slot, s_row, s_flags, -1);   // PopUpdate(allocs[it])
+        }
+        wave_sync();
+        offset = no;
+        // slide the cache (as k_window: a full pass restarts the ring)
+        if (stopped) {
+            rb = (rb + consumed) & 127u;
+            have = have > consumed ? have - consumed : 0u;
+        } else {
+            have = 0;
+        }
+        if (win_row < 0) break;
+        have = ds_cut((uint32_t)win_row, rb, have, rw0, rw1, lane);
+        placed++;
+    }
+    if (lane == 0) {
+        A.eval_status[0] = placed;
+        A.eval_status[1] = offset;
+        A.eval_status[2] = guard;
+    }
+    ds_publish();   // the last stop (or its undo) before every lane's write-back
+    if (A.writeback) writeback_overlay<64, false, false>(A, ov, H, nullptr);
+}
+
 // inplaceUpdate's loop (util.go:743-760) over a list of snapshot allocs: per
 // update AppendStoppedAlloc, a Select on the alloc's node alone, PopUpdate and,
 // on an option, the updated alloc in place of the old one. Only updates on one
@@ -6878,6 +7149,20 @@ hipError_t pe_launch_csi_loop(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, 
     const size_t lds = pe_place_lds_bytes(false, a->hash_bits, a->packed_overlay != 0, 0);
     if (log) hipLaunchKernelGGL(pe::k_csi_loop<true>, dim3(1), dim3(64), lds, st, *a, *c, log, log_cap);
     else hipLaunchKernelGGL(pe::k_csi_loop<false>, dim3(1), dim3(64), lds, st, *a, *c, (uint8_t*)nullptr, 0u);
+    return hipGetLastError();
+}
+
+// One evaluation, one wave; the overlay must hold the launch's placements, the
+// stop list kDsWords words per update.
+hipError_t pe_launch_destructive(const pe::BatchArgs* a, const pe::DestructiveArgs* d, hipStream_t st) {
+    if (!a->perms || a->n_visit == 0 || !a->full_out || !a->eval_status || !a->soa.rec || !a->soa.coll_job ||
+        !a->tg.coll_tg || !d->stops || (d->n_slots && (!d->palloc || !d->preempted)) || a->hash_bits < 0 ||
+        a->hash_bits > 30 ||
+        ((uint64_t)1 << a->hash_bits) < 2ull * a->count || a->ask.cores > 0 || a->tg.n_psets != 0)
+        return hipErrorInvalidValue;
+    if (a->ask.n_dev > 0 && (!a->tg.dev_cls || !a->tg.dev_free)) return hipErrorInvalidValue;   // a device ask reads both
+    const size_t lds = pe_place_lds_bytes(false, a->hash_bits, a->packed_overlay != 0, 0);
+    hipLaunchKernelGGL(pe::k_destructive, dim3(1), dim3(64), lds, st, *a, *d);
     return hipGetLastError();
 }
 

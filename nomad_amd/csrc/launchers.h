@@ -74,6 +74,8 @@ hipError_t pe_launch_csi_first(const pe::BatchArgs* a, const pe::CsiLoopArgs* c,
 // page-locked memory of log_cap >= count * n_visit bytes
 hipError_t pe_launch_csi_loop(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, hipStream_t st,
                               uint8_t* log = nullptr, uint32_t log_cap = 0);
+// pe_place_destructive's loop (k_destructive): the stop list holds a->count updates.
+hipError_t pe_launch_destructive(const pe::BatchArgs* a, const pe::DestructiveArgs* d, hipStream_t st);
 // pe_place_csi_full's loop (k_csi_full): ev_score / ev_kind hold n_visit entries each.
 // log (or null): the trace log of pe_place_csi_full_metrics (k_csi_full<*, true>), as pe_launch_csi_loop's
 uint32_t pe_csi_full_threads();

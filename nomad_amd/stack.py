@@ -1193,6 +1193,27 @@ def inplace_update_by_select(stack, tg, allocs: Sequence[int]):
     return records, status
 
 
+def place_destructive_by_select(stack, tg, allocs: Sequence[int]):
+    """computePlacements' destructive-update loop (generic_sched.go:543-645) as
+    the per-call sequence, on any stack with StopAllocs / SelectRaw / Commit /
+    PopUpdate (the engine's and the oracle's): per update
+    AppendStoppedAlloc(prev), Select(tg) on the current list from the current
+    cursor, AppendAlloc on an option; on nil PopUpdate(prev) and the loop ends.
+    SelectRaw keeps the nil Select's counters. Returns the records in
+    PlaceDestructive's shape: the placements, then the nil record if any."""
+    records = []
+    for ai in allocs:
+        ai = int(ai)
+        stack.StopAllocs([ai])
+        r = stack.SelectRaw(tg)
+        records.append(r)
+        if r.row < 0:
+            stack.PopUpdate(ai)
+            break
+        stack.Commit(tg, r.row)
+    return records
+
+
 def _is_dimension(reason: str) -> bool:
     """Whether an AllocMetric reason is one ExhaustedNode records
     (rank.go:255-497: a network or devices message, or AllocsFit's dimension)."""
@@ -1264,6 +1285,38 @@ class GenericStack(_Stack):
     def __init__(self, batch: bool = False, config: SchedulerConfig = None, device: int = 0,
                  devices: Optional[Sequence[int]] = None):
         super().__init__(load_engine(), "pe_", batch, config, device, devices)
+
+    def PlaceDestructive(self, tg, allocs: Sequence[int], fallback: bool = True) -> List[RankedNode]:
+        """computePlacements' destructive-update loop (generic_sched.go:543-645)
+        for the previous allocs `allocs` (alloc-table rows) of task group `tg`
+        in one call (pe_place_destructive): per update AppendStoppedAlloc, a
+        plain Select, AppendAlloc; a nil Select pops its stop and ends the loop.
+        Returns the records as Place does: the placements and, when the loop
+        ended early, the nil Select's record (row -1). Updates with penalty or
+        preferred nodes go through the per-call sequence. A job the batched
+        path refuses (Unsupported) is answered by place_destructive_by_select
+        when `fallback`, else the refusal propagates."""
+        allocs = [int(a) for a in allocs]
+        n = len(allocs)
+        try:
+            if not hasattr(self._lib, "pe_place_destructive"):
+                raise Unsupported(abi.PE_EUNSUPPORTED, "no batched destructive update behind this ABI")
+            a = np.ascontiguousarray(np.asarray(allocs or [0], dtype=np.uint32))
+            out = (abi.pe_ranked_node * max(1, n))()
+            placed = C.c_uint32(0)
+            self._check(self._lib.pe_place_destructive(self._h, self._tg_index(tg), a.ctypes.data_as(abi.u32p), n, out,
+                                                       C.byref(placed)))
+        except Unsupported:
+            if not fallback:
+                raise
+            return place_destructive_by_select(self, tg, allocs)
+        return [RankedNode.from_c(out[i], self.nodes) for i in range(min(n, placed.value + 1))]
+
+    def place_destructive_stats(self):
+        """(launches, synchronisations, uploads) of the last PlaceDestructive call."""
+        out = (C.c_uint64 * 3)()
+        self._check(self._lib.pe_place_destructive_stats(self._h, out))
+        return tuple(int(x) for x in out)
 
     def StageOrders(self, orders: np.ndarray):
         """Stage E visit orders (E x n rows, each a shuffled SetNodes list) in HBM."""

@@ -1,0 +1,218 @@
+"""Destructive-update probe: what pe_place_destructive costs
+against the per-call sequence it replaces.
+
+  (default) The C2 cluster of bench.py at its default node count (10k nodes,
+      seed 42), where an older version of svc-c2 already holds 600 allocs on
+      distinct random nodes; all 600 are updated, in shuffled order. Two
+      handles of one build and one type (GenericStack, metrics off):
+        call      pe_place_destructive(tg, allocs, 600)
+        sequence  per update pe_plan_stop(&alloc, 1), pe_select(tg, NULL), then
+                  pe_commit, or pe_plan_pop_update and a break
+      Every repetition starts from pe_reset_plan, pe_set_job and pe_set_nodes
+      followed by pe_flush (not timed), so both timed sections begin on an idle
+      device; both end with pe_flush (queued device work) and a device
+      synchronise (the call's own synchronisation has already drained its
+      stream). Three warm-up pairs, then the two versions alternate in one
+      process, the order swapping every pair. The host clock runs around the ctypes calls alone; the sequence's
+      arguments are built before it starts. The records are compared. The
+      call's own counters (pe_place_destructive_stats) give its launches,
+      synchronisations and uploads.
+
+          python tools/destructive_probe.py [--pairs 8] [--small] [--out profiles/place_destructive/probe.json]
+
+  --headline PARENT_LIB  `bench.py --gpus 1 --steps N --warmup 20` in fresh
+      processes, the parent commit's library (PE_ENGINE_LIB) and this tree's
+      alternating, the order swapping every leg.
+
+          python tools/destructive_probe.py --headline /path/to/parent/libnomadpe.so [--legs 6] [--steps 40000]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from nomad_amd import abi, synth  # noqa: E402
+from nomad_amd.structs import Allocation  # noqa: E402
+
+
+def shape(n, own, seed=42):
+    """bench.py's cluster_c2 where an older version of svc-c2 holds `own` allocs on distinct nodes."""
+    nodes, allocs = synth.cluster_c2(n, seed=seed)
+    rng = np.random.Generator(np.random.PCG64(seed + 1))
+    for k in rng.choice(n, size=own, replace=False):
+        allocs.append(Allocation(node_id=nodes[int(k)].id, job_id="svc-c2", task_group="web",
+                                 cpu_shares=500, memory_mb=256, disk_mb=150, priority=50))
+    job = synth.job_c2(own)
+    job.version = 7
+    own_idx = [i for i, a in enumerate(allocs) if a.job_id == "svc-c2"]
+    upd = [own_idx[int(k)] for k in rng.permutation(len(own_idx))]
+    return nodes, allocs, job, upd
+
+
+def hip_runtime():
+    """The HIP runtime the engine library is linked against (the process holds one copy)."""
+    for name in ("libamdhip64.so", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so")):
+        try:
+            hip = C.CDLL(name)
+        except OSError:
+            continue
+        hip.hipDeviceSynchronize.restype = C.c_int
+        hip.hipDeviceSynchronize.argtypes = []
+        return hip
+    raise RuntimeError("libamdhip64.so not found")
+
+
+def rec_key(r):
+    return (r.row, r.final_score, r.nodes_evaluated, r.nodes_filtered, r.nodes_exhausted, r.new_offset)
+
+
+def call_vs_sequence(args):
+    from nomad_amd.stack import GenericStack
+    n, own = (2000, 200) if args.small else (10000, 600)
+    nodes, allocs, job, upd = shape(n, own)
+    perm = synth.shuffle(n, 7)
+
+    def handle():
+        st = GenericStack()
+        st.SetState(nodes, allocs)
+        st.SetJob(job)
+        return st
+    a, b = handle(), handle()
+    lib = a._lib
+    lib.pe_flush.restype = C.c_int
+    lib.pe_flush.argtypes = [C.c_void_p]
+    length = len(upd)
+    arr = np.ascontiguousarray(np.asarray(upd, dtype=np.uint32))
+    recs = (abi.pe_ranked_node * length)()
+    placed = C.c_uint32(0)
+    one = [(C.c_uint32 * 1)(int(x)) for x in upd]
+    seq = (abi.pe_ranked_node * length)()
+
+    hip = hip_runtime()
+
+    def settle(st):
+        return lib.pe_flush(st._h) or hip.hipDeviceSynchronize()
+
+    def prepare(st):
+        st.ResetPlan()
+        st.SetJob(job)
+        st.SetNodes(perm)
+        assert settle(st) == 0
+
+    def run_call():
+        prepare(a)
+        t0 = time.perf_counter()
+        rc = lib.pe_place_destructive(a._h, 0, arr.ctypes.data_as(abi.u32p), length, recs, C.byref(placed))
+        rc = rc or settle(a)
+        t1 = time.perf_counter()
+        assert rc == 0, rc
+        return (t1 - t0) * 1e6
+
+    def run_sequence():
+        prepare(b)
+        done = 0
+        t0 = time.perf_counter()
+        for k in range(length):
+            rc = lib.pe_plan_stop(b._h, one[k], 1) or lib.pe_select(b._h, 0, None, C.byref(seq[k]))
+            assert rc == 0, rc
+            done = k + 1
+            if seq[k].row < 0:
+                lib.pe_plan_pop_update(b._h, int(upd[k]))
+                break
+            rc = lib.pe_commit(b._h, 0, seq[k].row)
+            assert rc == 0, rc
+        rc = settle(b)
+        t1 = time.perf_counter()
+        assert rc == 0, rc
+        return (t1 - t0) * 1e6, done
+
+    pairs, same, counters = [], True, set()
+    for r in range(args.pairs + 3):
+        order = ("call", "sequence") if r % 2 == 0 else ("sequence", "call")
+        t = {}
+        for who in order:
+            if who == "call":
+                t["call"] = run_call()
+                counters.add(a.place_destructive_stats())
+            else:
+                t["sequence"], done = run_sequence()
+        got = min(length, placed.value + 1)
+        same = same and got == done and all(rec_key(recs[k]) == rec_key(seq[k]) for k in range(got))
+        if r >= 3:
+            pairs.append({"pair": r - 2, "order": order[0] + " first", "call_us": t["call"], "sequence_us": t["sequence"],
+                          "difference_us": t["sequence"] - t["call"]})
+    diff = np.asarray([p["difference_us"] for p in pairs])
+    call = np.asarray([p["call_us"] for p in pairs])
+    sequ = np.asarray([p["sequence_us"] for p in pairs])
+    return {"tool": "tools/destructive_probe.py", "nodes": n, "updates": length, "placed": int(placed.value),
+            "records_equal": bool(same),
+            "call_us": {"min": float(call.min()), "median": float(np.median(call)), "max": float(call.max())},
+            "sequence_us": {"min": float(sequ.min()), "median": float(np.median(sequ)), "max": float(sequ.max())},
+            "median_paired_difference_us": float(np.median(diff)),
+            "paired_difference_range_us": [float(diff.min()), float(diff.max())],
+            "ranges_overlap": bool(call.max() >= sequ.min()),
+            "call_launches_synchronisations_uploads": sorted(counters),
+            "pairs": pairs}
+
+
+def run_json(cmd, lib):
+    env = dict(os.environ)
+    if lib:
+        env["PE_ENGINE_LIB"] = lib
+    else:
+        env.pop("PE_ENGINE_LIB", None)
+    out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, check=True, timeout=900).stdout.decode()
+    return json.loads([line for line in out.splitlines() if line.startswith("{")][-1])
+
+
+def headline(args):
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(args.steps), "--warmup", "20"]
+    legs = []
+    for k in range(args.legs):
+        order = ("parent", "change") if k % 2 == 0 else ("change", "parent")
+        entry = {"leg": k + 1, "order": order[0] + " first"}
+        for who in order:
+            res = run_json(cmd, os.path.abspath(args.headline) if who == "parent" else None)
+            entry[who] = {key: res[key] for key in ("value", "unit", "ms_per_step") if key in res}
+        legs.append(entry)
+    par = np.asarray([e["parent"]["value"] for e in legs]) / 1e6
+    chg = np.asarray([e["change"]["value"] for e in legs]) / 1e6
+    d = (chg / par - 1.0) * 100.0
+    return {"tool": "tools/destructive_probe.py --headline", "what": " ".join(cmd[1:]),
+            "note": "parent: the parent commit's engine build; change: this tree's; one process per leg and build",
+            "summary": {"pairs": len(legs),
+                        "parent_M_per_s": {"min": float(par.min()), "median": float(np.median(par)), "max": float(par.max())},
+                        "change_M_per_s": {"min": float(chg.min()), "median": float(np.median(chg)), "max": float(chg.max())},
+                        "change_faster_in_pairs": int((d > 0).sum()),
+                        "median_paired_difference_percent": float(np.median(d)),
+                        "paired_differences_percent": [float(x) for x in d]},
+            "legs": legs}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=8)
+    ap.add_argument("--legs", type=int, default=6)
+    ap.add_argument("--steps", type=int, default=40000)
+    ap.add_argument("--small", action="store_true")
+    ap.add_argument("--headline", default=None)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    res = headline(args) if args.headline else call_vs_sequence(args)
+    text = json.dumps(res, indent=1)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
