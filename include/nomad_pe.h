@@ -484,7 +484,9 @@ int pe_place_destructive(pe_stack* s, uint32_t tg_index, const uint32_t* allocs,
 /* Measurement aid: what the last pe_place_destructive issued. out3[0] kernel
  * launches (the loop, and a copy launch when the SetNodes list was not on the
  * device yet), [1] stream synchronisations, [2] uploads (the stop list, and
- * that list). */
+ * that list). After pe_place_destructive_metrics with metrics on the counts
+ * include the checkpoint's device copies and the trace's upload, two launches,
+ * copy back and synchronisation; none of them depends on `n`. */
 int pe_place_destructive_stats(const pe_stack* s, uint64_t* out3);
 /* inplaceUpdate (util.go:692-806) for `n` snapshot allocs (alloc-table rows) against task group
  * `tg_index`, in list order. For each: AppendStoppedAlloc, SetNodes([its node]), Select(tg),
@@ -1260,6 +1262,39 @@ int pe_place_csi_metrics_stats(const pe_stack* s, double* us4, uint64_t* log_byt
  * count * (visit list length) above 2^24). */
 int pe_place_csi_full_metrics(pe_stack* s, uint32_t tg_index, uint32_t count, const uint32_t* alloc_idx,
                               pe_ranked_node* out, uint32_t* placed);
+/* pe_place_destructive with AllocMetric kept: what
+ * GenericScheduler.computePlacements stores on each new alloc of its
+ * destructive loop and, for the nil Select that ends it, in failedTGAllocs
+ * (generic_sched.go:552-645). Arguments, records, contract and later state are
+ * pe_place_destructive's.
+ * With pe_set_metrics off the call is pe_place_destructive, and
+ * pe_place_destructive_maps answers PE_ESTATE. (pe_place_destructive itself
+ * keeps refusing a handle with metrics on.)
+ * With it on, records, maps and every later observable state equal those of
+ * the per-call sequence with metrics on: pe_plan_stop(&allocs[i], 1),
+ * pe_select(tg, NULL), the maps read, then pe_commit, or
+ * pe_plan_pop_update(allocs[i]) and a break. Later state includes the metrics
+ * shadow of the memo, which the call advances as that sequence's Selects
+ * would, the eligibility log, the cursor and the plan.
+ * pe_place_destructive_maps gives record k's maps in pe_place_csi_maps'
+ * layout: counts[counts_off[k] .. counts_off[k + 1]) and scores[scores_off[k]
+ * .. scores_off[k + 1]) for k < n_rec = the records written. There is one map
+ * set per returned record; the nil Select's are what the scheduler keeps in
+ * failedTGAllocs, and that Select saw its own stop. The maps stay valid until
+ * the handle's next mutating call. pe_last_metrics* answers PE_ESTATE after
+ * the call, as after pe_place_csi_metrics.
+ * The dynamic node columns are copied on the device before the loop, and the
+ * maps then cost one host walk over the consumed windows and one batched trace
+ * against that copy, which is told every stop record k's Select saw: two
+ * stream synchronisations per call, whatever `n`.
+ * PE_EINVAL, PE_ESTATE and n == 0 as pe_place_destructive. PE_EUNSUPPORTED,
+ * checked before anything changes: pe_place_destructive's list without its
+ * pe_set_metrics row. PE_EINTERNAL: a bounds guard of the loop kernel tripped;
+ * pe_place_destructive_maps then answers PE_ESTATE. */
+int pe_place_destructive_metrics(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n,
+                                 pe_ranked_node* out, uint32_t* placed);
+int pe_place_destructive_maps(const pe_stack* s, const pe_metric_count** counts, const uint32_t** counts_off,
+                              const pe_metric_score** scores, const uint32_t** scores_off, uint32_t* n_rec);
 /* The reason text CSIVolumeChecker.Feasible records (feasible.go:19-26) for
  * `reason` (PE_CSI_*): stateless, needs no device. `volume` is the request's
  * source after the per_alloc suffix (reasons 1, 5, 6, 7), `plugin` the volume's

@@ -235,6 +235,12 @@ def bind_csi(lib):
         lib.pe_place_destructive.argtypes = [H, C.c_uint32, u32p, C.c_uint32, C.POINTER(pe_ranked_node), u32p]
         lib.pe_place_destructive_stats.restype = C.c_int
         lib.pe_place_destructive_stats.argtypes = [H, u64p]
+    if hasattr(lib, "pe_place_destructive_metrics"):   # (an A/B library from before its metrics form)
+        lib.pe_place_destructive_metrics.restype = C.c_int
+        lib.pe_place_destructive_metrics.argtypes = [H, C.c_uint32, u32p, C.c_uint32, C.POINTER(pe_ranked_node), u32p]
+        lib.pe_place_destructive_maps.restype = C.c_int
+        lib.pe_place_destructive_maps.argtypes = [H, C.POINTER(C.POINTER(pe_metric_count)), C.POINTER(u32p),
+                                                  C.POINTER(C.POINTER(pe_metric_score)), C.POINTER(u32p), u32p]
     if not hasattr(lib, "pe_place_csi"):   # present or absent behind one ABI version (an A/B library)
         return lib
     lib.pe_place_csi.restype = C.c_int
@@ -352,6 +358,7 @@ ENGINE_SYMBOLS = [
     "pe_place_csi_full", "pe_csi_full_fold", "pe_csi_full_block", "pe_place_csi_full_metrics",
     "pe_probe_math", "pe_probe_go_sort",
     "pe_place_destructive", "pe_place_destructive_stats",
+    "pe_place_destructive_metrics", "pe_place_destructive_maps",
 ]
 
 

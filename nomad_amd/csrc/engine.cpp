@@ -887,6 +887,8 @@ struct pe_stack {
         bool timed = false;             // PE_CSI_TIME=1: us[] holds the last call's split
         double us[4] = {0, 0, 0, 0};    // loop, host walk, trace and maps (host clock)
     } csi_m;
+    // pe_place_destructive_metrics: the call's maps (pe_place_destructive_maps), valid while `gen` is the handle's
+    CsiMaps ds_m;
 
     // The unchanged SystemScheduler caller (scheduler_system.go:289-302):
     // SetNodes([node]) then Select for every node. From the third single-node
@@ -6685,6 +6687,13 @@ struct TraceRecs {
     uint32_t n_entries = 0;
 };
 
+// One stop of a destructive loop that changes something (pe::TraceStops): the
+// stopped alloc's node row, the record whose Select saw it first, its CSR slot
+// and its kDs* flags.
+struct TraceStopEv {
+    uint32_t row, rec, slot, flags;
+};
+
 // The checkpoint of the dynamic columns (spec_copy) as a trace's state.
 static void trace_ckpt_state(pe_stack* s, pe::NodeSoA* soa, pe::TgTables* t) {
     soa->rec = s->ck_rec.as<pe::NodeRec>();
@@ -6699,10 +6708,15 @@ static void trace_ckpt_state(pe_stack* s, pe::NodeSoA* soa, pe::TgTables* t) {
 // record's ScoreMetaData from k_trace_top; then record k's maps from acc[k]
 // (the host walk's filters) plus its entries' outcomes, appended to the
 // pe_spec_view layout (mcounts / mscores with their per-record offsets).
+// `stops` (pe_place_destructive_metrics): the records are a destructive loop's,
+// record k's Select also saw these stops of records <= k (k_trace<true>); they
+// travel in the rows' upload. `stats` (or null): launches (copies included),
+// synchronisations and uploads are added to it.
 static int trace_records(pe_stack* s, TgPlan& g, pe::NodeSoA soa, pe::TgTables t, const TraceRecs& R, MetricAcc* acc,
                          std::vector<pe_metric_count>& mcounts, std::vector<uint32_t>& mcounts_off,
                          std::vector<pe_metric_score>& mscores, std::vector<uint32_t>& mscores_off,
-                         double* t_traced = nullptr, bool allow_list = true) {
+                         double* t_traced = nullptr, bool allow_list = true,
+                         const std::vector<TraceStopEv>* stops = nullptr, uint64_t* stats = nullptr) {
     const uint32_t n_rec = R.n_rec, n_entries = R.n_entries;
     const std::vector<uint32_t>&xrows = R.xrows, &rec_end = R.rec_end, &rsrc = R.rsrc, &list = R.list;
     auto row_of = [&](uint32_t k, uint32_t j) -> uint32_t {   // trace_row on the host
@@ -6755,8 +6769,38 @@ static int trace_records(pe_stack* s, TgPlan& g, pe::NodeSoA soa, pe::TgTables t
         const size_t at_pl = in.size();
         in.resize(at_pl + 2 * pl.size());
         if (!pl.empty()) std::memcpy(in.data() + at_pl, pl.data(), pl.size() * sizeof(uint64_t));
+        // the stop events sorted by (row, record), then their slots in that order
+        const size_t at_ev = in.size(), n_ev = stops ? stops->size() : 0;
+        if (n_ev) {
+            std::vector<std::pair<uint64_t, uint32_t>> ev(n_ev);
+            for (size_t e = 0; e < n_ev; e++) {
+                const TraceStopEv& x = (*stops)[e];
+                if (x.row >= s->nodes.size() || x.rec >= n_rec || x.flags > 7u ||
+                    ((x.flags & pe::kDsLive) && x.slot >= s->h_palloc.size()))
+                    return s->fail(PE_EINTERNAL, "trace_records: a stop event's row, record or slot out of range");
+                ev[e] = {(uint64_t)x.row << 32 | (uint64_t)x.rec << 3 | x.flags, x.slot};
+            }
+            std::sort(ev.begin(), ev.end());
+            in.resize(at_ev + 3 * n_ev);
+            for (size_t e = 0; e < n_ev; e++) {
+                std::memcpy(in.data() + at_ev + 2 * e, &ev[e].first, sizeof(uint64_t));
+                in[at_ev + 2 * n_ev + e] = ev[e].second;
+            }
+        }
         HIP_TRY(s, upload_s(s, s->d_trace_rows, in));
+        if (stats) {
+            stats[0]++;
+            stats[2]++;
+        }
         const uint32_t* d_in = s->d_trace_rows.as<uint32_t>();
+        pe::TraceStops ts{};
+        if (stops) {
+            ts.ev = reinterpret_cast<const uint64_t*>(d_in + at_ev);
+            ts.slot = d_in + at_ev + 2 * n_ev;
+            ts.palloc = s->d_palloc.as<pe::PreemptAlloc>();
+            ts.n_ev = (uint32_t)n_ev;
+            ts.n_slots = (uint32_t)s->h_palloc.size();
+        }
         pe::TraceSrc src{};
         src.rows = d_in;
         src.rec_end = d_in + at_end;
@@ -6794,7 +6838,7 @@ static int trace_records(pe_stack* s, TgPlan& g, pe::NodeSoA soa, pe::TgTables t
             stab = s->d_trace_tabs.as<double>();
         }
         HIP_TRY_STATE(s, pe_launch_trace_batch(&soa, &t, &a, &src, (uint32_t)n_rows, d_codes, s->log10, stab,
-                                               s->d_trace_scores.as<double>(), s->stream));
+                                               s->d_trace_scores.as<double>(), s->stream, stops ? &ts : nullptr));
         const uint32_t flags = (a.dev_tw != 0.0 ? 1u : 0u) | (a.anti_aff ? 2u : 0u) |
                                (!g.affinities.empty() ? 4u : 0u) |
                                (s->cfg.stack_kind == PE_STACK_GENERIC ? 8u : 0u);
@@ -6821,6 +6865,10 @@ static int trace_records(pe_stack* s, TgPlan& g, pe::NodeSoA soa, pe::TgTables t
             HIP_TRY(s, hipMemcpyAsync(s->h_trace_top.p, s->d_trace_top.p, codes_at + n_rows * sizeof(uint32_t),
                                       hipMemcpyDeviceToHost, s->stream));
             HIP_TRY(s, hipStreamSynchronize(s->stream));
+            if (stats) {   // k_trace, k_trace_top, the copy back; one synchronisation
+                stats[0] += 3;
+                stats[1]++;
+            }
         }
     } else {
         std::memset(s->h_trace_top.as<uint8_t>() + top_bytes, 0, codes_at - top_bytes);
@@ -11271,9 +11319,15 @@ uint32_t pe_csi_full_block(void) { return pe_csi_full_threads(); }
 // the resources, build_collisions' for the counts), the kernel applies it
 // before that update's Select, and the mirrors are replayed from the records,
 // so that a later build_job_counts reproduces the device columns.
+// `metrics` (pe_place_destructive_metrics, AllocMetric on): the dynamic columns
+// are checkpointed before the launch and every record's maps follow it
+// (destructive_maps).
+static int destructive_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec, const pe_ranked_node* recs,
+                            const std::vector<TraceStopEv>& evs, uint64_t* stats);
+
 static int place_destructive_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
-                                 uint32_t* placed) {
-    const std::string fn = "pe_place_destructive: ";
+                                 uint32_t* placed, bool metrics = false) {
+    const std::string fn = metrics ? "pe_place_destructive_metrics: " : "pe_place_destructive: ";
     if (s->cfg.stack_kind != PE_STACK_GENERIC) return s->fail(PE_ESTATE, fn + "not a generic stack");
     if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
     if (!s->have_job) return s->fail(PE_ESTATE, "pe_set_job not called");
@@ -11296,7 +11350,7 @@ static int place_destructive_one(pe_stack* s, uint32_t tgi, const uint32_t* allo
                                              "the property-set counts are rebuilt per commit)");
     if (s->limit >= 0x7FFFFFFFu)
         return s->fail(PE_EUNSUPPORTED, fn + "a limit latched to MaxInt32 by a sibling group's Select");
-    if (s->metrics_on) return s->fail(PE_EUNSUPPORTED, fn + "pe_set_metrics on");
+    if (s->metrics_on && !metrics) return s->fail(PE_EUNSUPPORTED, fn + "pe_set_metrics on");
     if (s->cfg.preempt)
         return s->fail(PE_EUNSUPPORTED, fn + "a preempting stack (the loop retries a nil Select with Preempt)");
     if (!s->kids.empty()) return s->fail(PE_EUNSUPPORTED, fn + "a handle over several devices");
@@ -11390,6 +11444,14 @@ static int place_destructive_one(pe_stack* s, uint32_t tgi, const uint32_t* allo
     A.full_out = s->h_place_out.dev<pe_ranked_node>();
     A.eval_status = s->h_place_status.dev<uint32_t>();
     if (!A.full_out || !A.eval_status) return s->fail(PE_EHIP, "mapped result buffers unavailable");
+    if (metrics) {
+        // the state the call's first Select sees before its own stop, for the trace: every column a stop
+        // or a commit of the loop writes and load_node / status_loaded read (device copies, counted as launches)
+        rc = spec_copy(s, g, true);
+        if (rc) return rc;
+        for (const DevMem* col : {&s->d_rec, &s->d_coll_job, &g.coll_tg, &s->d_dev_free})
+            if (col->p && !s->nodes.empty()) stats[0]++;
+    }
     HIP_TRY_STATE(s, pe_launch_destructive(&A, &D, s->stream));
     stats[0]++;
     HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -11426,8 +11488,70 @@ static int place_destructive_one(pe_stack* s, uint32_t tgi, const uint32_t* allo
         cur = out[i].new_offset;
     }
     if (placed) *placed = p;
+    if (metrics) {   // one map set per returned record; the nil Select saw its own stop too
+        std::vector<TraceStopEv> evs;
+        for (uint32_t i = 0; i < got; i++)
+            if (stops[pe::kDsWords * i + 2])
+                evs.push_back({stops[pe::kDsWords * i + 1], i, stops[pe::kDsWords * i], stops[pe::kDsWords * i + 2]});
+        rc = destructive_maps(s, g, start, got, out, evs, stats);
+        if (rc) return rc;
+    }
     // a listed alloc of another group of the job: that group's column follows from the mirrors
     if (other_group) return build_job_counts(s);
+    return PE_OK;
+}
+
+// The maps of pe_place_destructive_metrics' records, after the loop's
+// synchronisation: record k's window is walked on the host in record order
+// against the reference memo, which it advances for good (the records are
+// final), and every row that passes the wrapper goes through one batched trace
+// (trace_records, k_trace<true>) against the checkpoint taken before the loop,
+// with the stops record k's Select saw as events beside the rows.
+static int destructive_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec, const pe_ranked_node* recs,
+                            const std::vector<TraceStopEv>& evs, uint64_t* stats) {
+    const bool prof = s->tun.metrics_prof;
+    const double t0 = prof ? now_us() : 0.0;
+    pe_stack::CsiMaps& M = s->ds_m;
+    M.gen = 0;
+    static thread_local std::vector<MetricAcc> acc;
+    if (acc.size() < n_rec) acc.resize(n_rec);
+    for (uint32_t k = 0; k < n_rec; k++) acc[k].reset();
+    TraceRecs R;
+    R.rec_end.resize(n_rec);
+    R.rsrc.resize(n_rec);
+    R.xrows.reserve(16 * (size_t)n_rec);
+    std::vector<int32_t> rec_row(n_rec);
+    uint32_t off = start;
+    uint64_t walked = 0;
+    for (uint32_t k = 0; k < n_rec; k++) {
+        const size_t x0 = R.xrows.size();
+        metrics_walk(s, g, s->visit, off, recs[k].nodes_evaluated, acc[k], R.xrows);
+        if (R.xrows.size() >= (size_t)pe::kTraceRot)
+            return s->fail(PE_EINTERNAL, "pe_place_destructive_metrics: trace rows overflow");
+        R.rsrc[k] = (uint32_t)x0;
+        R.rec_end[k] = (uint32_t)R.xrows.size();
+        rec_row[k] = recs[k].row;
+        walked += recs[k].nodes_evaluated;
+        off = recs[k].new_offset;
+    }
+    R.n_rec = n_rec;
+    R.rec_row = rec_row.data();
+    R.n_entries = (uint32_t)R.xrows.size();
+    const double t1 = prof ? now_us() : 0.0;
+    double t2 = t1;
+    pe::NodeSoA soa = soa_of(s);   // the state the call's first Select saw before its stop: the checkpoint
+    pe::TgTables t = tables_of(g);
+    trace_ckpt_state(s, &soa, &t);
+    const int rc = trace_records(s, g, soa, t, R, acc.data(), M.counts, M.counts_off, M.scores, M.scores_off,
+                                 prof ? &t2 : nullptr, false, &evs, stats);
+    if (rc) return rc;
+    M.n_rec = n_rec;
+    M.gen = s->gen;
+    if (prof)
+        std::fprintf(stderr, "place_destructive_metrics: %u records, %llu walked, %u traced rows, %zu stop events: "
+                             "walk %.1f us, trace %.1f us, maps %.1f us (%zu counts, %zu scores)\n", n_rec,
+                     (unsigned long long)walked, R.n_entries, evs.size(), t1 - t0, t2 - t1, now_us() - t2,
+                     M.counts.size(), M.scores.size());
     return PE_OK;
 }
 
@@ -11438,6 +11562,30 @@ int pe_place_destructive(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint
     PE_FLUSH_RESET(s);
     s->pre_overflow.clear();
     return place_destructive_one(s, tgi, allocs, n, out, placed);
+}
+
+// pe_place_destructive with AllocMetric kept. Off: the call is pe_place_destructive.
+int pe_place_destructive_metrics(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                                 uint32_t* placed) {
+    if (!s || (n && (!allocs || !out))) return PE_EINVAL;
+    if (!s->metrics_on) return pe_place_destructive(s, tgi, allocs, n, out, placed);
+    if (placed) *placed = 0;
+    PE_FLUSH_RESET(s);
+    s->pre_overflow.clear();
+    return place_destructive_one(s, tgi, allocs, n, out, placed, true);
+}
+
+int pe_place_destructive_maps(const pe_stack* s, const pe_metric_count** counts, const uint32_t** counts_off,
+                              const pe_metric_score** scores, const uint32_t** scores_off, uint32_t* n_rec) {
+    if (!s || !counts || !counts_off || !scores || !scores_off || !n_rec) return PE_EINVAL;
+    const pe_stack::CsiMaps& M = s->ds_m;
+    if (!M.gen || M.gen != s->gen) return PE_ESTATE;
+    *counts = M.counts.data();
+    *counts_off = M.counts_off.data();
+    *scores = M.scores.data();
+    *scores_off = M.scores_off.data();
+    *n_rec = M.n_rec;
+    return PE_OK;
 }
 
 int pe_place_destructive_stats(const pe_stack* s, uint64_t* out3) {

@@ -432,6 +432,19 @@ struct DestructiveArgs {
     uint32_t* own_existing;        // [n] or null
 };
 
+// The stops of a destructive loop's records for the batched trace of their maps
+// (k_trace<true>, pe_place_destructive_metrics): the trace reads the checkpoint
+// of the loop's starting state, and record k's Select saw the stops of records
+// 0..k, its own included. One event per stop that changes something, sorted:
+// node row << 32 | record << 3 | its kDs* flags; slot[i] is event i's CSR slot
+// (read for kDsLive alone). The false form of the kernel ignores the struct.
+struct TraceStops {
+    const uint64_t* ev;            // [n_ev]
+    const uint32_t* slot;          // [n_ev]
+    const PreemptAlloc* palloc;    // [n_slots]
+    uint32_t n_ev, n_slots;
+};
+
 // Full-scan Select reduction record (one per workgroup, and per GPU shard).
 // With limit >= options the LimitIterator returns every option, the first
 // kMaxSkip non-positive ones (in visit order) moved to the end; MaxScore then

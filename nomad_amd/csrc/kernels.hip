@@ -264,7 +264,9 @@ __device__ __forceinline__ bool distinct_ok(const TgTables& t, const double* tab
     return true;
 }
 
-template <bool kCores = true>
+// kDistinctHosts false (k_trace<true>): the caller ran the distinct_hosts test
+// itself, on a job count the column does not hold.
+template <bool kCores = true, bool kDistinctHosts = true>
 __device__ __forceinline__ int status_loaded(const NodeSoA& s, const TgTables& t, const uint8_t* class_ok,
                                              const Ask& a, uint32_t dk, uint32_t row, const NodeIn& in,
                                              ScoreIn* si, const double* ptab = nullptr) {
@@ -279,7 +281,7 @@ __device__ __forceinline__ int status_loaded(const NodeSoA& s, const TgTables& t
     }
     const uint32_t coll = in.coll_tg + dk;
     // DistinctHostsIterator (feasible.go:569-595)
-    if (ok && (a.distinct_job | a.distinct_tg)) {
+    if (kDistinctHosts && ok && (a.distinct_job | a.distinct_tg)) {
         if (a.distinct_job && s.coll_job[row] + dk > 0) ok = false;
         if (a.distinct_tg && coll > 0) ok = false;
     }
@@ -553,31 +555,117 @@ __device__ __forceinline__ uint32_t trace_fit(const NodeSoA& s, const Ask& a, ui
     return kTrOption;
 }
 
+// The node image record k's Select of a destructive loop saw (k_trace<true>,
+// TraceStops), from the image of the loop's starting state: the stops of
+// records <= k on the row leave it (ds_stop's arithmetic) and the dk placements
+// of records < k join it (ds_fold_row's), so the caller goes on with dk = 0.
+// All of it is integer sums, so the order is free, except for a device ask:
+// which group a placement's offer takes depends on the free counts it meets,
+// so the row's stops and placements are replayed in record order, the stop of
+// record j before the placement of record j. *job_sub: the stops that leave the
+// job's collision count. False: an event's slot is out of range.
+__device__ __forceinline__ bool trace_stops(const TgTables& t, const Ask& a, const TraceSrc& src, const TraceStops& S,
+                                            uint32_t row, uint32_t k, uint32_t dk, NodeIn& in, uint32_t* job_sub) {
+    const uint64_t key = (uint64_t)row << 32;
+    uint32_t lo = 0, hi = S.n_ev;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (S.ev[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    const bool devs = a.n_dev > 0 && t.dev_free;
+    uint32_t pi = 0, taken = 0;   // the row's placements: the next one, and how many the free counts hold
+    if (devs && dk) {
+        hi = src.n_pl;
+        while (pi < hi) {
+            const uint32_t mid = (pi + hi) >> 1;
+            if (src.pl[mid] < key) pi = mid + 1;
+            else hi = mid;
+        }
+    }
+    NodeRec& r = in.r;
+    uint32_t free = in.dev_free, sub = 0;
+    for (; lo < S.n_ev && (uint32_t)(S.ev[lo] >> 32) == row; lo++) {
+        const uint32_t w = (uint32_t)S.ev[lo], j = w >> 3;
+        if (j > k) break;
+        if (devs)   // the placements of records before this stop's
+            for (; taken < dk && pi < src.n_pl && (uint32_t)src.pl[pi] < j; pi++, taken++) {
+                double m;
+                dev_assign(a, t.dev_cls[r.cls], free, &m);
+            }
+        if (w & kDsLive) {
+            const uint32_t slot = S.slot[lo];
+            if (slot >= S.n_slots) return false;
+            const PreemptAlloc x = S.palloc[slot];
+            r.used_cpu -= x.cpu;
+            r.used_mem -= x.mem;
+            r.used_disk -= x.disk;
+            r.used_mbits -= x.mbits;
+            r.used_dyn -= x.dyn;
+            if (devs)
+                for (int q = 0; q < 4 && q < (int)x.n_dev; q++)
+                    free += ((x.dev_c >> (8 * q)) & 255u) << (8 * ((x.dev_g >> (8 * q)) & 255u));
+        }
+        if (w & kDsJob) sub++;
+        if (w & kDsTg) in.coll_tg--;
+    }
+    if (devs) free = dev_after(a, t.dev_cls[r.cls], free, dk - taken);
+    in.dev_free = free;
+    r.used_cpu += (int64_t)dk * a.cpu;
+    r.used_mem += (int64_t)dk * a.mem;
+    r.used_disk += (int64_t)dk * a.disk;
+    r.used_mbits += (int32_t)dk * a.commit_mbits;
+    r.used_dyn += (int32_t)dk * a.commit_dyn;
+    in.coll_tg += dk;
+    *job_sub = sub;
+    return true;
+}
+
 // dk (TraceSrc): placements of this task group on the row that the state
 // lacks (a speculative run's earlier Selects, traced against the run's
 // starting state; no distinct_property sets then), applied as status_loaded
 // does. In a batched trace record k's spread boosts are spread_tab + k *
 // pset_tab_total (k_spread_tables: the record's own use counts).
+// kStops (a batched trace of a destructive loop's records; no reserved-cores
+// ask): the loaded image is first brought to what record k's Select saw
+// (trace_stops), and every check after it runs on that image with dk = 0.
+template <bool kStops>
 __global__ void k_trace(NodeSoA s, TgTables t, Ask a, TraceSrc src, uint32_t n, uint32_t* out,
-                        const uint32_t* penalty_bits, double log10, const double* spread_tab, double* sc) {
+                        const uint32_t* penalty_bits, double log10, const double* spread_tab, double* sc,
+                        TraceStops stops) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    uint32_t row, dk;
+    uint32_t row, dk, rec = 0;
     if (src.rec_end) {
         const uint32_t k = trace_rec(src, i);
         row = trace_row(src, k, i - (k ? src.rec_end[k - 1] : 0u));
         dk = trace_dk(src, row, k);
         if (spread_tab) spread_tab += (size_t)k * t.pset_tab_total;
+        rec = k;
     } else {
         row = src.rows[i];
         dk = src.dks ? (uint32_t)src.dks[i] : 0u;
+    }
+    if (kStops && row >= s.n) {   // (the host walk's rows are the visit list's: a guard)
+        out[i] = kTrMismatch;
+        return;
     }
     NodeIn in;
     load_node(s, t, row, in);
     NodeRec& r = in.r;
     const uint32_t c = r.cls;
     uint32_t code = kTrOption;
-    if ((a.distinct_job && s.coll_job[row] + dk > 0) || (a.distinct_tg && in.coll_tg + dk > 0)) {
+    uint32_t dj = dk;   // what the job's collision column lacks
+    if (kStops) {
+        uint32_t sub;
+        if (!trace_stops(t, a, src, stops, row, rec, dk, in, &sub)) {
+            out[i] = kTrMismatch;
+            return;
+        }
+        dj = dk - sub;
+        dk = 0;
+    }
+    if ((a.distinct_job && s.coll_job[row] + dj > 0) || (a.distinct_tg && in.coll_tg + dk > 0)) {
         code = kTrDistinctHosts;                                   // feasible.go:569-595
     } else {
         for (int p = t.n_spread; p < t.n_psets && code == kTrOption; p++) {
@@ -603,7 +691,7 @@ __global__ void k_trace(NodeSoA s, TgTables t, Ask a, TraceSrc src, uint32_t n, 
             r.used_dyn -= (int32_t)dk * a.commit_dyn;
             r.used_mbits -= (int32_t)dk * a.commit_mbits;
         }
-        if (status_loaded(s, t, t.class_ok, a, dk, row, in, &si) != kOption) {
+        if (status_loaded<true, !kStops>(s, t, t.class_ok, a, dk, row, in, &si) != kOption) {
             out[i] = kTrMismatch;
             return;
         }
@@ -7252,18 +7340,23 @@ hipError_t pe_launch_trace(const pe::NodeSoA* s, const pe::TgTables* t, const pe
     pe::TraceSrc src{};
     src.rows = rows;
     src.dks = dks;
-    hipLaunchKernelGGL(pe::k_trace, dim3((n + 255) / 256), dim3(256), 0, st, *s, *t, *a, src, n, out,
-                       penalty_bits, log10, spread_tab, scores);
+    hipLaunchKernelGGL(pe::k_trace<false>, dim3((n + 255) / 256), dim3(256), 0, st, *s, *t, *a, src, n, out,
+                       penalty_bits, log10, spread_tab, scores, pe::TraceStops{});
     return hipGetLastError();
 }
 
 // Every record of a speculative run in one launch (TraceSrc batched form).
 hipError_t pe_launch_trace_batch(const pe::NodeSoA* s, const pe::TgTables* t, const pe::Ask* a,
                                  const pe::TraceSrc* src, uint32_t n, uint32_t* out, double log10,
-                                 const double* spread_tab, double* scores, hipStream_t st) {
+                                 const double* spread_tab, double* scores, hipStream_t st,
+                                 const pe::TraceStops* stops) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(pe::k_trace, dim3((n + 255) / 256), dim3(256), 0, st, *s, *t, *a, *src, n, out,
-                       nullptr, log10, spread_tab, scores);
+    if (stops)
+        hipLaunchKernelGGL(pe::k_trace<true>, dim3((n + 255) / 256), dim3(256), 0, st, *s, *t, *a, *src, n, out,
+                           nullptr, log10, spread_tab, scores, *stops);
+    else
+        hipLaunchKernelGGL(pe::k_trace<false>, dim3((n + 255) / 256), dim3(256), 0, st, *s, *t, *a, *src, n, out,
+                           nullptr, log10, spread_tab, scores, pe::TraceStops{});
     return hipGetLastError();
 }
 

@@ -116,6 +116,7 @@ hipError_t pe_launch_trace(const pe::NodeSoA* s, const pe::TgTables* t, const pe
                            const double* spread_tab, double* scores, hipStream_t st, const uint16_t* dks = nullptr);
 hipError_t pe_launch_trace_batch(const pe::NodeSoA* s, const pe::TgTables* t, const pe::Ask* a,
                                  const pe::TraceSrc* src, uint32_t n, uint32_t* out, double log10,
-                                 const double* spread_tab, double* scores, hipStream_t st);
+                                 const double* spread_tab, double* scores, hipStream_t st,
+                                 const pe::TraceStops* stops = nullptr);   // stops: k_trace<true>, a destructive loop's records
 hipError_t pe_launch_spread_tables(const pe::TgTables* t, uint32_t n_rec, uint32_t* delta, double* tab,
                                    hipStream_t st);

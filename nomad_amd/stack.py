@@ -1214,6 +1214,26 @@ def place_destructive_by_select(stack, tg, allocs: Sequence[int]):
     return records
 
 
+def place_destructive_metrics_by_select(stack, tg, allocs: Sequence[int]):
+    """place_destructive_by_select on a stack with EnableMetrics on (the
+    engine's or the oracle's), with LastMetrics() read after each SelectRaw,
+    before PopUpdate / Commit: what computePlacements stores on the new alloc,
+    or in failedTGAllocs for the nil Select (generic_sched.go:552-645). Returns
+    (records, maps) in PlaceDestructiveMetrics' shape."""
+    records, maps = [], []
+    for ai in allocs:
+        ai = int(ai)
+        stack.StopAllocs([ai])
+        r = stack.SelectRaw(tg)
+        records.append(r)
+        maps.append(stack.LastMetrics())
+        if r.row < 0:
+            stack.PopUpdate(ai)
+            break
+        stack.Commit(tg, r.row)
+    return records, maps
+
+
 def _is_dimension(reason: str) -> bool:
     """Whether an AllocMetric reason is one ExhaustedNode records
     (rank.go:255-497: a network or devices message, or AllocsFit's dimension)."""
@@ -1312,8 +1332,46 @@ class GenericStack(_Stack):
             return place_destructive_by_select(self, tg, allocs)
         return [RankedNode.from_c(out[i], self.nodes) for i in range(min(n, placed.value + 1))]
 
+    def PlaceDestructiveMetrics(self, tg, allocs: Sequence[int], fallback: bool = True):
+        """pe_place_destructive_metrics: PlaceDestructive with AllocMetric kept.
+        Returns (records, maps): PlaceDestructive's records and, with
+        EnableMetrics on, one dict per record in LastMetrics' shape, the nil
+        Select's included (metrics off: PlaceDestructive's records and None).
+        A job the batched path refuses (Unsupported) is answered by
+        place_destructive_metrics_by_select when `fallback`, else the refusal
+        propagates."""
+        allocs = [int(a) for a in allocs]
+        n = len(allocs)
+        try:
+            if not hasattr(self._lib, "pe_place_destructive_metrics"):
+                raise Unsupported(abi.PE_EUNSUPPORTED, "no batched destructive update with metrics behind this ABI")
+            a = np.ascontiguousarray(np.asarray(allocs or [0], dtype=np.uint32))
+            out = (abi.pe_ranked_node * max(1, n))()
+            placed = C.c_uint32(0)
+            self._check(self._lib.pe_place_destructive_metrics(self._h, self._tg_index(tg), a.ctypes.data_as(abi.u32p),
+                                                               n, out, C.byref(placed)))
+        except Unsupported:
+            if not fallback:
+                raise
+            if not getattr(self, "_metrics_on", False):
+                return place_destructive_by_select(self, tg, allocs), None
+            return place_destructive_metrics_by_select(self, tg, allocs)
+        records = [RankedNode.from_c(out[i], self.nodes) for i in range(min(n, placed.value + 1))]
+        if not getattr(self, "_metrics_on", False):
+            return records, None
+        return records, (self.PlaceDestructiveMaps() if n else [])
+
+    def PlaceDestructiveMaps(self) -> List[Dict]:
+        """pe_place_destructive_maps: the maps of the last
+        PlaceDestructiveMetrics' records, one dict per record in LastMetrics' shape."""
+        c, sc = C.POINTER(abi.pe_metric_count)(), C.POINTER(abi.pe_metric_score)()
+        co, so, n = abi.u32p(), abi.u32p(), C.c_uint32(0)
+        self._check(self._lib.pe_place_destructive_maps(self._h, C.byref(c), C.byref(co), C.byref(sc), C.byref(so),
+                                                        C.byref(n)))
+        return [decode_metrics(self, c, co[k], co[k + 1], sc, so[k], so[k + 1]) for k in range(n.value)]
+
     def place_destructive_stats(self):
-        """(launches, synchronisations, uploads) of the last PlaceDestructive call."""
+        """(launches, synchronisations, uploads) of the last PlaceDestructive or PlaceDestructiveMetrics call."""
         out = (C.c_uint64 * 3)()
         self._check(self._lib.pe_place_destructive_stats(self._h, out))
         return tuple(int(x) for x in out)

@@ -20,6 +20,15 @@ against the per-call sequence it replaces.
 
           python tools/destructive_probe.py [--pairs 8] [--small] [--out profiles/place_destructive/probe.json]
 
+  --metrics  The same comparison with pe_set_metrics on in both handles
+      (DESIGN.md §47): the call is pe_place_destructive_metrics followed by
+      pe_place_destructive_maps; the sequence reads pe_last_metrics_bin after
+      each pe_select, as a caller that keeps AllocMetric does. With
+      PE_METRICS_PROF set in the environment the call's host split (walk,
+      trace, maps) is read back from the engine's stderr lines.
+
+          PE_METRICS_PROF=1 python tools/destructive_probe.py --metrics [--out profiles/place_destructive_metrics/probe.json]
+
   --headline PARENT_LIB  `bench.py --gpus 1 --steps N --warmup 20` in fresh
       processes, the parent commit's library (PE_ENGINE_LIB) and this tree's
       alternating, the order swapping every leg.
@@ -31,7 +40,9 @@ import ctypes as C
 import json
 import os
 import subprocess
+import re
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -83,6 +94,8 @@ def call_vs_sequence(args):
         st = GenericStack()
         st.SetState(nodes, allocs)
         st.SetJob(job)
+        if args.metrics:
+            st.EnableMetrics(True)
         return st
     a, b = handle(), handle()
     lib = a._lib
@@ -103,24 +116,46 @@ def call_vs_sequence(args):
     def prepare(st):
         st.ResetPlan()
         st.SetJob(job)
+        if args.metrics:
+            st.EnableMetrics(True)
         st.SetNodes(perm)
         assert settle(st) == 0
+
+    place = lib.pe_place_destructive_metrics if args.metrics else lib.pe_place_destructive
+    mc, ms = C.POINTER(abi.pe_metric_count)(), C.POINTER(abi.pe_metric_score)()
+    mco, mso, mn = abi.u32p(), abi.u32p(), C.c_uint32(0)
+    lib.pe_last_metrics_bin.restype = C.c_int
+    lib.pe_last_metrics_bin.argtypes = [C.c_void_p, C.POINTER(C.POINTER(abi.pe_metric_count)), abi.u32p,
+                                        C.POINTER(C.POINTER(abi.pe_metric_score)), abi.u32p]
+    nc, ns = C.c_uint32(0), C.c_uint32(0)
+    map_sizes = {}
 
     def run_call():
         prepare(a)
         t0 = time.perf_counter()
-        rc = lib.pe_place_destructive(a._h, 0, arr.ctypes.data_as(abi.u32p), length, recs, C.byref(placed))
+        rc = place(a._h, 0, arr.ctypes.data_as(abi.u32p), length, recs, C.byref(placed))
+        if args.metrics:
+            rc = rc or lib.pe_place_destructive_maps(a._h, C.byref(mc), C.byref(mco), C.byref(ms), C.byref(mso),
+                                                     C.byref(mn))
         rc = rc or settle(a)
         t1 = time.perf_counter()
         assert rc == 0, rc
+        if args.metrics:
+            map_sizes["call"] = (int(mn.value), int(mco[mn.value]), int(mso[mn.value]))
         return (t1 - t0) * 1e6
 
     def run_sequence():
         prepare(b)
         done = 0
+        sizes = [0, 0]
+        map_sizes["sequence"] = sizes
         t0 = time.perf_counter()
         for k in range(length):
             rc = lib.pe_plan_stop(b._h, one[k], 1) or lib.pe_select(b._h, 0, None, C.byref(seq[k]))
+            if args.metrics:
+                rc = rc or lib.pe_last_metrics_bin(b._h, C.byref(mc), C.byref(nc), C.byref(ms), C.byref(ns))
+                sizes[0] += nc.value
+                sizes[1] += ns.value
             assert rc == 0, rc
             done = k + 1
             if seq[k].row < 0:
@@ -134,6 +169,14 @@ def call_vs_sequence(args):
         return (t1 - t0) * 1e6, done
 
     pairs, same, counters = [], True, set()
+    # PE_METRICS_PROF: the engine writes the call's host split to stderr; keep the process's stderr in a file
+    prof = args.metrics and bool(os.environ.get("PE_METRICS_PROF"))
+    saved_err = None
+    if prof:
+        sys.stderr.flush()
+        err_file = tempfile.TemporaryFile(mode="w+b")
+        saved_err = os.dup(2)
+        os.dup2(err_file.fileno(), 2)
     for r in range(args.pairs + 3):
         order = ("call", "sequence") if r % 2 == 0 else ("sequence", "call")
         t = {}
@@ -148,10 +191,33 @@ def call_vs_sequence(args):
         if r >= 3:
             pairs.append({"pair": r - 2, "order": order[0] + " first", "call_us": t["call"], "sequence_us": t["sequence"],
                           "difference_us": t["sequence"] - t["call"]})
+    split = None
+    if prof:
+        C.CDLL(None).fflush(None)
+        os.dup2(saved_err, 2)
+        os.close(saved_err)
+        err_file.seek(0)
+        lines = [ln for ln in err_file.read().decode(errors="replace").splitlines()
+                 if ln.startswith("place_destructive_metrics:")]
+        rows = [[float(x) for x in re.search(r"walk ([\d.]+) us, trace ([\d.]+) us, maps ([\d.]+) us", ln).groups()]
+                for ln in lines][3:]                           # (the warm-ups' lines dropped)
+        if rows:
+            arr3 = np.asarray(rows)
+            split = {"calls": len(rows), "line": lines[-1],
+                     "median_us": dict(zip(("walk", "trace", "maps"), (float(x) for x in np.median(arr3, axis=0)))),
+                     "min_us": dict(zip(("walk", "trace", "maps"), (float(x) for x in arr3.min(axis=0)))),
+                     "max_us": dict(zip(("walk", "trace", "maps"), (float(x) for x in arr3.max(axis=0))))}
     diff = np.asarray([p["difference_us"] for p in pairs])
     call = np.asarray([p["call_us"] for p in pairs])
     sequ = np.asarray([p["sequence_us"] for p in pairs])
-    return {"tool": "tools/destructive_probe.py", "nodes": n, "updates": length, "placed": int(placed.value),
+    extra = {}
+    if args.metrics:
+        same = same and map_sizes["call"][1:] == tuple(map_sizes["sequence"])
+        extra = {"metrics": True, "call_records_counts_scores": list(map_sizes["call"]),
+                 "sequence_counts_scores": list(map_sizes["sequence"]),
+                 "call_host_split_PE_METRICS_PROF": split}
+    return {"tool": "tools/destructive_probe.py" + (" --metrics" if args.metrics else ""), "nodes": n,
+            "updates": length, "placed": int(placed.value), **extra,
             "records_equal": bool(same),
             "call_us": {"min": float(call.min()), "median": float(np.median(call)), "max": float(call.max())},
             "sequence_us": {"min": float(sequ.min()), "median": float(np.median(sequ)), "max": float(sequ.max())},
@@ -202,6 +268,7 @@ def main():
     ap.add_argument("--legs", type=int, default=6)
     ap.add_argument("--steps", type=int, default=40000)
     ap.add_argument("--small", action="store_true")
+    ap.add_argument("--metrics", action="store_true")
     ap.add_argument("--headline", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
