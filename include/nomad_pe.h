@@ -1295,6 +1295,40 @@ int pe_place_destructive_metrics(pe_stack* s, uint32_t tg_index, const uint32_t*
                                  pe_ranked_node* out, uint32_t* placed);
 int pe_place_destructive_maps(const pe_stack* s, const pe_metric_count** counts, const uint32_t** counts_off,
                               const pe_metric_score** scores, const uint32_t** scores_off, uint32_t* n_rec);
+/* pe_place_destructive for a group that runs full passes: node affinities or
+ * spreads (target or even, at job or group level, attributes that some nodes
+ * lack included), or a plain group under a limit that a sibling group's Select
+ * latched to MaxInt32. Arguments and records are pe_place_destructive's. On a
+ * group that runs no full passes under an unlatched limit the call is
+ * pe_place_destructive, so a caller that keeps no AllocMetric uses this one
+ * entry for every run of destructive updates.
+ *
+ * One staged upload (the stop list with each stop's list position, and per
+ * value of every spread set what build_psets and cleared_counts read at the
+ * call's start), one launch of k_destructive_full and one synchronisation
+ * whatever `n`. Records and every later observable state equal those of the
+ * per-call sequence pe_plan_stop(&allocs[i], 1), pe_select(tg, NULL), then
+ * pe_commit, or pe_plan_pop_update(allocs[i]) and a break. Every Select is a
+ * full pass: nodes_evaluated is the list length, nodes_filtered and
+ * nodes_exhausted are those of the state that Select saw (its own stop
+ * included), new_offset is the cursor unchanged, and pe_get_cursor afterwards
+ * reads limit MaxInt32. The spread counts each Select sees are those
+ * propertySet.GetCombinedUseMap gives with the stops so far cleared
+ * (propertyset.go:159-209), kept on the device in closed form.
+ *
+ * PE_EINVAL, PE_ESTATE, n == 0 and PE_EINTERNAL as pe_place_destructive.
+ * PE_EUNSUPPORTED, checked before anything changes (cursor, limit, memo, plan
+ * and NodeUpdate untouched; the per-call sequence answers instead), each with
+ * this entry's name in the message: every row of pe_place_destructive's list
+ * except the full-pass one (n: more than 4096 updates); distinct_property at
+ * job or group level; spread sets or affinity scores beyond the folded
+ * per-node word (more than 2 sets, a set of more than 255 values, more than
+ * 256 distinct affinity scores); a node list that names a row twice; more
+ * options and listed stop positions than one workgroup's LDS holds (8192; the
+ * kernel finds this while it builds its entries, before the first stop).
+ * pe_place_destructive_stats covers this call too. */
+int pe_place_destructive_full(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                              uint32_t* placed);
 /* The reason text CSIVolumeChecker.Feasible records (feasible.go:19-26) for
  * `reason` (PE_CSI_*): stateless, needs no device. `volume` is the request's
  * source after the per_alloc suffix (reasons 1, 5, 6, 7), `plugin` the volume's

@@ -241,6 +241,9 @@ def bind_csi(lib):
         lib.pe_place_destructive_maps.restype = C.c_int
         lib.pe_place_destructive_maps.argtypes = [H, C.POINTER(C.POINTER(pe_metric_count)), C.POINTER(u32p),
                                                   C.POINTER(C.POINTER(pe_metric_score)), C.POINTER(u32p), u32p]
+    if hasattr(lib, "pe_place_destructive_full"):   # (an A/B library from before its full-pass form)
+        lib.pe_place_destructive_full.restype = C.c_int
+        lib.pe_place_destructive_full.argtypes = [H, C.c_uint32, u32p, C.c_uint32, C.POINTER(pe_ranked_node), u32p]
     if not hasattr(lib, "pe_place_csi"):   # present or absent behind one ABI version (an A/B library)
         return lib
     lib.pe_place_csi.restype = C.c_int
@@ -359,6 +362,7 @@ ENGINE_SYMBOLS = [
     "pe_probe_math", "pe_probe_go_sort",
     "pe_place_destructive", "pe_place_destructive_stats",
     "pe_place_destructive_metrics", "pe_place_destructive_maps",
+    "pe_place_destructive_full",
 ]
 
 

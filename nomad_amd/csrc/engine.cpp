@@ -8962,6 +8962,39 @@ static int inplace_metrics_finish(pe_stack* s, TgPlan& g, uint32_t n, const uint
     return PE_OK;
 }
 
+// What build_psets and cleared_counts read at a call's start for spread set p,
+// per value in the pset_cnt_off layout (`cols` values per column), into
+// base[0, 3 * cols): ep0 (the group's existing and plan allocs), craw0
+// (NodeUpdate's allocs of this job, namespace and group, terminal ones
+// included) and prop0 (a plan alloc of the group has the value). Shared by
+// pe_inplace_update_spread and pe_place_destructive_full.
+static void spread_start_columns(pe_stack* s, TgPlan& g, const pe::TgTables& t, int p, uint32_t cols, uint32_t* base) {
+    const PsetDev& ps = *g.psets[p];
+    const auto node_val = [&](uint32_t row) {
+        return ps.per_node ? ps.h_val_node[row] : ps.h_val_class[s->nodes[row].cls];
+    };
+    const auto mine = [&](const HostAlloc& a) { return a.job == s->job_id && a.ns == s->job_ns && a.tg == g.name; };
+    uint32_t* ep0 = base + t.pset_cnt_off[p];
+    uint32_t* craw0 = ep0 + cols;
+    uint32_t* prop0 = craw0 + cols;
+    for (uint32_t ai : s->own_allocs())
+        if (const HostAlloc& a = s->allocs[ai]; a.ns == s->job_ns && a.tg == g.name) {
+            const uint32_t v = node_val(a.row);
+            if (v != pe::kMissing) ep0[v]++;
+        }
+    for (auto& e : plan_of(s))
+        if (e.first == g.name) {
+            const uint32_t v = node_val(e.second);
+            if (v != pe::kMissing) { ep0[v]++; prop0[v] = 1; }
+        }
+    for (auto& kv : s->node_update)
+        for (uint32_t ai : kv.second)
+            if (const HostAlloc& a = s->allocs[ai]; mine(a)) {
+                const uint32_t v = node_val(a.row);
+                if (v != pe::kMissing) craw0[v]++;
+            }
+}
+
 // pe_inplace_update_spread's second stage: what build_psets and
 // cleared_counts read at the call's start, per value of every spread set in
 // the pset_cnt_off layout (ep0: the group's existing and plan allocs; craw0:
@@ -8989,25 +9022,7 @@ static int inplace_spread_inputs(pe_stack* s, TgPlan& g, const uint32_t* allocs,
         const auto node_val = [&](uint32_t row) {
             return ps.per_node ? ps.h_val_node[row] : ps.h_val_class[s->nodes[row].cls];
         };
-        uint32_t* ep0 = base + SP->tg.pset_cnt_off[p];
-        uint32_t* craw0 = ep0 + cols;
-        uint32_t* prop0 = craw0 + cols;
-        for (uint32_t ai : s->own_allocs())
-            if (const HostAlloc& a = s->allocs[ai]; a.ns == s->job_ns && a.tg == g.name) {
-                const uint32_t v = node_val(a.row);
-                if (v != pe::kMissing) ep0[v]++;
-            }
-        for (auto& e : plan_of(s))
-            if (e.first == g.name) {
-                const uint32_t v = node_val(e.second);
-                if (v != pe::kMissing) { ep0[v]++; prop0[v] = 1; }
-            }
-        for (auto& kv : s->node_update)
-            for (uint32_t ai : kv.second)
-                if (const HostAlloc& a = s->allocs[ai]; mine(a)) {
-                    const uint32_t v = node_val(a.row);
-                    if (v != pe::kMissing) craw0[v]++;
-                }
+        spread_start_columns(s, g, SP->tg, p, cols, base);
         for (uint32_t i = 0; i < n; i++) val[(size_t)p * n + i] = node_val(s->allocs[allocs[i]].row);
     }
     HIP_TRY(s, upload_s(s, s->d_inplace_sp_in, in));
@@ -11592,6 +11607,201 @@ int pe_place_destructive_stats(const pe_stack* s, uint64_t* out3) {
     if (!s || !out3) return PE_EINVAL;
     for (int i = 0; i < 3; i++) out3[i] = s->destructive_stats[i];
     return PE_OK;
+}
+
+// ---- pe_place_destructive_full: the loop for a group that runs full passes ------
+//  place_destructive_one's order: the refusals, spec_flush,
+// prepare_tg, the fold and the folded per-node word (build_aux), then one
+// staged upload [stop list | named positions | ep0 craw0 prop0], one
+// k_destructive_full launch with its records in mapped page-locked memory, one
+// synchronisation, and the mirrors replayed from the records. Every Select is
+// a full pass: the cursor stays, the limit latches to MaxInt32 and every
+// returned record logs the whole list's eligibility span.
+constexpr uint32_t kDestructiveFullMaxN = 4096;   // updates of one call (one workgroup runs them one after the other)
+
+static int place_destructive_full_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n,
+                                      pe_ranked_node* out, uint32_t* placed) {
+    const std::string fn = "pe_place_destructive_full: ";
+    if (s->cfg.stack_kind != PE_STACK_GENERIC) return s->fail(PE_ESTATE, fn + "not a generic stack");
+    if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
+    if (!s->have_job) return s->fail(PE_ESTATE, "pe_set_job not called");
+    if (tgi >= s->tgs.size()) return s->fail(PE_EINVAL, "task group index out of range");
+    for (uint32_t i = 0; i < n; i++)
+        if (allocs[i] >= s->allocs.size()) return s->fail(PE_EINVAL, "alloc index out of range");
+    {
+        std::vector<uint32_t> sorted(allocs, allocs + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return s->fail(PE_EINVAL, fn + "an alloc listed twice");
+    }
+    if (s->visit.empty()) return s->fail(PE_ESTATE, fn + "no node list (pe_set_nodes)");
+    if (!n) return PE_OK;
+    // refusals, all before anything changes
+    TgPlan& g = *s->tgs[tgi];
+    if (!g.unsupported.empty()) return s->fail(PE_EUNSUPPORTED, g.unsupported);
+    if (s->metrics_on) return s->fail(PE_EUNSUPPORTED, fn + "pe_set_metrics on");
+    if (s->cfg.preempt)
+        return s->fail(PE_EUNSUPPORTED, fn + "a preempting stack (the loop retries a nil Select with Preempt)");
+    if (!s->kids.empty()) return s->fail(PE_EUNSUPPORTED, fn + "a handle over several devices");
+    if (g.ask.cores > 0) return s->fail(PE_EUNSUPPORTED, fn + "a reserved-cores ask");
+    for (uint32_t i = 0; i < n; i++) {
+        const HostAlloc& a = s->allocs[allocs[i]];
+        if (a.cores[0] | a.cores[1] | a.cores[2] | a.cores[3] || a.cores_beyond)
+            return s->fail(PE_EUNSUPPORTED, fn + "a listed alloc holds reserved cores");
+    }
+    if (has_static(g)) return s->fail(PE_EUNSUPPORTED, fn + "static port asks in the group (a stop frees ports the gates were built with)");
+    if (tg_md(s, g)) return s->fail(PE_EUNSUPPORTED, fn + "a task network on a snapshot with multi-device nodes");
+    if (g.has_csi && !g.csi_reqs.empty()) return s->fail(PE_EUNSUPPORTED, fn + "a group with CSI requests");
+    for (size_t k = 0; k < s->tgs.size(); k++)
+        if (k != tgi && s->tgs[k]->name == g.name)
+            return s->fail(PE_EUNSUPPORTED, fn + "two task groups of one name (a stop moves the sibling's collision counts too)");
+    bool distinct_property = !g.distinct_props.empty();
+    for (auto& c : s->job_constraints) distinct_property = distinct_property || c.op == "distinct_property";
+    if (distinct_property)
+        return s->fail(PE_EUNSUPPORTED, fn + "distinct_property (it filters, and its counts are rebuilt per commit)");
+    if (n > kDestructiveFullMaxN) return s->fail(PE_EUNSUPPORTED, fn + "n exceeds the updates of one launch");
+    if (!s->visit_unique) return s->fail(PE_EUNSUPPORTED, fn + "a node list that names a row twice");
+    int rc = spec_flush(s);
+    if (rc) return rc;
+    HIP_TRY(s, hipSetDevice(s->device));
+    rc = prepare_tg(s, tgi, s->visit, s->offset);
+    if (rc) return rc;
+    if (g.n_spread != (int)g.psets.size()) return s->fail(PE_EUNSUPPORTED, fn + "distinct_property");
+    if (g.md_on) return s->fail(PE_EUNSUPPORTED, fn + "a task network on a snapshot with multi-device nodes");
+    rc = flush_fold(s);   // the class table reaches the device with the group's fold
+    if (rc) return rc;
+    uint64_t stats[3] = {0, 0, 0};
+    const uint32_t m = (uint32_t)s->visit.size();
+    const uint32_t start = s->offset % m;
+    pe::SweepArgs A;
+    {
+        if (!g.aux_valid) stats[0]++;          // build_aux's fold launch
+        if (!s->rank_of_valid) { stats[0]++; stats[2]++; }
+        uint32_t blocks = 0;
+        rc = sweep_setup(s, g, nullptr, 0, (uint32_t)s->nodes.size(), &A, &blocks);
+        if (rc) return rc;
+    }
+    A.offset = start;
+    const int np = A.tg.n_psets;
+    if (!A.node_aux || A.tg.pset_cnt_total > (uint32_t)(pe::kAuxPsets * pe::kAuxValues))
+        return s->fail(PE_EUNSUPPORTED, fn + "spread sets or affinity scores beyond the folded per-node word (more than 2 "
+                                             "sets, a set of more than 255 values, or more than 256 distinct affinity scores)");
+    if (s->stop_count.size() != s->allocs.size()) s->stop_count.assign(s->allocs.size(), 0);
+    // one upload: [stop list: kDfWords x n | named positions | ep0 craw0 prop0: cols each]
+    const uint32_t cols = np ? A.tg.pset_cnt_total : 0u;
+    const size_t named_off = (size_t)pe::kDfWords * n, sp_off = named_off + (m + 31) / 32;
+    std::vector<uint32_t> in(sp_off + 3 * (size_t)cols, 0);
+    std::vector<uint32_t> pos_of(s->nodes.size(), PE_NONE);
+    for (uint32_t i = 0; i < m; i++) pos_of[s->visit[i]] = i;
+    bool other_group = false, any_live = false;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t ai = allocs[i];
+        const HostAlloc& a = s->allocs[ai];
+        const uint32_t slot = s->alloc_slot[ai];
+        const bool fresh = s->stop_count[ai] == 0;   // an alloc already in NodeUpdate adds its entry alone
+        uint32_t f = 0;
+        if (fresh && !a.terminal && slot != PE_NONE && s->h_preempted[slot] == 0) f |= pe::kDsLive;
+        if (fresh && !a.terminal && a.job == s->job_id) {
+            f |= pe::kDsJob;
+            if (a.tg == g.name) f |= pe::kDsTg;
+            else other_group = true;
+        }
+        if (a.job == s->job_id && a.ns == s->job_ns && a.tg == g.name) f |= pe::kDsOwn;   // cleared_counts' test
+        any_live = any_live || (f & pe::kDsLive);
+        const uint32_t pos = pos_of[a.row];
+        in[pe::kDfWords * i] = slot;
+        in[pe::kDfWords * i + 1] = a.row;
+        in[pe::kDfWords * i + 2] = f;
+        in[pe::kDfWords * i + 3] = pos;
+        if (pos != PE_NONE) in[named_off + (pos >> 5)] |= 1u << (pos & 31u);
+    }
+    for (int p = 0; p < np; p++) spread_start_columns(s, g, A.tg, p, cols, in.data() + sp_off);
+    const uint32_t* staged = reinterpret_cast<const uint32_t*>(stage_only(s, in));
+    stats[2]++;
+    if (!staged) {   // the staging ring does not take it: a copy of its own
+        HIP_TRY(s, upload_s(s, s->d_stop_slots, in));
+        staged = s->d_stop_slots.as<uint32_t>();
+        stats[0]++;
+    }
+    pe::DestructiveFullArgs F;
+    std::memset(&F, 0, sizeof(F));
+    F.d.stops = staged;
+    F.d.palloc = s->d_palloc.as<pe::PreemptAlloc>();
+    F.d.n_slots = (uint32_t)s->h_palloc.size();
+    F.d.preempted = s->d_preempted.as<uint8_t>();
+    F.d.dev_free = s->dev_packable ? s->d_dev_free.as<uint32_t>() : nullptr;
+    F.d.own_existing = s->d_own_existing.as<uint32_t>();
+    F.named = staged + named_off;
+    F.sp = np ? staged + sp_off : nullptr;
+    if (!s->d_visit_is_visit) {   // the first call after SetNodes carries the list
+        stats[0]++;
+        stats[2]++;
+    }
+    HIP_TRY(s, upload_visit(s, s->visit));
+    s->h_full_args = A;
+    HIP_TRY(s, s->d_full_args.ensure(sizeof(pe::SweepArgs)));
+    HIP_TRY(s, hipMemcpyAsync(s->d_full_args.p, &s->h_full_args, sizeof(pe::SweepArgs), hipMemcpyHostToDevice, s->stream));
+    stats[2]++;
+    HIP_TRY(s, s->h_place_out.ensure(sizeof(pe_ranked_node) * (size_t)n));
+    HIP_TRY(s, s->h_place_status.ensure(8 * sizeof(uint32_t)));
+    pe_ranked_node* d_out = s->h_place_out.dev<pe_ranked_node>();
+    uint32_t* d_state = s->h_place_status.dev<uint32_t>();
+    if (!d_out || !d_state) return s->fail(PE_EHIP, "mapped result buffers unavailable");
+    std::memset(s->h_place_out.as<pe_ranked_node>(), 0, sizeof(pe_ranked_node) * (size_t)n);
+    std::memset(s->h_place_status.as<uint32_t>(), 0, 8 * sizeof(uint32_t));
+    HIP_TRY_STATE(s, pe_launch_destructive_full(&A, s->d_full_args.as<pe::SweepArgs>(), np, &F, s->d_visit.as<uint32_t>(),
+                                                m, n, d_out, d_state, s->stream));
+    stats[0]++;
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    stats[1]++;
+    uint32_t st8[8];
+    std::memcpy(st8, const_cast<const uint32_t*>(s->h_place_status.as<uint32_t>()), sizeof(st8));
+    if (st8[5])   // found during the build, before the first stop: nothing changed
+        return s->fail(PE_EUNSUPPORTED, fn + "more options and named positions than one workgroup's LDS holds (" +
+                                             std::to_string(pe_destructive_full_cap()) + " entries)");
+    // ---- nothing is refused from here on ----
+    s->gen++;
+    s->metrics_valid = false;
+    for (int i = 0; i < 3; i++) s->destructive_stats[i] = stats[i];
+    const uint32_t p = std::min(st8[1], n), got = std::min(n, p + (st8[0] ? 1u : 0u));
+    // the host mirrors, in list order, as the per-call sequence leaves them (as place_destructive_one)
+    const pe_ranked_node* recs = s->h_place_out.as<pe_ranked_node>();
+    for (uint32_t i = 0; i < p; i++)
+        if (recs[i].row < 0 || (size_t)recs[i].row >= s->nodes.size())
+            return s->fail(PE_EINTERNAL, "k_destructive_full: a placement's row out of range");
+    if (!st8[2]) std::memcpy(out, recs, sizeof(pe_ranked_node) * got);
+    auto& plan = plan_of(s);
+    for (uint32_t i = 0; i < p; i++) {
+        const uint32_t ai = allocs[i], row = s->allocs[ai].row;
+        s->node_update[row].push_back(ai);
+        s->stop_count[ai]++;
+        if (in[pe::kDfWords * i + 2] & pe::kDsLive) s->h_preempted[s->alloc_slot[ai]] = 2;
+        plan.emplace_back(g.name, (uint32_t)recs[i].row);
+    }
+    s->offer_row = -1;
+    s->limit = 0x7FFFFFFF;   // as a Select of such a group leaves it (stack.go:165-167)
+    if (any_live) invalidate_static(s);   // the stopped allocs' ports
+    for (auto& t : s->tgs) t->psets_built = false;   // the job's stopped allocs feed the property sets
+    if (p) invalidate_job_distinct(s, tgi);
+    if (st8[2])
+        return s->fail(PE_EINTERNAL, "k_destructive_full: a bounds guard tripped (a stop's slot, row or position out of range)");
+    for (uint32_t i = 0; i < got; i++) elig_log_span(s, tgi, start, m);   // every Select pulled the whole list
+    if (placed) *placed = p;
+    // a listed alloc of another group of the job: that group's column follows from the mirrors
+    if (other_group) return build_job_counts(s);
+    return PE_OK;
+}
+
+int pe_place_destructive_full(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
+                              uint32_t* placed) {
+    if (!s || (n && (!allocs || !out))) return PE_EINVAL;
+    // a windowed group under an unlatched limit: the call is pe_place_destructive
+    if (s->have_job && tgi < s->tgs.size() && !tg_full_scan(s, *s->tgs[tgi]) && s->limit < 0x7FFFFFFFu)
+        return pe_place_destructive(s, tgi, allocs, n, out, placed);
+    if (placed) *placed = 0;
+    PE_FLUSH_RESET(s);
+    s->pre_overflow.clear();
+    return place_destructive_full_one(s, tgi, allocs, n, out, placed);
 }
 
 // The maps of pe_place_csi_metrics' records, after the loop's synchronisation:

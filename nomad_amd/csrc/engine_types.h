@@ -432,6 +432,23 @@ struct DestructiveArgs {
     uint32_t* own_existing;        // [n] or null
 };
 
+// k_destructive_full (pe_place_destructive_full): the same loop for a group
+// that runs full passes. Four words per update: CSR slot, node row, flags, and
+// the row's position in the node list (PE_NONE: not listed). kDsOwn: the alloc
+// passes cleared_counts' job, namespace and group test, whatever its state (its
+// NodeUpdate entry counts). `named` has one bit per list position that some
+// update names; `sp` holds what build_psets and cleared_counts read at the
+// call's start, per value of every spread set in the pset_cnt_off layout: ep0
+// (the group's existing and plan allocs), craw0 (NodeUpdate's allocs that pass
+// the test) and prop0 (a plan alloc of the group has the value).
+constexpr uint32_t kDsOwn = 8u;
+constexpr uint32_t kDfWords = 4;
+struct DestructiveFullArgs {
+    DestructiveArgs d;             // d.stops: [count][kDfWords]
+    const uint32_t* named;         // [ceil(n_visit / 32)]
+    const uint32_t* sp;            // [3][pset_cnt_total] or null (no spread set)
+};
+
 // The stops of a destructive loop's records for the batched trace of their maps
 // (k_trace<true>, pe_place_destructive_metrics): the trace reads the checkpoint
 // of the loop's starting state, and record k's Select saw the stops of records

@@ -5031,7 +5031,8 @@ __device__ __forceinline__ void ds_fold_row(const BatchArgs& A, const Overlay& o
 }
 
 // AppendStoppedAlloc (sign +1) / PopUpdate (sign -1, the same steps in reverse order) of one update (one lane).
-__device__ __forceinline__ void ds_stop(const BatchArgs& A, const DestructiveArgs& D, uint32_t slot, uint32_t row,
+template <class Args>   // BatchArgs (k_destructive) or SweepArgs (k_destructive_full): the node columns and the group's
+__device__ __forceinline__ void ds_stop(const Args& A, const DestructiveArgs& D, uint32_t slot, uint32_t row,
                                         uint32_t flags, int sign) {
     const auto resources = [&]() {
         if (!(flags & kDsLive)) return;
@@ -5260,6 +5261,437 @@ __global__ void __launch_bounds__(64) k_destructive(BatchArgs A, DestructiveArgs
     }
     ds_publish();   // the last stop (or its undo) before every lane's write-back
     if (A.writeback) writeback_overlay<64, false, false>(A, ov, H, nullptr);
+}
+
+// ---- pe_place_destructive_full: the same loop for a group that runs full passes --
+// k_fullpass_lds's shape (one workgroup, one build pass over the list, one LDS
+// entry per option, the approximate and the exact pass per Select, the exact
+// skip rule when no option is positive, the winner evaluated at dk = 0 and with
+// the placement added, the commit straight to the SoA) with k_destructive's
+// stop before every Select. What the stops add:
+// - A stop can turn an exhausted node, or one that distinct_hosts filtered, into
+//   an option: the build gives an entry to every option and to every list
+//   position the stop list names (one bit per position from the host), whatever
+//   its status. After the stop the thread that holds the row's entry evaluates
+//   the row again from HBM at dk = 0 and moves the block's filtered and
+//   exhausted counters with the status. The launch's placements are in HBM
+//   already, so there is nothing to fold.
+// - The spread counts under stops (DESIGN.md §38's closed form): per set and
+//   value the group's existing and plan allocs with this launch's winners (ep),
+//   NodeUpdate's allocs that pass cleared_counts' test with this launch's stops
+//   (craw), and whether a plan alloc of the group has the value (prop). The
+//   count a Select sees is ep less the cleared count, not below zero, where one
+//   cleared alloc is forgiven when prop is set and more than one is cleared
+//   (propertyset.go:199-208). One thread advances them between Selects; a
+//   target set refreshes the one boost whose count moved, an even set rebuilds
+//   its table.
+// - A nil Select: the same lane takes the stop back, spread columns first, and
+//   the loop ends.
+// Every loop is bounded without the data: updates by count, entries by kDfCap.
+// A slot, row or position of the stop list out of range raises state[2] and
+// ends the call before anything is indexed with it. More entries than kDfCap:
+// state[5] = 1 before the first stop is applied.
+constexpr int kDfPer = 8;                               // entries per thread
+constexpr uint32_t kDfCap = kFullThreads * kDfPer;      // LDS entries (16 B each)
+
+// GetCombinedUseMap of one value: existing + proposed - cleared, not below 0
+__device__ __forceinline__ uint32_t df_count(uint32_t ep, uint32_t craw, uint32_t prop) {
+    const uint32_t cleared = craw - ((prop && craw > 1u) ? 1u : 0u);
+    return ep >= cleared ? ep - cleared : 0u;
+}
+
+// Workgroup-wide ordering point for HBM stores of one thread that others load next.
+__device__ __forceinline__ void df_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int NP>   // spread properties scored, at most kAuxPsets
+__global__ void __launch_bounds__(kFullThreads) k_destructive_full(const SweepArgs* __restrict__ Ap,
+                                                                   DestructiveFullArgs F, const uint32_t* visit,
+                                                                   uint32_t n, uint32_t count, pe_ranked_node* out,
+                                                                   uint32_t* state) {
+    const SweepArgs& A = *Ap;
+    extern __shared__ double ent_sum[];                                   // [kDfCap] score_head sums
+    uint32_t* ent_meta = reinterpret_cast<uint32_t*>(ent_sum + kDfCap);    // status | k << 2 | spread values
+    uint32_t* ent_pos = ent_meta + kDfCap;                                 // visit position
+    __shared__ double tab[kAuxPsets * (kAuxValues + 1)];
+    __shared__ double desired[kAuxPsets * kAuxValues];
+    __shared__ uint32_t counts[kAuxPsets * kAuxValues];     // what each Select's table is built from
+    __shared__ uint32_t sp_ep[kAuxPsets * kAuxValues];      // EP0 + ks
+    __shared__ uint32_t sp_craw[kAuxPsets * kAuxValues];    // Craw0 + kc (+ the staged stop)
+    __shared__ uint32_t sp_prop[kAuxPsets * kAuxValues];    // prop0 || ks > 0
+    __shared__ double aff_lds[kAuxValues];
+    __shared__ double red_s[kFullWaves];
+    __shared__ uint32_t red_r[kFullWaves];
+    __shared__ uint32_t red_f[kFullWaves], red_e[kFullWaves];
+    __shared__ SweepRec red[kFullWaves];
+    __shared__ uint32_t scratch[4];
+    __shared__ uint32_t sh_nf, sh_ne, sh_stop, sh_win, sh_m;
+    __shared__ uint32_t sh_meta;   // the winner's new entry meta (sh_win stays the skip rule's rank: waves read it late)
+    __shared__ double parts1[PE_MAX_SCORES];   // lane 1's parts (unused)
+    __shared__ double rcp_k[8];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const TgTables& t = A.tg;
+    constexpr int np = NP;
+    const uint32_t off = A.offset;
+    bool any_even = false;
+    for (int p = 0; p < np; p++) any_even = any_even || t.pset_even[p];
+    for (int i = tid; i < kAuxValues; i += kFullThreads) aff_lds[i] = A.aff_vals[i];
+    if (tid < 8) rcp_k[tid] = tid ? 1.0 / (double)tid : 0.0;
+    if (tid == 0) sh_m = 0;
+    for (int p = 0; p < np; p++)
+        for (int v = tid; v < t.pset_nvals[p]; v += kFullThreads) {
+            const uint32_t i = t.pset_cnt_off[p] + (uint32_t)v;
+            sp_ep[i] = F.sp[i];
+            sp_craw[i] = F.sp[t.pset_cnt_total + i];
+            sp_prop[i] = F.sp[2u * t.pset_cnt_total + i];
+            counts[i] = df_count(sp_ep[i], sp_craw[i], sp_prop[i]);
+            desired[i] = t.pset_even[p] ? 0.0 : t.pset_desired[p][v];
+        }
+    __syncthreads();
+    if (np) build_spread_table<kFullThreads>(t, counts, tab, scratch);
+    auto spread_of = [&](uint32_t meta) __attribute__((always_inline)) -> double {   // lookup_scores' total
+        double sp = 0.0;
+#pragma unroll
+        for (int p = 0; p < np; p++) {
+            const uint32_t v = (meta >> (8 + 8 * p)) & 255u;
+            sp += (v == kAuxMissing) ? -1.0 : tab[t.pset_tab_off[p] + v];
+        }
+        return sp;
+    };
+    auto load = [&](uint32_t row, NodeIn& in) __attribute__((always_inline)) -> uint32_t {   // the sweep's AUX fetch
+        in.r = A.soa.rec[row];
+        in.coll_tg = t.coll_tg[row];
+        in.dev_free = t.dev_free ? t.dev_free[row] : 0u;
+        const uint32_t aux = A.node_aux[row];
+        in.feas = aux >> 31;
+        return aux;
+    };
+    // status and score_head of a loaded node with dk placements added; with a
+    // `parts` pointer the parts are written there
+    auto head = [&](uint32_t row, const NodeIn& in, uint32_t aux, uint32_t dk, double* parts, double* sum,
+                    uint32_t* kk) __attribute__((always_inline)) -> int {
+        ScoreIn si;
+        const int st = status_loaded(A.soa, t, t.class_ok, A.ask, dk, row, in, &si);
+        *kk = 0;
+        *sum = 0.0;
+        if (st == kOption) {
+            si.penalty = A.penalty_bits ? (A.penalty_bits[row >> 5] >> (row & 31)) & 1u : 0u;
+            si.aff = aff_lds[aux & 255u];
+            si.spread = 0.0;
+            *sum = parts ? score_head<true>(A.ask, A.log10, si, parts, *kk)
+                         : score_head<false>(A.ask, A.log10, si, nullptr, *kk);
+        }
+        return st;
+    };
+    // the final score of an entry (score_option's tail)
+    auto final_sum = [&](uint32_t e, uint32_t* kk_out) __attribute__((always_inline)) -> double {
+        const uint32_t meta = ent_meta[e];
+        double sum = ent_sum[e];
+        const double sp = spread_of(meta);
+        uint32_t kk = (meta >> 2) & 7u;
+        if (sp != 0.0) { sum += sp; kk++; }
+        *kk_out = kk;
+        return sum;
+    };
+    // one value's count after its columns moved, and a target set's boost of it
+    // (build_spread_table's arithmetic; an even set rebuilds its table)
+    auto refresh = [&](int p, uint32_t v) __attribute__((always_inline)) {
+        const uint32_t i = t.pset_cnt_off[p] + v;
+        const uint32_t c = df_count(sp_ep[i], sp_craw[i], sp_prop[i]);
+        counts[i] = c;
+        if (!t.pset_even[p]) {
+            const double d = desired[i];
+            tab[t.pset_tab_off[p] + v] = d != d ? -1.0 : ((d - (double)(c + 1u)) / d) * t.pset_weight_frac[p];
+        }
+    };
+    uint32_t nf = 0, ne = 0;
+    for (uint32_t pos = tid; pos < n; pos += kFullThreads) {
+        const uint32_t row = visit[pos];
+        NodeIn in;
+        const uint32_t aux = load(row, in);
+        double s;
+        uint32_t kk;
+        const int st = head(row, in, aux, 0u, nullptr, &s, &kk);
+        nf += st == kFiltered;
+        ne += st == kExhausted;
+        const bool named = (F.named[pos >> 5] >> (pos & 31u)) & 1u;   // a stop of the list can bring it back
+        if (st == kOption || named) {
+            const uint32_t e = atomicAdd(&sh_m, 1u);
+            if (e < kDfCap) {
+                ent_sum[e] = s;
+                ent_meta[e] = (uint32_t)st | (kk << 2) | (aux & 0x00FFFF00u);
+                ent_pos[e] = pos;
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        nf += (uint32_t)__shfl_xor((int)nf, o);
+        ne += (uint32_t)__shfl_xor((int)ne, o);
+    }
+    if (lane == 0) { red_f[wid] = nf; red_e[wid] = ne; }
+    __syncthreads();
+    const uint32_t m = sh_m;
+    if (m > kDfCap) {   // uniform: no stop applied yet, the caller's per-call sequence answers
+        if (tid == 0) state[5] = 1;
+        return;
+    }
+    if (tid == 0) {
+        uint32_t a = 0, b = 0;
+        for (int w = 0; w < kFullWaves; w++) { a += red_f[w]; b += red_e[w]; }
+        sh_nf = a;
+        sh_ne = b;
+        sh_stop = 0;
+    }
+    __syncthreads();
+    auto rank_of_pos = [&](uint32_t pos) __attribute__((always_inline)) -> uint32_t {
+        return pos >= off ? pos - off : pos + n - off;
+    };
+    uint32_t placed = 0, guard = 0, nil = 0;
+    // the next update's stop words are loaded one Select ahead (the list is in mapped host memory)
+    uint32_t nx[kDfWords] = {0, 0, 0, 0};
+    if (count)
+        for (uint32_t w = 0; w < kDfWords; w++) nx[w] = F.d.stops[w];
+    for (uint32_t it = 0; it < count; it++) {
+        // ---- AppendStoppedAlloc(allocs[it]) ----
+        const uint32_t s_slot = nx[0], s_row = nx[1], s_flags = nx[2], s_pos = nx[3];
+        if (it + 1 < count)
+            for (uint32_t w = 0; w < kDfWords; w++) nx[w] = F.d.stops[kDfWords * (it + 1) + w];
+        uint32_t s_aux = 0;
+        if (s_flags) {
+            if (s_row >= A.soa.n || ((s_flags & kDsLive) && s_slot >= F.d.n_slots) || (s_pos != PE_NONE && s_pos >= n)) {
+                guard = 1u;   // uniform
+                break;
+            }
+            s_aux = A.node_aux[s_row];
+            if (tid == 0) {
+                ds_stop(A, F.d, s_slot, s_row, s_flags, +1);
+                if (s_flags & kDsOwn) {
+#pragma unroll
+                    for (int p = 0; p < np; p++) {
+                        const uint32_t v = (s_aux >> (8 + 8 * p)) & 255u;
+                        if (v == kAuxMissing || v >= (uint32_t)t.pset_nvals[p]) continue;
+                        sp_craw[t.pset_cnt_off[p] + v]++;
+                        refresh(p, v);
+                    }
+                }
+            }
+            df_sync();
+            if (s_pos != PE_NONE && (s_flags & (kDsLive | kDsJob | kDsTg))) {   // the row's entry from HBM, dk = 0
+#pragma unroll
+                for (int j = 0; j < kDfPer; j++) {
+                    const uint32_t e = (uint32_t)tid + (uint32_t)j * kFullThreads;
+                    if (e < m && ent_pos[e] == s_pos) {
+                        const uint32_t row = visit[s_pos];
+                        NodeIn in;
+                        const uint32_t aux = load(row, in);
+                        double s;
+                        uint32_t kk;
+                        const int st = head(row, in, aux, 0u, nullptr, &s, &kk);
+                        const int was = (int)(ent_meta[e] & 3u);
+                        ent_sum[e] = s;
+                        ent_meta[e] = (uint32_t)st | (kk << 2) | (aux & 0x00FFFF00u);
+                        sh_nf += (uint32_t)(st == kFiltered) - (uint32_t)(was == kFiltered);   // one entry per position
+                        sh_ne += (uint32_t)(st == kExhausted) - (uint32_t)(was == kExhausted);
+                    }
+                }
+            }
+            if (any_even && (s_flags & kDsOwn)) build_spread_table<kFullThreads>(t, counts, tab, scratch);
+            __syncthreads();
+        }
+
+        // ---- Select: k_fullpass_lds's passes ----
+        double ap[kDfPer];
+        double amax = -__builtin_inff();
+#pragma unroll
+        for (int j = 0; j < kDfPer; j++) {
+            const uint32_t e = (uint32_t)tid + (uint32_t)j * kFullThreads;
+            ap[j] = -__builtin_inff();
+            if (e < m) {
+                uint32_t kk;
+                const double sum = final_sum(e, &kk);
+                if ((ent_meta[e] & 3u) == (uint32_t)kOption) ap[j] = sum * rcp_k[kk];
+            }
+            amax = ap[j] > amax ? ap[j] : amax;
+        }
+        amax = __ockl_wfred_max_f64(amax);
+        const double cut = amax - (__builtin_fabs(amax) * 0x1p-48 + 0x1p-1000);
+        double best = -__builtin_inff();
+        uint32_t best_rank = 0xFFFFFFFFu;
+#pragma unroll
+        for (int j = 0; j < kDfPer; j++) {
+            const bool near = ap[j] >= cut && ap[j] != -__builtin_inff();   // options only
+            if (__ballot(near)) {
+                if (near) {
+                    const uint32_t e = (uint32_t)tid + (uint32_t)j * kFullThreads;
+                    uint32_t kk;
+                    const double sc = final_sum(e, &kk) / (double)kk;
+                    const uint32_t rk = rank_of_pos(ent_pos[e]);
+                    if (sc > best || (sc == best && rk < best_rank)) { best = sc; best_rank = rk; }
+                }
+            }
+        }
+        {   // the wave's (max, earliest rank) over its few candidate lanes
+            uint64_t cand = __ballot(best_rank != 0xFFFFFFFFu);
+            double wb = -__builtin_inff();
+            uint32_t wr = 0xFFFFFFFFu;
+            for (int q = 0; q < 64 && cand; q++) {
+                const int l = __builtin_ctzll(cand);
+                cand &= cand - 1;
+                const double b = readlane_f64(best, l);
+                const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)best_rank, l);
+                if (b > wb || (b == wb && r < wr)) { wb = b; wr = r; }
+            }
+            best = wb;
+            best_rank = wr;
+        }
+        if (lane == 0) { red_s[wid] = best; red_r[wid] = best_rank; }
+        const uint32_t my_rank = best_rank;   // wave-uniform
+        uint32_t c_row = 0;
+        if (lane < 2 && my_rank != 0xFFFFFFFFu) {
+            uint32_t pos = off + my_rank;
+            if (pos >= n) pos -= n;
+            c_row = visit[pos];
+        }
+        __syncthreads();
+        // every wave resolves the block's winner itself: the maximum score,
+        // then the earliest rank among the waves holding it
+        best = lane < kFullWaves ? red_s[lane] : -__builtin_inff();
+        best_rank = lane < kFullWaves ? red_r[lane] : 0xFFFFFFFFu;
+        best = __ockl_wfred_max_f64(best);
+        uint32_t win = __ockl_wfred_min_u32(lane < kFullWaves && red_s[lane] == best ? best_rank : 0xFFFFFFFFu);
+        if (win != 0xFFFFFFFFu && !(best > 0.0)) {   // every option non-positive: the skip rule decides
+            SweepRec r;
+            rec_init(r);
+            for (uint32_t e = tid; e < m; e += kFullThreads) {
+                if ((ent_meta[e] & 3u) != (uint32_t)kOption) continue;
+                uint32_t kk;
+                const double sum = final_sum(e, &kk);
+                rec_add(r, rank_of_pos(ent_pos[e]), sum / (double)kk);
+            }
+            rec_block_reduce<kFullThreads>(r, red);
+            if (tid == 0) sh_win = rec_winner(r);
+            __syncthreads();
+            win = sh_win;
+        }
+        pe_ranked_node* o = out + it;
+        // the wave whose candidate won evaluates it; when the skip rule picked
+        // a rank no wave held, wave 0 loads it
+        bool mine = win != 0xFFFFFFFFu && my_rank == win;
+        if (win != 0xFFFFFFFFu && wid == 0 &&
+            __ballot(lane < kFullWaves && red_r[lane] == win) == 0) {   // wave-uniform
+            mine = true;
+            if (lane < 2) {
+                uint32_t pos = off + win;
+                if (pos >= n) pos -= n;
+                c_row = visit[pos];
+            }
+        }
+        if (wid == 0 && win == 0xFFFFFFFFu) {
+            if (lane == 0) {   // the nil Select: its record, then PopUpdate(allocs[it]) in reverse order
+                o->row = -1;
+                o->nodes_evaluated = n;            // a full pass pulls every node
+                o->nodes_filtered = sh_nf;
+                o->nodes_exhausted = sh_ne;
+                o->new_offset = off;
+                if (s_flags) {
+                    if (s_flags & kDsOwn) {
+#pragma unroll
+                        for (int p = np - 1; p >= 0; p--) {
+                            const uint32_t v = (s_aux >> (8 + 8 * p)) & 255u;
+                            if (v == kAuxMissing || v >= (uint32_t)t.pset_nvals[p]) continue;
+                            sp_craw[t.pset_cnt_off[p] + v]--;
+                        }
+                    }
+                    ds_stop(A, F.d, s_slot, s_row, s_flags, -1);
+                }
+                sh_stop = 1;
+            }
+        } else if (mine && lane < 2) {
+            const uint32_t row = c_row;
+            NodeIn in;
+            const uint32_t aux = load(row, in);
+            double s;
+            uint32_t kk;
+            const int st = head(row, in, aux, (uint32_t)lane, lane == 0 ? o->scores : parts1, &s, &kk);
+            const int st1 = __shfl(st, 1);
+            const uint32_t meta0 = (aux & 0x00FFFF00u);   // spread values: the entry's
+            if (lane == 1) {
+                sh_meta = (uint32_t)st | (kk << 2) | meta0;
+                parts1[0] = s;
+            } else {           // the placement's record, then the commit
+                const double sp = spread_of(meta0);
+                if (sp != 0.0) {   // SpreadIterator (spread.go:110-174)
+                    s += sp;
+                    o->scores[kk] = sp;
+                    kk++;
+                }
+                o->row = (int32_t)row;
+                o->final_score = s / (double)kk;   // ScoreNormalizationIterator (rank.go:762-767)
+                o->n_scores = kk;
+                o->nodes_evaluated = n;            // a full pass pulls every node
+                o->nodes_filtered = sh_nf;
+                o->nodes_exhausted = sh_ne;
+                o->new_offset = off;               // and leaves the cursor where it is
+                record_offers(A.soa, A.ask, t, row, 0u, o);
+                uint32_t offers = 0xFFFFFFFFu;
+                if (o->n_device_offers) {
+                    offers = 0;
+                    for (uint32_t q = 0; q < o->n_device_offers && q < 4; q++)
+                        offers |= (o->device_offer_group[q] & 255u) << (8 * q);
+                }
+                if (A.ask.n_dev == 0 && A.ask.cores == 0) {   // commit_row from the loaded values: stores only
+                    NodeRec& r = A.soa.rec[row];
+                    r.used_cpu = in.r.used_cpu + A.ask.cpu;
+                    r.used_mem = in.r.used_mem + A.ask.mem;
+                    r.used_disk = in.r.used_disk + A.ask.disk;
+                    r.used_mbits = in.r.used_mbits + A.ask.commit_mbits;
+                    r.used_dyn = in.r.used_dyn + A.ask.commit_dyn;
+                    A.soa.coll_job[row] += 1;
+                    t.coll_tg[row] = in.coll_tg + 1;
+                } else {
+                    commit_row(A.soa, t, A.ask, row, offers);
+                }
+#pragma unroll
+                for (int p = 0; p < np; p++) {   // the winner's value: one more proposed alloc of the group
+                    const uint32_t v = (meta0 >> (8 + 8 * p)) & 255u;
+                    if (v == kAuxMissing || v >= (uint32_t)t.pset_nvals[p]) continue;
+                    sp_ep[t.pset_cnt_off[p] + v]++;
+                    sp_prop[t.pset_cnt_off[p] + v] = 1u;
+                    refresh(p, v);
+                }
+                sh_nf += st1 == kFiltered;
+                sh_ne += st1 == kExhausted;
+            }
+        }
+        df_sync();   // the commit (or the undo) before the next stop's or winner's loads
+        if (sh_stop) {
+            nil = 1u;
+            break;
+        }
+        placed++;
+        {   // the winner's entry with this placement added
+            uint32_t pos = off + win;
+            if (pos >= n) pos -= n;
+#pragma unroll
+            for (int j = 0; j < kDfPer; j++) {
+                const uint32_t e = (uint32_t)tid + (uint32_t)j * kFullThreads;
+                if (e < m && ent_pos[e] == pos) {
+                    ent_sum[e] = parts1[0];
+                    ent_meta[e] = sh_meta;
+                }
+            }
+        }
+        if (any_even) build_spread_table<kFullThreads>(t, counts, tab, scratch);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        state[0] = nil;
+        state[1] = placed;
+        state[2] = guard;
+    }
 }
 
 // inplaceUpdate's loop (util.go:743-760) over a list of snapshot allocs: per
@@ -7251,6 +7683,53 @@ hipError_t pe_launch_destructive(const pe::BatchArgs* a, const pe::DestructiveAr
     if (a->ask.n_dev > 0 && (!a->tg.dev_cls || !a->tg.dev_free)) return hipErrorInvalidValue;   // a device ask reads both
     const size_t lds = pe_place_lds_bytes(false, a->hash_bits, a->packed_overlay != 0, 0);
     hipLaunchKernelGGL(pe::k_destructive, dim3(1), dim3(64), lds, st, *a, *d);
+    return hipGetLastError();
+}
+
+uint32_t pe_destructive_full_cap() { return pe::kDfCap; }
+
+// One workgroup; dynamic LDS = 16 B per entry.
+hipError_t pe_launch_destructive_full(const pe::SweepArgs* a, const pe::SweepArgs* a_dev, int np,
+                                      const pe::DestructiveFullArgs* f, const uint32_t* visit, uint32_t n,
+                                      uint32_t count, pe_ranked_node* out, uint32_t* state, hipStream_t st) {
+    const pe::DestructiveArgs& d = f->d;
+    if (!a_dev || !visit || n == 0 || !out || !state || !a->soa.rec || !a->soa.coll_job || !a->tg.coll_tg ||
+        !a->node_aux || !a->aff_vals || !d.stops || !f->named || (d.n_slots && (!d.palloc || !d.preempted)) ||
+        a->ask.cores > 0 || np < 0 || np > pe::kAuxPsets || np != a->tg.n_psets || (np && !f->sp) ||
+        a->tg.pset_cnt_total > (uint32_t)(pe::kAuxPsets * pe::kAuxValues) ||
+        a->tg.pset_tab_total > (uint32_t)(pe::kAuxPsets * (pe::kAuxValues + 1)))
+        return hipErrorInvalidValue;
+    for (int p = 0; p < np; p++)
+        if (a->tg.pset_nvals[p] > (int)pe::kAuxMissing ||
+            a->tg.pset_cnt_off[p] + (uint32_t)a->tg.pset_nvals[p] > a->tg.pset_cnt_total ||
+            a->tg.pset_tab_off[p] + (uint32_t)a->tg.pset_nvals[p] + 1u > a->tg.pset_tab_total)
+            return hipErrorInvalidValue;
+    if (a->ask.n_dev > 0 && (!a->tg.dev_cls || !a->tg.dev_free)) return hipErrorInvalidValue;   // a device ask reads both
+    const size_t lds = (size_t)pe::kDfCap * (sizeof(double) + 2 * sizeof(uint32_t));
+    static bool attr = false;
+    if (!attr) {
+        for (const void* fn : {reinterpret_cast<const void*>(&pe::k_destructive_full<0>),
+                               reinterpret_cast<const void*>(&pe::k_destructive_full<1>),
+                               reinterpret_cast<const void*>(&pe::k_destructive_full<2>)}) {
+            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        attr = true;
+    }
+    switch (np) {
+        case 0:
+            hipLaunchKernelGGL(pe::k_destructive_full<0>, dim3(1), dim3(pe::kFullThreads), lds, st, a_dev, *f, visit, n,
+                               count, out, state);
+            break;
+        case 1:
+            hipLaunchKernelGGL(pe::k_destructive_full<1>, dim3(1), dim3(pe::kFullThreads), lds, st, a_dev, *f, visit, n,
+                               count, out, state);
+            break;
+        default:
+            hipLaunchKernelGGL(pe::k_destructive_full<2>, dim3(1), dim3(pe::kFullThreads), lds, st, a_dev, *f, visit, n,
+                               count, out, state);
+            break;
+    }
     return hipGetLastError();
 }
 

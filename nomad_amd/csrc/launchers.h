@@ -76,6 +76,14 @@ hipError_t pe_launch_csi_loop(const pe::BatchArgs* a, const pe::CsiLoopArgs* c, 
                               uint8_t* log = nullptr, uint32_t log_cap = 0);
 // pe_place_destructive's loop (k_destructive): the stop list holds a->count updates.
 hipError_t pe_launch_destructive(const pe::BatchArgs* a, const pe::DestructiveArgs* d, hipStream_t st);
+// pe_place_destructive_full's loop (k_destructive_full): a_dev is a device copy of
+// `a` (a group's folded SweepArgs with np spread sets), the stop list holds
+// `count` updates of kDfWords words, `out` and `state` (8 words, zeroed) may be
+// mapped page-locked memory. pe_destructive_full_cap: the LDS entries it holds.
+uint32_t pe_destructive_full_cap();
+hipError_t pe_launch_destructive_full(const pe::SweepArgs* a, const pe::SweepArgs* a_dev, int np,
+                                      const pe::DestructiveFullArgs* f, const uint32_t* visit, uint32_t n,
+                                      uint32_t count, pe_ranked_node* out, uint32_t* state, hipStream_t st);
 // pe_place_csi_full's loop (k_csi_full): ev_score / ev_kind hold n_visit entries each.
 // log (or null): the trace log of pe_place_csi_full_metrics (k_csi_full<*, true>), as pe_launch_csi_loop's
 uint32_t pe_csi_full_threads();

@@ -170,6 +170,56 @@ class DeviceStack:
         self._mirror_eligibility(self.eng.Eligibility(changed_only=True))
         return r
 
+    def PlaceDestructive(self, tg, alloc_rows, ids=None):
+        """computePlacements' loop over a run of plain destructive updates of
+        one group (generic_sched.go:543-645; INTEGRATION.md, "Destructive
+        updates over one call"): per update Plan.AppendStoppedAlloc(prev),
+        Select, Plan.AppendAlloc; a nil Select pops its stop and ends the run.
+        With AllocMetric off the engine answers through
+        pe_place_destructive_full, the one entry for windowed and full-pass
+        groups alike; with it on through pe_place_destructive_metrics. The plan
+        and the shim's mirror then take the stops and placements the call made,
+        so the next _sync replays nothing. A run the engine refuses goes
+        update by update through Select. `ids`: the new allocs' IDs. Returns
+        the placements' records."""
+        self._sync()
+        name = tg if isinstance(tg, str) else self._tg_names[tg]
+        ti = self._tg_names.index(name)
+        rows = [int(a) for a in alloc_rows]
+        ids = list(ids) if ids is not None else ["update-%d" % a for a in rows]
+        node_row = self.eng.state.alloc_table.node_row
+        try:
+            if getattr(self.eng, "_metrics_on", False):
+                records, _ = self.eng.PlaceDestructiveMetrics(ti, rows, fallback=False)
+            else:
+                records = self.eng.PlaceDestructiveFull(ti, rows, fallback=False)
+        except Unsupported:
+            out = []
+            for a, new_id in zip(rows, ids):
+                node = int(node_row[a])
+                self.plan.AppendStoppedAlloc(a, node)
+                r = self.Select(tg)
+                if r is None:
+                    self.plan.PopUpdate(a, node)
+                    break
+                self.plan.AppendAlloc(PlanAlloc(new_id, r.row, name))
+                out.append(r)
+            return out
+        placed = [r for r in records if r.row >= 0]
+        for a, new_id, r in zip(rows, ids, placed):
+            node = int(node_row[a])
+            self.plan.AppendStoppedAlloc(a, node)
+            self.plan.AppendAlloc(PlanAlloc(new_id, r.row, name))
+            self._upd[node] = list(self.plan.node_update[node])
+            self._alloc_seen[r.row] = len(self.plan.node_allocation[r.row])
+            if self.fallback is not None:
+                self.fallback.StopAllocs([a])
+                self.fallback.Commit(ti, r.row, [])
+        if name not in self._seen_tgs:
+            self._seen_tgs.append(name)
+        self._mirror_eligibility(self.eng.Eligibility(changed_only=True))
+        return placed
+
     def _fallback_select(self, tg, name, options):
         """The reference chain answers; both sides then hold the same iterator
         state, plan and memo (pe_get_cursor / pe_set_cursor / pe_put_eligibility)."""

@@ -1332,6 +1332,30 @@ class GenericStack(_Stack):
             return place_destructive_by_select(self, tg, allocs)
         return [RankedNode.from_c(out[i], self.nodes) for i in range(min(n, placed.value + 1))]
 
+    def PlaceDestructiveFull(self, tg, allocs: Sequence[int], fallback: bool = True) -> List[RankedNode]:
+        """pe_place_destructive_full: PlaceDestructive for a task group that
+        runs full passes (node affinities, spreads, or a limit a sibling
+        group's Select latched to MaxInt32); on any other group the call is
+        PlaceDestructive's. Records in PlaceDestructive's shape. A job the
+        batched path refuses (Unsupported) is answered by
+        place_destructive_by_select when `fallback`, else the refusal
+        propagates."""
+        allocs = [int(a) for a in allocs]
+        n = len(allocs)
+        try:
+            if not hasattr(self._lib, "pe_place_destructive_full"):
+                raise Unsupported(abi.PE_EUNSUPPORTED, "no batched full-pass destructive update behind this ABI")
+            a = np.ascontiguousarray(np.asarray(allocs or [0], dtype=np.uint32))
+            out = (abi.pe_ranked_node * max(1, n))()
+            placed = C.c_uint32(0)
+            self._check(self._lib.pe_place_destructive_full(self._h, self._tg_index(tg), a.ctypes.data_as(abi.u32p), n,
+                                                            out, C.byref(placed)))
+        except Unsupported:
+            if not fallback:
+                raise
+            return place_destructive_by_select(self, tg, allocs)
+        return [RankedNode.from_c(out[i], self.nodes) for i in range(min(n, placed.value + 1))]
+
     def PlaceDestructiveMetrics(self, tg, allocs: Sequence[int], fallback: bool = True):
         """pe_place_destructive_metrics: PlaceDestructive with AllocMetric kept.
         Returns (records, maps): PlaceDestructive's records and, with
@@ -1371,7 +1395,8 @@ class GenericStack(_Stack):
         return [decode_metrics(self, c, co[k], co[k + 1], sc, so[k], so[k + 1]) for k in range(n.value)]
 
     def place_destructive_stats(self):
-        """(launches, synchronisations, uploads) of the last PlaceDestructive or PlaceDestructiveMetrics call."""
+        """(launches, synchronisations, uploads) of the last PlaceDestructive, PlaceDestructiveMetrics or
+        PlaceDestructiveFull call."""
         out = (C.c_uint64 * 3)()
         self._check(self._lib.pe_place_destructive_stats(self._h, out))
         return tuple(int(x) for x in out)

@@ -29,6 +29,14 @@ against the per-call sequence it replaces.
 
           PE_METRICS_PROF=1 python tools/destructive_probe.py --metrics [--out profiles/place_destructive_metrics/probe.json]
 
+  --full  The same comparison for a group that runs full passes (DESIGN.md
+      §48): the C3 cluster (10k nodes, seed 7) and job_c3 (a node affinity and
+      a datacenter target spread), where an older version of svc-c3 holds 600
+      allocs on distinct random nodes, all 600 updated. The call is
+      pe_place_destructive_full; the sequence is the same per-call sequence.
+
+          python tools/destructive_probe.py --full [--out profiles/place_destructive_full/probe.json]
+
   --headline PARENT_LIB  `bench.py --gpus 1 --steps N --warmup 20` in fresh
       processes, the parent commit's library (PE_ENGINE_LIB) and this tree's
       alternating, the order swapping every leg.
@@ -67,6 +75,20 @@ def shape(n, own, seed=42):
     return nodes, allocs, job, upd
 
 
+def shape_full(n, own, seed=7):
+    """cluster_c3 and job_c3 where an older version of svc-c3 holds `own` allocs on distinct nodes."""
+    nodes, allocs = synth.cluster_c3(n, seed=seed)
+    rng = np.random.Generator(np.random.PCG64(seed + 1))
+    for k in rng.choice(n, size=own, replace=False):
+        allocs.append(Allocation(node_id=nodes[int(k)].id, job_id="svc-c3", task_group="web",
+                                 cpu_shares=250, memory_mb=128, disk_mb=150, priority=50))
+    job = synth.job_c3(own)
+    job.version = 7
+    own_idx = [i for i, a in enumerate(allocs) if a.job_id == "svc-c3"]
+    upd = [own_idx[int(k)] for k in rng.permutation(len(own_idx))]
+    return nodes, allocs, job, upd
+
+
 def hip_runtime():
     """The HIP runtime the engine library is linked against (the process holds one copy)."""
     for name in ("libamdhip64.so", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so")):
@@ -87,7 +109,7 @@ def rec_key(r):
 def call_vs_sequence(args):
     from nomad_amd.stack import GenericStack
     n, own = (2000, 200) if args.small else (10000, 600)
-    nodes, allocs, job, upd = shape(n, own)
+    nodes, allocs, job, upd = shape_full(n, own) if args.full else shape(n, own)
     perm = synth.shuffle(n, 7)
 
     def handle():
@@ -122,6 +144,8 @@ def call_vs_sequence(args):
         assert settle(st) == 0
 
     place = lib.pe_place_destructive_metrics if args.metrics else lib.pe_place_destructive
+    if args.full:
+        place = lib.pe_place_destructive_full
     mc, ms = C.POINTER(abi.pe_metric_count)(), C.POINTER(abi.pe_metric_score)()
     mco, mso, mn = abi.u32p(), abi.u32p(), C.c_uint32(0)
     lib.pe_last_metrics_bin.restype = C.c_int
@@ -216,7 +240,12 @@ def call_vs_sequence(args):
         extra = {"metrics": True, "call_records_counts_scores": list(map_sizes["call"]),
                  "sequence_counts_scores": list(map_sizes["sequence"]),
                  "call_host_split_PE_METRICS_PROF": split}
-    return {"tool": "tools/destructive_probe.py" + (" --metrics" if args.metrics else ""), "nodes": n,
+    if args.full:
+        opts = [r.nodes_evaluated - r.nodes_filtered - r.nodes_exhausted for r in recs[:min(length, placed.value + 1)]]
+        extra["full"] = True
+        extra["options_per_select"] = {"min": int(min(opts)), "max": int(max(opts))}
+    return {"tool": "tools/destructive_probe.py" + (" --metrics" if args.metrics else "") +
+            (" --full" if args.full else ""), "nodes": n,
             "updates": length, "placed": int(placed.value), **extra,
             "records_equal": bool(same),
             "call_us": {"min": float(call.min()), "median": float(np.median(call)), "max": float(call.max())},
@@ -269,9 +298,12 @@ def main():
     ap.add_argument("--steps", type=int, default=40000)
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--metrics", action="store_true")
+    ap.add_argument("--full", action="store_true")
     ap.add_argument("--headline", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.full and args.metrics:
+        ap.error("--full has no metrics form")
     res = headline(args) if args.headline else call_vs_sequence(args)
     text = json.dumps(res, indent=1)
     print(text)
