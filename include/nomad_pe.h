@@ -121,8 +121,9 @@ typedef struct pe_node_table {
     const uint32_t* rsv_host_ports;
     /* NodeResources.Networks[*] addresses (str ids, per net_off entry): the IP
        field (PE_NONE = "") and the one address AssignNetwork yields from the
-       CIDR (yieldIP, network.go:294-315; PE_NONE when the CIDR does not parse
-       or holds more than one address). NULL: unknown (task-level static ports
+       CIDR (yieldIP, network.go:294-315; PE_NONE when the CIDR does not parse;
+       an IPv4 block of several addresses may be given as its text "a.b.c.d/len",
+       which the engine treats as not one address). NULL: unknown (task-level static ports
        are then not on the device path) */
     const uint32_t* net_ip; const uint32_t* net_cidr_ip;
 } pe_node_table;
@@ -1396,6 +1397,22 @@ int pe_probe_go_sort(const double* keys, const uint32_t* off, uint32_t n_arrays,
  * feasible.go:785-820), exposed for known-answer tests; needs no device.
  * l_state / r_state: 0 nil (unknown ${...} target), 1 found, 2 missing ("", false). */
 int pe_check_constraint(const char* op, const char* l, int l_state, const char* r, int r_state);
+/* The typed-attribute comparator of device constraints and affinities
+ * (checkAttributeConstraint, feasible.go:1334-1447, over Attribute.Compare,
+ * plugins/shared/structs/attribute.go:314-426), exposed for known-answer tests;
+ * needs no device. The left side is a typed attribute as a device fingerprint
+ * carries it: l_kind picks the value (PE_ATTR_INT: l_int, PE_ATTR_FLOAT:
+ * l_float, PE_ATTR_STRING: l_str, PE_ATTR_BOOL: l_int != 0), l_unit is its unit
+ * ("" or NULL: none), l_found whether the target resolved. The right side is
+ * the constraint's literal text, parsed as RTarget is (ParseAttribute); r_found
+ * == 0 or r_text == NULL stands for a target that did not resolve. */
+#define PE_ATTR_NONE 0
+#define PE_ATTR_INT 1
+#define PE_ATTR_FLOAT 2
+#define PE_ATTR_STRING 3
+#define PE_ATTR_BOOL 4
+int pe_check_attr(const char* op, int l_kind, int64_t l_int, double l_float, const char* l_str,
+                  const char* l_unit, int l_found, const char* r_text, int r_found);
 
 /* ======================================================================== *
  * Plan applier fit check (leader side).

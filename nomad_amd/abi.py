@@ -313,6 +313,37 @@ def bind_probes(lib):
     return lib
 
 
+PE_ATTR_NONE, PE_ATTR_INT, PE_ATTR_FLOAT, PE_ATTR_STRING, PE_ATTR_BOOL = range(5)
+
+
+def bind_check_attr(lib, name="pe_check_attr"):
+    """pe_check_attr / oracle_check_attr: the typed-attribute comparator; needs no device."""
+    fn = getattr(lib, name)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, C.c_int, C.c_int64, C.c_double, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                   C.c_int]
+    return lib
+
+
+def call_check_attr(fn, op, left, r_text):
+    """left: None (the target did not resolve) or (value, unit) with a bool, int,
+    float or str value; r_text: the constraint's literal, None when not found."""
+    kind, li, lf, ls, unit, found = PE_ATTR_NONE, 0, 0.0, None, b"", 0
+    if left is not None:
+        v, u = left
+        unit, found = u.encode(), 1
+        if isinstance(v, bool):
+            kind, li = PE_ATTR_BOOL, int(v)
+        elif isinstance(v, int):
+            kind, li = PE_ATTR_INT, v
+        elif isinstance(v, float):
+            kind, lf = PE_ATTR_FLOAT, v
+        else:
+            kind, ls = PE_ATTR_STRING, v.encode()
+    rt = None if r_text is None else r_text.encode()
+    return bool(fn(op.encode(), kind, li, lf, ls, unit, found, rt, 0 if rt is None else 1))
+
+
 # Entry points declared in include/nomad_pe.h: (name, restype, argtypes)
 def _sigs(prefix, handle):
     H = C.c_void_p
@@ -342,7 +373,7 @@ ENGINE_SYMBOLS = [
     "pe_abi_version", "pe_stack_create", "pe_stack_destroy", "pe_last_error", "pe_set_state",
     "pe_reset_plan", "pe_set_job", "pe_set_nodes", "pe_select", "pe_commit", "pe_commit_preempt", "pe_place", "pe_system_place",
     "pe_last_kernel_ms", "pe_stage_orders", "pe_place_batch", "pe_batch_results", "pe_last_phase_ms",
-    "pe_check_constraint", "pe_last_sweep_bytes", "pe_select_shard", "pe_select_merge",
+    "pe_check_constraint", "pe_check_attr", "pe_last_sweep_bytes", "pe_select_shard", "pe_select_merge",
     "pe_set_metrics", "pe_last_metrics", "pe_update_allocs", "pe_speculation_stats",
     "pe_plan_stop", "pe_plan_pop_update", "pe_update_nodes", "pe_comm_unique_id", "pe_comm_init", "pe_comm_init_host",
     "pe_place_sharded", "pe_last_exchange_us", "pe_get_eligibility", "pe_put_eligibility", "pe_get_cursor",

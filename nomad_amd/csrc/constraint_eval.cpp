@@ -367,6 +367,100 @@ bool go_parse_float(const std::string& s, double* out) {   // strconv.ParseFloat
     *out = std::strtod(s.c_str(), nullptr);
     return true;
 }
+
+// math/big.Float at the 256 bits of precision getBigFloat sets (attribute.go:20,
+// floatPrecision), rounding to nearest even, with the three operations
+// getBigFloat needs: SetInt64 / SetFloat64 (exact), Quo(1, multiplier) and Mul.
+// value = sign * m * 2^exp with bit 255 of m set; sign 0 is zero.
+struct Big256 {
+    int sign = 0;
+    bool inf = false;
+    int64_t exp = 0;
+    uint64_t m[4] = {0, 0, 0, 0};   // little-endian limbs
+};
+
+// x[0..n) * 2^exp plus, when `sticky`, a fraction below x's last bit, rounded to 256 bits
+Big256 big_round(const uint64_t* x, int n, bool sticky, int64_t exp, int sign) {
+    Big256 r;
+    int top = -1;
+    for (int k = n - 1; k >= 0 && top < 0; k--)
+        if (x[k]) top = 64 * k + 63 - __builtin_clzll(x[k]);
+    if (top < 0) return r;
+    r.sign = sign;
+    auto bit = [&](int64_t k) -> bool { return k >= 0 && k < 64 * (int64_t)n && ((x[k >> 6] >> (k & 63)) & 1u); };
+    const int64_t s = (int64_t)top - 255;   // bits dropped (negative: shift left, exact)
+    for (int k = 0; k < 256; k++)
+        if (bit(s + k)) r.m[k >> 6] |= 1ull << (k & 63);
+    r.exp = exp + s;
+    if (s > 0) {
+        const bool guard = bit(s - 1);
+        bool rest = sticky;
+        for (int64_t k = 0; k < s - 1 && !rest; k++) rest = bit(k);
+        if (guard && (rest || (r.m[0] & 1u))) {
+            int k = 0;
+            while (k < 4 && ++r.m[k] == 0) k++;
+            if (k == 4) { r.m[3] = 1ull << 63; r.exp++; }   // carried out of the top bit
+        }
+    }
+    return r;
+}
+
+Big256 big_from_int(int64_t v) {
+    const uint64_t mag = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    return big_round(&mag, 1, false, 0, v < 0 ? -1 : 1);
+}
+
+Big256 big_from_double(double d) {   // finite or infinite, never NaN
+    Big256 r;
+    if (std::isinf(d)) { r.sign = d < 0 ? -1 : 1; r.inf = true; return r; }
+    int e;
+    const double f = std::frexp(std::fabs(d), &e);   // f in [0.5, 1)
+    const uint64_t mant = (uint64_t)std::ldexp(f, 53);
+    return big_round(&mant, 1, false, (int64_t)e - 53, std::signbit(d) ? -1 : 1);
+}
+
+Big256 big_mul(const Big256& a, const Big256& b) {   // b is finite and non-zero here
+    if (a.sign == 0 || a.inf) {
+        Big256 r = a;
+        r.sign = a.sign * b.sign;
+        return r;
+    }
+    uint64_t p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; i++) {
+        unsigned __int128 carry = 0;
+        for (int j = 0; j < 4; j++) {
+            const unsigned __int128 t = (unsigned __int128)a.m[i] * b.m[j] + p[i + j] + carry;
+            p[i + j] = (uint64_t)t;
+            carry = t >> 64;
+        }
+        p[i + 4] = (uint64_t)carry;
+    }
+    return big_round(p, 8, false, a.exp + b.exp, a.sign * b.sign);
+}
+
+Big256 big_recip(int64_t mult) {   // Quo(1, mult), mult > 0: 2^320 / mult has at least 257 bits
+    uint64_t q[6];
+    unsigned __int128 rem = 0;
+    for (int k = 5; k >= 0; k--) {
+        const unsigned __int128 cur = (rem << 64) | (k == 5 ? 1ull : 0ull);
+        q[k] = (uint64_t)(cur / (uint64_t)mult);
+        rem = cur % (uint64_t)mult;
+    }
+    // 2^320 is limb 5 = 1: q holds floor(2^320 / mult)
+    return big_round(q, 6, rem != 0, -320, 1);
+}
+
+int big_cmp(const Big256& a, const Big256& b) {   // big.Float.Cmp
+    if (a.sign != b.sign) return a.sign < b.sign ? -1 : 1;
+    if (a.sign == 0) return 0;
+    int mag = 0;   // |a| against |b|
+    if (a.inf || b.inf) mag = a.inf == b.inf ? 0 : (a.inf ? 1 : -1);
+    else if (a.exp != b.exp) mag = a.exp < b.exp ? -1 : 1;
+    else
+        for (int k = 3; k >= 0 && mag == 0; k--)
+            if (a.m[k] != b.m[k]) mag = a.m[k] < b.m[k] ? -1 : 1;
+    return a.sign * mag;
+}
 }  // namespace
 
 DevAttr parse_dev_attr(const std::string& in) {
@@ -426,15 +520,21 @@ int compare_dev_attr(const DevAttr& a, const DevAttr& b, bool* ok) {
         return x == y ? 0 : (x < y ? -1 : 1);
     }
     if (b.kind != DevAttr::kInt && b.kind != DevAttr::kFloat) return 0;
-    // getBigFloat: value x multiplier (1/multiplier for inverse units)
-    auto big = [](const DevAttr& x, const UnitInfo* u) -> long double {
-        const long double v = x.kind == DevAttr::kInt ? (long double)x.i : (long double)x.f;
+    // big.NewFloat / SetFloat64 panic on NaN; the comparison of one is unpinned and
+    // kept as "equal"
+    if ((a.kind == DevAttr::kFloat && std::isnan(a.f)) || (b.kind == DevAttr::kFloat && std::isnan(b.f))) {
+        *ok = true;
+        return 0;
+    }
+    // getBigFloat (attribute.go:395-426): value x multiplier, 1/multiplier for the
+    // inverse unit, each step rounded to 256 bits
+    auto big = [](const DevAttr& x, const UnitInfo* u) -> Big256 {
+        const Big256 v = x.kind == DevAttr::kInt ? big_from_int(x.i) : big_from_double(x.f);
         if (!u) return v;
-        return u->inverse ? v * (1.0L / (long double)u->mult) : v * (long double)u->mult;
+        return big_mul(v, u->inverse ? big_recip(u->mult) : big_from_int(u->mult));
     };
-    const long double x = big(a, ua), y = big(b, ub);
     *ok = true;
-    return x < y ? -1 : (x > y ? 1 : 0);
+    return big_cmp(big(a, ua), big(b, ub));
 }
 
 bool ConstraintEvaluator::check_attr(const std::string& op, const DevAttr& l, bool lf, const DevAttr& r, bool rf) {

@@ -1378,6 +1378,12 @@ bool meets(const pe_stack* s, pe::ConstraintEvaluator& ev, const ParsedConstrain
     return ok;
 }
 
+// pe_node_table.net_cidr_ip as the one address yieldIP gives: a block of several
+// addresses ("a.b.c.d/len") is not one, and counts as unknown here
+uint32_t one_address(const pe_stack* s, uint32_t id) {
+    return id != PE_NONE && s->S(id).find('/') != std::string::npos ? PE_NONE : id;
+}
+
 // ---- devices (host side) ------------------------------------------------------
 DevTarget parse_dev_target(const pe_stack* s, const std::string& t) {
     DevTarget d;
@@ -1869,7 +1875,7 @@ int apply_nodes(pe_stack* s, const pe_node_table* nt, const std::vector<uint32_t
                     h.first_mbits = nt->net_mbits[k];
                     h.first_dev = nt->net_device[k];
                     if (nt->net_ip) h.first_ipfield = nt->net_ip[k];
-                    if (nt->net_cidr_ip) { h.first_yield = nt->net_cidr_ip[k]; h.yield_known = h.first_yield != PE_NONE; }
+                    if (nt->net_cidr_ip) { h.first_yield = one_address(s, nt->net_cidr_ip[k]); h.yield_known = h.first_yield != PE_NONE; }
                 }
                 h.n_device_nets++;
             }
@@ -1881,7 +1887,7 @@ int apply_nodes(pe_stack* s, const pe_node_table* nt, const std::vector<uint32_t
             for (uint32_t k = nt->net_off[i]; k < nt->net_off[i + 1]; k++)
                 if (!s->S(nt->net_device[k]).empty())
                     s->node_dnets[r].push_back(HostNet{nt->net_device[k], nt->net_ip ? nt->net_ip[k] : PE_NONE,
-                                                       nt->net_cidr_ip ? nt->net_cidr_ip[k] : PE_NONE,
+                                                       nt->net_cidr_ip ? one_address(s, nt->net_cidr_ip[k]) : PE_NONE,
                                                        nt->net_mbits[k]});
         }
         h.n_devices = (uint16_t)s->dev_ix.n(r);
@@ -5322,6 +5328,23 @@ int pe_check_constraint(const char* op, const char* l, int ls, const char* r, in
     return ev.check(op ? op : "", lt, rt) ? 1 : 0;
 }
 
+int pe_check_attr(const char* op, int l_kind, int64_t l_int, double l_float, const char* l_str,
+                  const char* l_unit, int l_found, const char* r_text, int r_found) {
+    pe::ConstraintEvaluator ev;
+    pe::DevAttr l, r;
+    switch (l_kind) {
+        case PE_ATTR_INT: l.kind = pe::DevAttr::kInt; l.i = l_int; break;
+        case PE_ATTR_FLOAT: l.kind = pe::DevAttr::kFloat; l.f = l_float; break;
+        case PE_ATTR_STRING: l.kind = pe::DevAttr::kString; l.s = l_str ? l_str : ""; break;
+        case PE_ATTR_BOOL: l.kind = pe::DevAttr::kBool; l.b = l_int != 0; break;
+        default: break;
+    }
+    if (l_unit) l.unit = l_unit;
+    const bool rf = r_found && r_text;
+    if (rf) r = pe::parse_dev_attr(r_text);
+    return ev.check_attr(op ? op : "", l, l_found != 0, r, rf) ? 1 : 0;
+}
+
 // ---- EvalEligibility export (context.go:190-356) ---------------------------
 
 static void elig_reset(pe_stack* s) {
@@ -7503,21 +7526,26 @@ static int select_impl(pe_stack* s, uint32_t tgi, const pe_select_options* opts,
     s->metrics_valid = false;
     HIP_TRY(s, hipSetDevice(s->device));
     if (s->cfg.stack_kind != PE_STACK_GENERIC) {
-        // SystemStack.Select: single pass over the (single-node) list, no limit;
-        // BinPack evicts when the scheduler configuration enables preemption
-        // (multi-device verdicts are built for the state the Select sees)
+        // SystemStack.Select: the first option of a pass over the list (a single
+        // node in the system scheduler), no limit; like the reference's
+        // StaticIterator the pass starts where the last Select stopped
+        // (feasible.go:74-117: Reset clears `seen`, not `offset`). BinPack evicts
+        // when the scheduler configuration enables preemption (multi-device
+        // verdicts are built for the state the Select sees)
         if (s->cfg.preempt && tgi < s->tgs.size() && tg_md(s, *s->tgs[tgi])) s->tgs[tgi]->tables_valid = false;
-        int rc = prepare_tg(s, tgi, s->visit, 0);
+        const uint32_t start = s->offset;
+        int rc = prepare_tg(s, tgi, s->visit, start);
         if (rc) return rc;
-        uint32_t placed, no;
+        uint32_t placed, no = start;
         const uint32_t saved = s->limit;
         s->limit = 1;
-        if (s->cfg.preempt) rc = run_evict_select(s, *s->tgs[tgi], s->visit, 0, nullptr, out, &no, rec);
-        else rc = run_place(s, tgi, 1, 0, s->visit, 0, nullptr, out, &placed, &no);
+        if (s->cfg.preempt) rc = run_evict_select(s, *s->tgs[tgi], s->visit, start, nullptr, out, &no, rec);
+        else rc = run_place(s, tgi, 1, 0, s->visit, start, nullptr, out, &placed, &no);
         s->limit = saved;
-        if (rc == PE_OK) elig_log_span(s, tgi, 0, out->nodes_evaluated);
+        if (rc == PE_OK) s->offset = no;
+        if (rc == PE_OK) elig_log_span(s, tgi, start, out->nodes_evaluated);
         if (rc == PE_OK && s->metrics_on)
-            rc = compute_metrics(s, *s->tgs[tgi], s->visit, 0, out->nodes_evaluated, nullptr, s->cfg.preempt != 0);
+            rc = compute_metrics(s, *s->tgs[tgi], s->visit, start, out->nodes_evaluated, nullptr, s->cfg.preempt != 0);
         return rc;
     }
     if (opts && opts->preferred_count > 0) {

@@ -344,15 +344,16 @@ def encode_csi_requests(reqs: Sequence[CSIVolumeRequest], interner: Interner):
 
 
 def _cidr_single(cidr: str, intern) -> int:
-    """The only address of a CIDR block, interned (PE_NONE when the CIDR does
-    not parse or holds more than one address)."""
+    """The only address of a CIDR block, interned; an IPv4 block of several
+    addresses as its text "a.b.c.d/len" (the masked address yieldIP starts from,
+    network.go:294-315); PE_NONE when the CIDR does not parse."""
     import ipaddress
     try:
         net = ipaddress.ip_network(cidr, strict=False)
     except ValueError:
         return abi.PE_NONE
     if net.num_addresses != 1:
-        return abi.PE_NONE
+        return intern(str(net)) if net.version == 4 else abi.PE_NONE
     return intern(str(net.network_address))
 
 

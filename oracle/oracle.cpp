@@ -41,6 +41,7 @@
 #include <stdexcept>
 #include <new>
 #include <cfloat>
+#include <cstdio>
 #include <algorithm>
 #include <atomic>
 
@@ -55,7 +56,24 @@ struct Unsupported : std::runtime_error {
 static const int32_t kDynPortCapacity = 32000 - 20000 + 1;   // IndexesInRange is inclusive
 
 struct DriverInfo { bool detected, healthy, nil; };
-struct NetRes { std::string mode, device; int32_t mbits; std::string ip, cidr_ip; };   // cidr_ip: yieldIP's one address
+// cidr_ip: the one address yieldIP gives, or an IPv4 block of several as "a.b.c.d/len"
+struct NetRes { std::string mode, device; int32_t mbits; std::string ip, cidr_ip; };
+
+static bool parse_cidr4(const std::string& c, uint32_t* base, uint32_t* count) {
+    unsigned a, b, d, e, len;
+    char tail;
+    if (std::sscanf(c.c_str(), "%u.%u.%u.%u/%u%c", &a, &b, &d, &e, &len, &tail) != 5) return false;
+    if (a > 255 || b > 255 || d > 255 || e > 255 || len < 1 || len > 32) return false;
+    const uint32_t mask = len == 32 ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> len);
+    *base = ((a << 24) | (b << 16) | (d << 8) | e) & mask;
+    *count = len == 32 ? 1u : (0xFFFFFFFFu >> len) + 1u;
+    return true;
+}
+
+static std::string ip4_text(uint32_t v) {
+    return std::to_string(v >> 24) + "." + std::to_string((v >> 16) & 255) + "." + std::to_string((v >> 8) & 255) +
+           "." + std::to_string(v & 255);
+}
 
 struct ODev {
     std::string vendor, type, name;
@@ -1536,6 +1554,7 @@ struct BinPackIterator : RankIterator {
                     for (auto& rp : t.rports) rport_values.push_back(rp.first);
                     const std::string* yield_ip = nullptr;
                     const std::string* yield_dev = nullptr;
+                    std::string yield_buf;
                     auto assign_network = [&](const std::vector<const OAlloc*>& prop, std::string* err) {
                         *err = "no networks available";
                         for (auto& nw : n.nets) {   // yieldIP: the AvailNetworks in node order
@@ -1543,8 +1562,18 @@ struct BinPackIterator : RankIterator {
                             auto ub = used_bw.find(nw.device);
                             const int32_t used = ub == used_bw.end() ? 0 : ub->second;
                             if (used + t.net_mbits > avail_bw.at(nw.device)) { *err = "bandwidth exceeded"; continue; }
+                            // yieldIP (network.go:294-315): every address of the CIDR in turn, the
+                            // first one on which the static ports are free is offered
+                            uint32_t base = 0, count = 1;
+                            const bool block = nw.cidr_ip.find('/') != std::string::npos;
                             if (!t.rports.empty()) {
                                 if (nw.cidr_ip.empty()) throw Unsupported("task static ports on a network that is not one address");
+                                if (block && !parse_cidr4(nw.cidr_ip, &base, &count))
+                                    throw Unsupported("task static ports on a network that is not one address");
+                            }
+                            bool offered = false;
+                            for (uint32_t k = 0; k < count && !offered; k++) {
+                                const std::string ip = block ? ip4_text(base + k) : nw.cidr_ip;
                                 bool bad = false;
                                 for (auto& rp : t.rports) {
                                     if (rp.first < 0 || rp.first >= 65536) {
@@ -1552,16 +1581,19 @@ struct BinPackIterator : RankIterator {
                                         bad = true;
                                         break;
                                     }
-                                    if (port_used(prop, nw.cidr_ip, rp.first)) {
+                                    if (port_used(prop, ip, rp.first)) {
                                         *err = "reserved port collision " + rp.second + "=" + std::to_string(rp.first);
                                         bad = true;
                                         break;
                                     }
                                 }
                                 if (bad) continue;
+                                if (kDynPortCapacity - used_dyn < t.net_dyn) { *err = "dynamic port selection failed"; continue; }
+                                offered = true;
+                                yield_buf = ip;
                             }
-                            if (kDynPortCapacity - used_dyn < t.net_dyn) { *err = "dynamic port selection failed"; continue; }
-                            yield_ip = &nw.cidr_ip;
+                            if (!offered) continue;
+                            yield_ip = &yield_buf;
                             yield_dev = &nw.device;
                             return true;
                         }
@@ -2615,6 +2647,20 @@ int oracle_check_constraint(const char* op, const char* l, int ls, const char* r
     lv.is_nil = ls == 0; if (ls) lv.s = l ? l : "";
     rv.is_nil = rs == 0; if (rs) rv.s = r ? r : "";
     return orasem::check_constraint(c, op, lv, rv, ls == 1, rs == 1) ? 1 : 0;
+}
+
+int oracle_check_attr(const char* op, int l_kind, int64_t l_int, double l_float, const char* l_str,
+                      const char* l_unit, int l_found, const char* r_text, int r_found) {
+    orasem::Caches c;
+    orasem::Attr l, r;
+    if (l_kind == 1) { l.kind = orasem::Attr::Int; l.i = l_int; }
+    else if (l_kind == 2) { l.kind = orasem::Attr::Float; l.f = l_float; }
+    else if (l_kind == 3) { l.kind = orasem::Attr::Str; l.s = l_str ? l_str : ""; }
+    else if (l_kind == 4) { l.kind = orasem::Attr::Bool; l.b = l_int != 0; }
+    if (l_unit) l.unit = l_unit;
+    const bool rf = r_found && r_text;
+    if (rf) r = orasem::parse_attribute(r_text);
+    return orasem::check_attribute_constraint(c, op ? op : "", l, r, l_found != 0, rf) ? 1 : 0;
 }
 
 int oracle_limit_iter(const double* scores, int n, int limit, double threshold, int max_skip,

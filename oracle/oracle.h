@@ -65,6 +65,10 @@ void oracle_sort_heap_reset(void);
 void oracle_sort_killer(uint32_t n, double* keys_out);
 /* feasible.go:785: l_state/r_state: 0 = nil (unknown target), 1 = found, 2 = ("", false) */
 int oracle_check_constraint(const char* op, const char* l, int l_state, const char* r, int r_state);
+/* feasible.go:1334-1447 checkAttributeConstraint: pe_check_attr on the oracle
+ * (l_kind as PE_ATTR_*, the right side the literal text ParseAttribute reads). */
+int oracle_check_attr(const char* op, int l_kind, int64_t l_int, double l_float, const char* l_str,
+                      const char* l_unit, int l_found, const char* r_text, int r_found);
 /* select.go: LimitIterator(limit, threshold, maxSkip) + MaxScoreIterator over a
  * StaticRankIterator of `n` FinalScores. Writes the emitted order (indices) to
  * out_order (capacity n), returns the count; *winner = MaxScore pick (-1 none);

@@ -49,6 +49,7 @@ def load():
         lib.oracle_score_fit.argtypes = [C.c_int] + [C.c_int64] * 6
         lib.oracle_check_constraint.restype = C.c_int
         lib.oracle_check_constraint.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
+        abi.bind_check_attr(lib, "oracle_check_attr")
         lib.oracle_limit_iter.restype = C.c_int
         lib.oracle_limit_iter.argtypes = [abi.f64p, C.c_int, C.c_int, C.c_double, C.c_int,
                                           abi.i32p, abi.i32p, abi.i32p]
@@ -145,6 +146,11 @@ def check_constraint(op, l, r):
     lv, ls = enc(l)
     rv, rs = enc(r)
     return bool(load().oracle_check_constraint(op.encode(), lv, ls, rv, rs))
+
+
+def check_attr(op, left, r_text):
+    """checkAttributeConstraint: left as abi.call_check_attr takes it, r_text the literal."""
+    return abi.call_check_attr(load().oracle_check_attr, op, left, r_text)
 
 
 def limit_iter(scores, limit, threshold=0.0, max_skip=3):

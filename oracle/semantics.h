@@ -345,9 +345,10 @@ static inline bool check_constraint(Caches& c, const std::string& op, const Val&
 // plugins/shared/structs/attribute.go (ParseAttribute 55-103, Comparable 296-320,
 // Compare 322-385) and units.go (unit table); checkAttributeConstraint and
 // checkAttributeVersionMatch (scheduler/feasible.go:1334-1447, 896-930).
-// Numbers are compared through long double where Go uses a 256-bit big.Float:
-// exact whenever value bits + multiplier bits <= 64 (every unit multiplier here
-// is <= 2^60 or 10^18; beyond that the comparison is parity unpinned).
+// Mixed and float numbers are compared as Go compares them, through a 256-bit
+// big.Float rounded to nearest even (Big256 below): value x multiplier is exact
+// (at most 64 + 60 bits), and the inverse unit mW multiplies by Quo(1, 1000)
+// rounded to 256 bits, so 1000.0 mW equals 1.0 W as it does in the reference.
 struct Attr {
     enum Kind { None, Int, Float, Str, Bool } kind = None;
     int64_t i = 0;
@@ -449,6 +450,100 @@ static inline Attr parse_attribute(const std::string& in) {
     return a;
 }
 
+// math/big.Float at the 256 bits of precision getBigFloat sets (attribute.go:20,
+// floatPrecision), rounding to nearest even, with the three operations
+// getBigFloat needs: SetInt64 / SetFloat64 (exact), Quo(1, multiplier) and Mul.
+// value = sign * m * 2^exp with bit 255 of m set; sign 0 is zero.
+struct Big256 {
+    int sign = 0;
+    bool inf = false;
+    int64_t exp = 0;
+    uint64_t m[4] = {0, 0, 0, 0};   // little-endian limbs
+};
+
+// x[0..n) * 2^exp plus, when `sticky`, a fraction below x's last bit, rounded to 256 bits
+static inline Big256 big_round(const uint64_t* x, int n, bool sticky, int64_t exp, int sign) {
+    Big256 r;
+    int top = -1;
+    for (int k = n - 1; k >= 0 && top < 0; k--)
+        if (x[k]) top = 64 * k + 63 - __builtin_clzll(x[k]);
+    if (top < 0) return r;
+    r.sign = sign;
+    auto bit = [&](int64_t k) -> bool { return k >= 0 && k < 64 * (int64_t)n && ((x[k >> 6] >> (k & 63)) & 1u); };
+    const int64_t s = (int64_t)top - 255;   // bits dropped (negative: shift left, exact)
+    for (int k = 0; k < 256; k++)
+        if (bit(s + k)) r.m[k >> 6] |= 1ull << (k & 63);
+    r.exp = exp + s;
+    if (s > 0) {
+        const bool guard = bit(s - 1);
+        bool rest = sticky;
+        for (int64_t k = 0; k < s - 1 && !rest; k++) rest = bit(k);
+        if (guard && (rest || (r.m[0] & 1u))) {
+            int k = 0;
+            while (k < 4 && ++r.m[k] == 0) k++;
+            if (k == 4) { r.m[3] = 1ull << 63; r.exp++; }   // carried out of the top bit
+        }
+    }
+    return r;
+}
+
+static inline Big256 big_from_int(int64_t v) {
+    const uint64_t mag = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    return big_round(&mag, 1, false, 0, v < 0 ? -1 : 1);
+}
+
+static inline Big256 big_from_double(double d) {   // finite or infinite, never NaN
+    Big256 r;
+    if (std::isinf(d)) { r.sign = d < 0 ? -1 : 1; r.inf = true; return r; }
+    int e;
+    const double f = std::frexp(std::fabs(d), &e);   // f in [0.5, 1)
+    const uint64_t mant = (uint64_t)std::ldexp(f, 53);
+    return big_round(&mant, 1, false, (int64_t)e - 53, std::signbit(d) ? -1 : 1);
+}
+
+static inline Big256 big_mul(const Big256& a, const Big256& b) {   // b is finite and non-zero here
+    if (a.sign == 0 || a.inf) {
+        Big256 r = a;
+        r.sign = a.sign * b.sign;
+        return r;
+    }
+    uint64_t p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; i++) {
+        unsigned __int128 carry = 0;
+        for (int j = 0; j < 4; j++) {
+            const unsigned __int128 t = (unsigned __int128)a.m[i] * b.m[j] + p[i + j] + carry;
+            p[i + j] = (uint64_t)t;
+            carry = t >> 64;
+        }
+        p[i + 4] = (uint64_t)carry;
+    }
+    return big_round(p, 8, false, a.exp + b.exp, a.sign * b.sign);
+}
+
+static inline Big256 big_recip(int64_t mult) {   // Quo(1, mult), mult > 0: 2^320 / mult has at least 257 bits
+    uint64_t q[6];
+    unsigned __int128 rem = 0;
+    for (int k = 5; k >= 0; k--) {
+        const unsigned __int128 cur = (rem << 64) | (k == 5 ? 1ull : 0ull);
+        q[k] = (uint64_t)(cur / (uint64_t)mult);
+        rem = cur % (uint64_t)mult;
+    }
+    // 2^320 is limb 5 = 1: q holds floor(2^320 / mult)
+    return big_round(q, 6, rem != 0, -320, 1);
+}
+
+static inline int big_cmp(const Big256& a, const Big256& b) {   // big.Float.Cmp
+    if (a.sign != b.sign) return a.sign < b.sign ? -1 : 1;
+    if (a.sign == 0) return 0;
+    int mag = 0;   // |a| against |b|
+    if (a.inf || b.inf) mag = a.inf == b.inf ? 0 : (a.inf ? 1 : -1);
+    else if (a.exp != b.exp) mag = a.exp < b.exp ? -1 : 1;
+    else
+        for (int k = 3; k >= 0 && mag == 0; k--)
+            if (a.m[k] != b.m[k]) mag = a.m[k] < b.m[k] ? -1 : 1;
+    return a.sign * mag;
+}
+
 static inline bool attr_comparable(const Attr& a, const Attr& b) {
     const UnitDef* ua = find_unit(a.unit);
     const UnitDef* ub = find_unit(b.unit);
@@ -478,15 +573,19 @@ static inline int attr_compare(const Attr& a, const Attr& b, bool* ok) {
         return ai == bi ? 0 : (ai < bi ? -1 : 1);
     }
     if (b.kind != Attr::Int && b.kind != Attr::Float) return 0;
-    auto big = [](const Attr& x) -> long double {
-        long double v = x.kind == Attr::Int ? (long double)x.i : (long double)x.f;
+    // SetFloat64 panics on NaN in Go; the comparison of one is unpinned and kept as "equal"
+    if ((a.kind == Attr::Float && std::isnan(a.f)) || (b.kind == Attr::Float && std::isnan(b.f))) {
+        *ok = true;
+        return 0;
+    }
+    auto big = [](const Attr& x) -> Big256 {   // getBigFloat (attribute.go:395-426)
+        const Big256 v = x.kind == Attr::Int ? big_from_int(x.i) : big_from_double(x.f);
         const UnitDef* u = find_unit(x.unit);
         if (!u) return v;
-        return u->inverse ? v * (1.0L / (long double)u->mult) : v * (long double)u->mult;
+        return big_mul(v, u->inverse ? big_recip(u->mult) : big_from_int(u->mult));
     };
-    const long double af = big(a), bf = big(b);
     *ok = true;
-    return af < bf ? -1 : (af > bf ? 1 : 0);
+    return big_cmp(big(a), big(b));
 }
 
 // checkAttributeVersionMatch (feasible.go:896-930)
