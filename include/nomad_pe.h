@@ -1330,6 +1330,37 @@ int pe_place_destructive_maps(const pe_stack* s, const pe_metric_count** counts,
  * pe_place_destructive_stats covers this call too. */
 int pe_place_destructive_full(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n, pe_ranked_node* out,
                               uint32_t* placed);
+/* pe_place_destructive_full with AllocMetric kept: the one entry of a caller
+ * that keeps it (GenericScheduler always does, generic_sched.go:552-645) for
+ * every run of destructive updates. Arguments and records are
+ * pe_place_destructive_full's; the maps come back through
+ * pe_place_destructive_maps (the same store, layout and lifetime as after
+ * pe_place_destructive_metrics), one map set per returned record, the nil
+ * Select's included, and that Select saw its own stop; the counters through
+ * pe_place_destructive_stats.
+ * With pe_set_metrics off the call is pe_place_destructive_full (no further
+ * launch; the maps accessor answers PE_ESTATE). With it on and a group that
+ * runs no full passes under an unlatched limit the call is
+ * pe_place_destructive_metrics. With it on and a full-pass group, records,
+ * maps and every later observable state equal those of the per-call sequence
+ * with metrics on: pe_plan_stop(&allocs[i], 1), pe_select(tg, NULL), the maps
+ * read, then pe_commit, or pe_plan_pop_update(allocs[i]) and a break. Later
+ * state includes the metrics shadow of the memo. The records also equal
+ * pe_place_destructive_full's on a handle with metrics off. pe_last_metrics*
+ * answers PE_ESTATE after the call.
+ * The dynamic node columns are copied on the device before the loop, the loop
+ * kernel logs the spread use counts every Select saw, the host walks the list
+ * until a walk changes no memo entry (later records reuse that walk), and one
+ * batched trace builds the maps: the number of launches, uploads and
+ * synchronisations does not depend on `n`.
+ * PE_EINVAL, PE_ESTATE and n == 0 as pe_place_destructive_full. PE_EUNSUPPORTED,
+ * checked before anything changes (the memo's metrics shadow included), with
+ * this entry's name in the message: pe_place_destructive_full's list without
+ * its pe_set_metrics row, and n * (node list length) above 2^24 (the caller
+ * splits the run). PE_EINTERNAL: a bounds guard of the loop kernel tripped;
+ * no maps are built and pe_place_destructive_maps answers PE_ESTATE. */
+int pe_place_destructive_full_metrics(pe_stack* s, uint32_t tg_index, const uint32_t* allocs, uint32_t n,
+                                      pe_ranked_node* out, uint32_t* placed);
 /* The reason text CSIVolumeChecker.Feasible records (feasible.go:19-26) for
  * `reason` (PE_CSI_*): stateless, needs no device. `volume` is the request's
  * source after the per_alloc suffix (reasons 1, 5, 6, 7), `plugin` the volume's

@@ -244,6 +244,10 @@ def bind_csi(lib):
     if hasattr(lib, "pe_place_destructive_full"):   # (an A/B library from before its full-pass form)
         lib.pe_place_destructive_full.restype = C.c_int
         lib.pe_place_destructive_full.argtypes = [H, C.c_uint32, u32p, C.c_uint32, C.POINTER(pe_ranked_node), u32p]
+    if hasattr(lib, "pe_place_destructive_full_metrics"):   # (an A/B library from before its metrics form)
+        lib.pe_place_destructive_full_metrics.restype = C.c_int
+        lib.pe_place_destructive_full_metrics.argtypes = [H, C.c_uint32, u32p, C.c_uint32, C.POINTER(pe_ranked_node),
+                                                          u32p]
     if not hasattr(lib, "pe_place_csi"):   # present or absent behind one ABI version (an A/B library)
         return lib
     lib.pe_place_csi.restype = C.c_int
@@ -394,6 +398,7 @@ ENGINE_SYMBOLS = [
     "pe_place_destructive", "pe_place_destructive_stats",
     "pe_place_destructive_metrics", "pe_place_destructive_maps",
     "pe_place_destructive_full",
+    "pe_place_destructive_full_metrics",
 ]
 
 

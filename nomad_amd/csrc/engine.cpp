@@ -927,6 +927,7 @@ struct pe_stack {
     DevMem d_cm_ends;        // compute_metrics: the one record's end and source (k_trace_top)
     DevMem d_trace_top;
     DevMem d_trace_delta, d_trace_tabs;   // spec_metrics: per record spread use counts and boost tables
+    DevMem d_cnt_log;                     // pe_place_destructive_full_metrics: the loop's use counts per update
     DevMem d_wc_list;                     // compute_metrics: a settled whole-list walk's passing rows
     DevMem d_loop_out, d_loop_state;   // device-resident full-pass count loop
     DevMem d_ploop_mask, d_ev_score_p, d_ev_status_p, d_ev_dep;
@@ -6734,12 +6735,18 @@ static void trace_ckpt_state(pe_stack* s, pe::NodeSoA* soa, pe::TgTables* t) {
 // `stops` (pe_place_destructive_metrics): the records are a destructive loop's,
 // record k's Select also saw these stops of records <= k (k_trace<true>); they
 // travel in the rows' upload. `stats` (or null): launches (copies included),
-// synchronisations and uploads are added to it.
+// synchronisations and uploads are added to it. `abs_counts` (or null; device
+// memory, n_rec x pset_cnt_total): every record's spread use counts themselves,
+// as the loop kept them (pe_place_destructive_full_metrics), in place of the
+// checkpoint's counts plus the earlier records' placements. `top_path` (or
+// null): 0 everything came back in one copy, 1 k_trace_top's lists served, 2 a
+// list overflowed and every code came back as well.
 static int trace_records(pe_stack* s, TgPlan& g, pe::NodeSoA soa, pe::TgTables t, const TraceRecs& R, MetricAcc* acc,
                          std::vector<pe_metric_count>& mcounts, std::vector<uint32_t>& mcounts_off,
                          std::vector<pe_metric_score>& mscores, std::vector<uint32_t>& mscores_off,
                          double* t_traced = nullptr, bool allow_list = true,
-                         const std::vector<TraceStopEv>* stops = nullptr, uint64_t* stats = nullptr) {
+                         const std::vector<TraceStopEv>* stops = nullptr, uint64_t* stats = nullptr,
+                         uint32_t* abs_counts = nullptr, int* top_path = nullptr) {
     const uint32_t n_rec = R.n_rec, n_entries = R.n_entries;
     const std::vector<uint32_t>&xrows = R.xrows, &rec_end = R.rec_end, &rsrc = R.rsrc, &list = R.list;
     auto row_of = [&](uint32_t k, uint32_t j) -> uint32_t {   // trace_row on the host
@@ -6837,7 +6844,13 @@ static int trace_records(pe_stack* s, TgPlan& g, pe::NodeSoA soa, pe::TgTables t
         HIP_TRY(s, s->d_trace_top.ensure(codes_at + n_rows * sizeof(uint32_t)));
         uint32_t* d_codes = reinterpret_cast<uint32_t*>(s->d_trace_top.as<uint8_t>() + codes_at);
         const double* stab = nullptr;
-        if (t.n_spread > 0) {   // every record's boosts from its own use counts (k_spread_tables)
+        if (t.n_spread > 0 && abs_counts) {   // every record's boosts from the counts its Select saw
+            HIP_TRY(s, s->d_trace_tabs.ensure(sizeof(double) * (size_t)n_rec * t.pset_tab_total));
+            HIP_TRY_STATE(s, pe_launch_spread_tables(&t, n_rec, abs_counts, s->d_trace_tabs.as<double>(), s->stream,
+                                                     true));
+            if (stats) stats[0]++;
+            stab = s->d_trace_tabs.as<double>();
+        } else if (t.n_spread > 0) {   // every record's boosts from its own use counts (k_spread_tables)
             for (int p = 0; p < t.n_psets; p++) t.pset_counts[p] = s->ck_pset[p].as<uint32_t>();
             const size_t nc = t.pset_cnt_total;
             std::vector<uint32_t> delta((size_t)n_rec * nc, 0u), cur(nc, 0u);
@@ -6884,6 +6897,11 @@ static int trace_records(pe_stack* s, TgPlan& g, pe::NodeSoA soa, pe::TgTables t
                                           n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
                 HIP_TRY(s, hipStreamSynchronize(s->stream));
             }
+            if (stats) {   // k_trace, k_trace_top, the copy back; a list that overflowed: the codes' copy as well
+                stats[0] += all_codes ? 4 : 3;
+                stats[1] += all_codes ? 2 : 1;
+            }
+            if (top_path) *top_path = all_codes ? 2 : 1;
         } else {   // short runs: everything in one copy
             HIP_TRY(s, hipMemcpyAsync(s->h_trace_top.p, s->d_trace_top.p, codes_at + n_rows * sizeof(uint32_t),
                                       hipMemcpyDeviceToHost, s->stream));
@@ -11645,11 +11663,18 @@ int pe_place_destructive_stats(const pe_stack* s, uint64_t* out3) {
 // synchronisation, and the mirrors replayed from the records. Every Select is
 // a full pass: the cursor stays, the limit latches to MaxInt32 and every
 // returned record logs the whole list's eligibility span.
+// `metrics` (pe_place_destructive_full_metrics, AllocMetric on):
+// the dynamic columns are checkpointed before the launch, the kernel logs every
+// Select's spread use counts, and every record's maps follow the mirrors
+// (destructive_full_maps).
 constexpr uint32_t kDestructiveFullMaxN = 4096;   // updates of one call (one workgroup runs them one after the other)
 
+static int destructive_full_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec, const pe_ranked_node* recs,
+                                 const std::vector<TraceStopEv>& evs, uint32_t* cnt_log, uint64_t* stats);
+
 static int place_destructive_full_one(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n,
-                                      pe_ranked_node* out, uint32_t* placed) {
-    const std::string fn = "pe_place_destructive_full: ";
+                                      pe_ranked_node* out, uint32_t* placed, bool metrics = false) {
+    const std::string fn = metrics ? "pe_place_destructive_full_metrics: " : "pe_place_destructive_full: ";
     if (s->cfg.stack_kind != PE_STACK_GENERIC) return s->fail(PE_ESTATE, fn + "not a generic stack");
     if (!s->have_state) return s->fail(PE_ESTATE, "pe_set_state not called");
     if (!s->have_job) return s->fail(PE_ESTATE, "pe_set_job not called");
@@ -11667,7 +11692,7 @@ static int place_destructive_full_one(pe_stack* s, uint32_t tgi, const uint32_t*
     // refusals, all before anything changes
     TgPlan& g = *s->tgs[tgi];
     if (!g.unsupported.empty()) return s->fail(PE_EUNSUPPORTED, g.unsupported);
-    if (s->metrics_on) return s->fail(PE_EUNSUPPORTED, fn + "pe_set_metrics on");
+    if (s->metrics_on && !metrics) return s->fail(PE_EUNSUPPORTED, fn + "pe_set_metrics on");
     if (s->cfg.preempt)
         return s->fail(PE_EUNSUPPORTED, fn + "a preempting stack (the loop retries a nil Select with Preempt)");
     if (!s->kids.empty()) return s->fail(PE_EUNSUPPORTED, fn + "a handle over several devices");
@@ -11680,6 +11705,10 @@ static int place_destructive_full_one(pe_stack* s, uint32_t tgi, const uint32_t*
     if (has_static(g)) return s->fail(PE_EUNSUPPORTED, fn + "static port asks in the group (a stop frees ports the gates were built with)");
     if (tg_md(s, g)) return s->fail(PE_EUNSUPPORTED, fn + "a task network on a snapshot with multi-device nodes");
     if (g.has_csi && !g.csi_reqs.empty()) return s->fail(PE_EUNSUPPORTED, fn + "a group with CSI requests");
+    // every record's trace covers the whole list: one entry per position at most, compared in 64 bits
+    if (metrics && (uint64_t)n * (uint64_t)s->visit.size() > pe::kCsiLogCap)
+        return s->fail(PE_EUNSUPPORTED, fn + "n times the node list's length exceeds the trace of one call (2^24 "
+                                             "positions; split the run)");
     for (size_t k = 0; k < s->tgs.size(); k++)
         if (k != tgi && s->tgs[k]->name == g.name)
             return s->fail(PE_EUNSUPPORTED, fn + "two task groups of one name (a stop moves the sibling's collision counts too)");
@@ -11777,8 +11806,24 @@ static int place_destructive_full_one(pe_stack* s, uint32_t tgi, const uint32_t*
     if (!d_out || !d_state) return s->fail(PE_EHIP, "mapped result buffers unavailable");
     std::memset(s->h_place_out.as<pe_ranked_node>(), 0, sizeof(pe_ranked_node) * (size_t)n);
     std::memset(s->h_place_status.as<uint32_t>(), 0, 8 * sizeof(uint32_t));
+    uint32_t* cnt_log = nullptr;
+    const size_t cnt_words = (size_t)n * cols;
+    if (metrics) {
+        // the state the call's first Select sees before its own stop, for the trace (as place_destructive_one);
+        // the spread counts come from the loop itself (cnt_log), not from the checkpoint's
+        rc = spec_copy(s, g, true);
+        if (rc) return rc;
+        for (const DevMem* col : {&s->d_rec, &s->d_coll_job, &g.coll_tg, &s->d_dev_free})
+            if (col->p && !s->nodes.empty()) stats[0]++;
+        for (size_t p = 0; p < g.psets.size() && p < (size_t)pe::kMaxPsets; p++)
+            if (g.psets[p]->counts.p) stats[0]++;
+        if (cnt_words) {
+            HIP_TRY(s, s->d_cnt_log.ensure(cnt_words * sizeof(uint32_t)));
+            cnt_log = s->d_cnt_log.as<uint32_t>();
+        }
+    }
     HIP_TRY_STATE(s, pe_launch_destructive_full(&A, s->d_full_args.as<pe::SweepArgs>(), np, &F, s->d_visit.as<uint32_t>(),
-                                                m, n, d_out, d_state, s->stream));
+                                                m, n, d_out, d_state, s->stream, cnt_log, cnt_words));
     stats[0]++;
     HIP_TRY(s, hipStreamSynchronize(s->stream));
     stats[1]++;
@@ -11815,8 +11860,99 @@ static int place_destructive_full_one(pe_stack* s, uint32_t tgi, const uint32_t*
         return s->fail(PE_EINTERNAL, "k_destructive_full: a bounds guard tripped (a stop's slot, row or position out of range)");
     for (uint32_t i = 0; i < got; i++) elig_log_span(s, tgi, start, m);   // every Select pulled the whole list
     if (placed) *placed = p;
+    if (metrics) {   // one map set per returned record; the nil Select saw its own stop too
+        std::vector<TraceStopEv> evs;
+        for (uint32_t i = 0; i < got; i++)
+            if (const uint32_t f = in[pe::kDfWords * i + 2] & (pe::kDsLive | pe::kDsJob | pe::kDsTg))
+                evs.push_back({in[pe::kDfWords * i + 1], i, in[pe::kDfWords * i], f});
+        rc = destructive_full_maps(s, g, start, got, out, evs, cnt_log, s->destructive_stats);
+        if (rc) return rc;
+    }
     // a listed alloc of another group of the job: that group's column follows from the mirrors
     if (other_group) return build_job_counts(s);
+    return PE_OK;
+}
+
+// The maps of pe_place_destructive_full_metrics' records, after the loop's
+// synchronisation (destructive_maps for full passes). Every record's window is
+// the whole list from one cursor, so the host walks it (metrics_walk against
+// the reference memo, advanced for good) until a walk changes no memo entry;
+// that walk's filter counts and passing rows serve every later record, the rows
+// as one list rotated to the cursor on the device (TraceSrc, kTraceRot). One
+// batched trace (trace_records, k_trace<true>) then runs against the checkpoint
+// taken before the loop, with the stops record k's Select saw as events and
+// record k's spread boosts from the use counts the loop itself logged (cnt_log).
+static int destructive_full_maps(pe_stack* s, TgPlan& g, uint32_t start, uint32_t n_rec, const pe_ranked_node* recs,
+                                 const std::vector<TraceStopEv>& evs, uint32_t* cnt_log, uint64_t* stats) {
+    const bool prof = s->tun.metrics_prof;
+    const double t0 = prof ? now_us() : 0.0;
+    pe_stack::CsiMaps& M = s->ds_m;
+    M.gen = 0;
+    static thread_local std::vector<MetricAcc> acc;
+    if (acc.size() < n_rec) acc.resize(n_rec);
+    for (uint32_t k = 0; k < n_rec; k++) acc[k].reset();
+    const auto& order = s->visit;
+    const uint32_t m = (uint32_t)order.size();
+    TraceRecs R;
+    R.rec_end.resize(n_rec);
+    R.rsrc.resize(n_rec);
+    std::vector<int32_t> rec_row(n_rec);
+    std::vector<MemoDelta> mlog;
+    std::vector<uint8_t> pass;
+    MetricCounts cf, kf;
+    bool cached = false;
+    uint32_t n_entries = 0, walked_recs = 0, rot = 0;
+    for (uint32_t k = 0; k < n_rec; k++) {
+        if (recs[k].nodes_evaluated != m)
+            return s->fail(PE_EINTERNAL, "pe_place_destructive_full_metrics: a record that is no full pass");
+        if (cached) {
+            acc[k].cf = cf;
+            acc[k].kf = kf;
+            R.rsrc[k] = pe::kTraceRot | rot;
+            n_entries += (uint32_t)R.list.size();
+        } else {
+            const size_t x0 = R.xrows.size(), l0 = mlog.size();
+            pass.assign(m, 0);
+            metrics_walk(s, g, order, start, m, acc[k], R.xrows, &mlog, &pass);
+            walked_recs++;
+            if (R.xrows.size() >= (size_t)pe::kTraceRot)
+                return s->fail(PE_EINTERNAL, "pe_place_destructive_full_metrics: trace rows overflow");
+            if (mlog.size() == l0) {   // the memo has settled: no verdict depends on the visit order any more
+                cf = acc[k].cf;
+                kf = acc[k].kf;
+                for (uint32_t q = 0; q < m; q++)
+                    if (pass[q]) {
+                        if (q < start) rot++;   // the list's first row at or after the cursor
+                        R.list.push_back(order[q]);
+                    }
+                if (rot == R.list.size()) rot = 0;
+                cached = true;
+            }
+            R.rsrc[k] = (uint32_t)x0;
+            n_entries += (uint32_t)(R.xrows.size() - x0);
+        }
+        R.rec_end[k] = n_entries;
+        rec_row[k] = recs[k].row;
+    }
+    R.n_rec = n_rec;
+    R.rec_row = rec_row.data();
+    R.n_entries = n_entries;
+    const double t1 = prof ? now_us() : 0.0;
+    double t2 = t1;
+    pe::NodeSoA soa = soa_of(s);   // the state the call's first Select saw before its stop: the checkpoint
+    pe::TgTables t = tables_of(g);
+    trace_ckpt_state(s, &soa, &t);
+    int top_path = 0;
+    const int rc = trace_records(s, g, soa, t, R, acc.data(), M.counts, M.counts_off, M.scores, M.scores_off,
+                                 prof ? &t2 : nullptr, true, &evs, stats, cnt_log, &top_path);
+    if (rc) return rc;
+    M.n_rec = n_rec;
+    M.gen = s->gen;
+    if (prof)
+        std::fprintf(stderr, "place_destructive_full_metrics: %u records, %u walked on the host, %u traced entries, %zu "
+                             "stop events, k_trace_top path %d: walk %.1f us, trace %.1f us, maps %.1f us (%zu counts, "
+                             "%zu scores)\n", n_rec, walked_recs, n_entries, evs.size(), top_path, t1 - t0, t2 - t1,
+                     now_us() - t2, M.counts.size(), M.scores.size());
     return PE_OK;
 }
 
@@ -11830,6 +11966,21 @@ int pe_place_destructive_full(pe_stack* s, uint32_t tgi, const uint32_t* allocs,
     PE_FLUSH_RESET(s);
     s->pre_overflow.clear();
     return place_destructive_full_one(s, tgi, allocs, n, out, placed);
+}
+
+// pe_place_destructive_full with AllocMetric kept: the one entry of a caller that keeps
+// it. Off: the call is pe_place_destructive_full. On, a windowed group under an unlatched
+// limit: the call is pe_place_destructive_metrics.
+int pe_place_destructive_full_metrics(pe_stack* s, uint32_t tgi, const uint32_t* allocs, uint32_t n,
+                                      pe_ranked_node* out, uint32_t* placed) {
+    if (!s || (n && (!allocs || !out))) return PE_EINVAL;
+    if (!s->metrics_on) return pe_place_destructive_full(s, tgi, allocs, n, out, placed);
+    if (s->have_job && tgi < s->tgs.size() && !tg_full_scan(s, *s->tgs[tgi]) && s->limit < 0x7FFFFFFFu)
+        return pe_place_destructive_metrics(s, tgi, allocs, n, out, placed);
+    if (placed) *placed = 0;
+    PE_FLUSH_RESET(s);
+    s->pre_overflow.clear();
+    return place_destructive_full_one(s, tgi, allocs, n, out, placed, true);
 }
 
 // The maps of pe_place_csi_metrics' records, after the loop's synchronisation:

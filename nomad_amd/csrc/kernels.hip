@@ -3785,15 +3785,22 @@ __global__ void __launch_bounds__(512) k_sweep_merge(const SweepRec* recs, uint3
 // checkpoint) plus the earlier records' placements (`delta`: n_rec x
 // pset_cnt_total, host-built, completed here in place); one block per record,
 // its table at tab + k * pset_tab_total. Spread sets only.
+// kAbsolute (pe_place_destructive_full_metrics): `delta` holds record k's use
+// counts themselves (k_destructive_full<*, true>'s cnt_log), and t.pset_counts
+// is not read.
+template <bool kAbsolute>
 __global__ void __launch_bounds__(256) k_spread_tables(TgTables t, uint32_t* delta, double* tab) {
     __shared__ uint32_t scratch[4];
     const uint32_t k = blockIdx.x;
     uint32_t* cnt = delta + (size_t)k * t.pset_cnt_total;
-    for (int p = 0; p < t.n_psets; p++)
-        for (int v = threadIdx.x; v < t.pset_nvals[p]; v += 256) cnt[t.pset_cnt_off[p] + v] += t.pset_counts[p][v];
-    __syncthreads();
+    if constexpr (!kAbsolute) {
+        for (int p = 0; p < t.n_psets; p++)
+            for (int v = threadIdx.x; v < t.pset_nvals[p]; v += 256) cnt[t.pset_cnt_off[p] + v] += t.pset_counts[p][v];
+        __syncthreads();
+    }
     build_spread_table<256>(t, cnt, tab + (size_t)k * t.pset_tab_total, scratch);
 }
+template __global__ void k_spread_tables<false>(TgTables, uint32_t*, double*);   // the existing form first
 
 __global__ void __launch_bounds__(256) k_spread_table(TgTables t, double* tab) {
     __shared__ uint32_t counts[kLdsPsetValues];
@@ -5307,11 +5314,17 @@ __device__ __forceinline__ void df_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-template <int NP>   // spread properties scored, at most kAuxPsets
+// kMetrics (pe_place_destructive_full_metrics): update k's Select's use counts,
+// counts[] after its stop and before its winner's placement (a nil Select's
+// before its undo), go to cnt_log[k * pset_cnt_total + i] in device memory:
+// what k_spread_tables<true> builds record k's boosts from for the trace of its
+// maps, so the closed form above stays in this kernel alone. The launcher checks
+// that the log holds count * pset_cnt_total words.
+template <int NP, bool kMetrics>   // spread properties scored, at most kAuxPsets
 __global__ void __launch_bounds__(kFullThreads) k_destructive_full(const SweepArgs* __restrict__ Ap,
                                                                    DestructiveFullArgs F, const uint32_t* visit,
                                                                    uint32_t n, uint32_t count, pe_ranked_node* out,
-                                                                   uint32_t* state) {
+                                                                   uint32_t* state, uint32_t* cnt_log) {
     const SweepArgs& A = *Ap;
     extern __shared__ double ent_sum[];                                   // [kDfCap] score_head sums
     uint32_t* ent_meta = reinterpret_cast<uint32_t*>(ent_sum + kDfCap);    // status | k << 2 | spread values
@@ -5503,6 +5516,10 @@ __global__ void __launch_bounds__(kFullThreads) k_destructive_full(const SweepAr
         }
 
         // ---- Select: k_fullpass_lds's passes ----
+        if constexpr (kMetrics && NP > 0) {   // this Select's use counts (they move behind the next barrier only)
+            const uint32_t nc = t.pset_cnt_total;
+            for (uint32_t i = (uint32_t)tid; i < nc; i += kFullThreads) cnt_log[(size_t)it * nc + i] = counts[i];
+        }
         double ap[kDfPer];
         double amax = -__builtin_inff();
 #pragma unroll
@@ -7688,10 +7705,12 @@ hipError_t pe_launch_destructive(const pe::BatchArgs* a, const pe::DestructiveAr
 
 uint32_t pe_destructive_full_cap() { return pe::kDfCap; }
 
-// One workgroup; dynamic LDS = 16 B per entry.
+// One workgroup; dynamic LDS = 16 B per entry. cnt_log (or null): every update's use counts for the
+// trace of its maps (k_destructive_full<*, true>), cnt_log_words >= count * pset_cnt_total words of device memory.
 hipError_t pe_launch_destructive_full(const pe::SweepArgs* a, const pe::SweepArgs* a_dev, int np,
                                       const pe::DestructiveFullArgs* f, const uint32_t* visit, uint32_t n,
-                                      uint32_t count, pe_ranked_node* out, uint32_t* state, hipStream_t st) {
+                                      uint32_t count, pe_ranked_node* out, uint32_t* state, hipStream_t st,
+                                      uint32_t* cnt_log, size_t cnt_log_words) {
     const pe::DestructiveArgs& d = f->d;
     if (!a_dev || !visit || n == 0 || !out || !state || !a->soa.rec || !a->soa.coll_job || !a->tg.coll_tg ||
         !a->node_aux || !a->aff_vals || !d.stops || !f->named || (d.n_slots && (!d.palloc || !d.preempted)) ||
@@ -7705,29 +7724,43 @@ hipError_t pe_launch_destructive_full(const pe::SweepArgs* a, const pe::SweepArg
             a->tg.pset_tab_off[p] + (uint32_t)a->tg.pset_nvals[p] + 1u > a->tg.pset_tab_total)
             return hipErrorInvalidValue;
     if (a->ask.n_dev > 0 && (!a->tg.dev_cls || !a->tg.dev_free)) return hipErrorInvalidValue;   // a device ask reads both
+    if (cnt_log && (uint64_t)count * a->tg.pset_cnt_total > (uint64_t)cnt_log_words) return hipErrorInvalidValue;
+    const bool log = cnt_log && np > 0;   // no spread set: nothing to store, the plain form
     const size_t lds = (size_t)pe::kDfCap * (sizeof(double) + 2 * sizeof(uint32_t));
+    // (the plain forms are named first here and below: they are instantiated first and keep their place in the code object)
     static bool attr = false;
     if (!attr) {
-        for (const void* fn : {reinterpret_cast<const void*>(&pe::k_destructive_full<0>),
-                               reinterpret_cast<const void*>(&pe::k_destructive_full<1>),
-                               reinterpret_cast<const void*>(&pe::k_destructive_full<2>)}) {
+        for (const void* fn : {reinterpret_cast<const void*>(&pe::k_destructive_full<0, false>),
+                               reinterpret_cast<const void*>(&pe::k_destructive_full<1, false>),
+                               reinterpret_cast<const void*>(&pe::k_destructive_full<2, false>),
+                               reinterpret_cast<const void*>(&pe::k_destructive_full<1, true>),
+                               reinterpret_cast<const void*>(&pe::k_destructive_full<2, true>)}) {
             const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
         }
         attr = true;
     }
+    uint32_t* const none = nullptr;
     switch (np) {
         case 0:
-            hipLaunchKernelGGL(pe::k_destructive_full<0>, dim3(1), dim3(pe::kFullThreads), lds, st, a_dev, *f, visit, n,
-                               count, out, state);
+            hipLaunchKernelGGL((pe::k_destructive_full<0, false>), dim3(1), dim3(pe::kFullThreads), lds, st, a_dev, *f,
+                               visit, n, count, out, state, none);
             break;
         case 1:
-            hipLaunchKernelGGL(pe::k_destructive_full<1>, dim3(1), dim3(pe::kFullThreads), lds, st, a_dev, *f, visit, n,
-                               count, out, state);
+            if (!log)
+                hipLaunchKernelGGL((pe::k_destructive_full<1, false>), dim3(1), dim3(pe::kFullThreads), lds, st, a_dev,
+                                   *f, visit, n, count, out, state, none);
+            else
+                hipLaunchKernelGGL((pe::k_destructive_full<1, true>), dim3(1), dim3(pe::kFullThreads), lds, st, a_dev,
+                                   *f, visit, n, count, out, state, cnt_log);
             break;
         default:
-            hipLaunchKernelGGL(pe::k_destructive_full<2>, dim3(1), dim3(pe::kFullThreads), lds, st, a_dev, *f, visit, n,
-                               count, out, state);
+            if (!log)
+                hipLaunchKernelGGL((pe::k_destructive_full<2, false>), dim3(1), dim3(pe::kFullThreads), lds, st, a_dev,
+                                   *f, visit, n, count, out, state, none);
+            else
+                hipLaunchKernelGGL((pe::k_destructive_full<2, true>), dim3(1), dim3(pe::kFullThreads), lds, st, a_dev,
+                                   *f, visit, n, count, out, state, cnt_log);
             break;
     }
     return hipGetLastError();
@@ -7840,10 +7873,14 @@ hipError_t pe_launch_trace_batch(const pe::NodeSoA* s, const pe::TgTables* t, co
 }
 
 // Spread boost tables of every record of a speculative run (k_spread_tables).
+// absolute: `delta` holds every record's counts themselves (k_spread_tables<true>).
 hipError_t pe_launch_spread_tables(const pe::TgTables* t, uint32_t n_rec, uint32_t* delta, double* tab,
-                                   hipStream_t st) {
+                                   hipStream_t st, bool absolute) {
     if (n_rec == 0) return hipSuccess;
-    hipLaunchKernelGGL(pe::k_spread_tables, dim3(n_rec), dim3(256), 0, st, *t, delta, tab);
+    if (!absolute)
+        hipLaunchKernelGGL(pe::k_spread_tables<false>, dim3(n_rec), dim3(256), 0, st, *t, delta, tab);
+    else
+        hipLaunchKernelGGL(pe::k_spread_tables<true>, dim3(n_rec), dim3(256), 0, st, *t, delta, tab);
     return hipGetLastError();
 }
 

@@ -80,10 +80,13 @@ hipError_t pe_launch_destructive(const pe::BatchArgs* a, const pe::DestructiveAr
 // `a` (a group's folded SweepArgs with np spread sets), the stop list holds
 // `count` updates of kDfWords words, `out` and `state` (8 words, zeroed) may be
 // mapped page-locked memory. pe_destructive_full_cap: the LDS entries it holds.
+// cnt_log (or null): pe_place_destructive_full_metrics' use counts per update
+// (k_destructive_full<*, true>), count * pset_cnt_total words of device memory.
 uint32_t pe_destructive_full_cap();
 hipError_t pe_launch_destructive_full(const pe::SweepArgs* a, const pe::SweepArgs* a_dev, int np,
                                       const pe::DestructiveFullArgs* f, const uint32_t* visit, uint32_t n,
-                                      uint32_t count, pe_ranked_node* out, uint32_t* state, hipStream_t st);
+                                      uint32_t count, pe_ranked_node* out, uint32_t* state, hipStream_t st,
+                                      uint32_t* cnt_log = nullptr, size_t cnt_log_words = 0);
 // pe_place_csi_full's loop (k_csi_full): ev_score / ev_kind hold n_visit entries each.
 // log (or null): the trace log of pe_place_csi_full_metrics (k_csi_full<*, true>), as pe_launch_csi_loop's
 uint32_t pe_csi_full_threads();
@@ -127,4 +130,4 @@ hipError_t pe_launch_trace_batch(const pe::NodeSoA* s, const pe::TgTables* t, co
                                  const double* spread_tab, double* scores, hipStream_t st,
                                  const pe::TraceStops* stops = nullptr);   // stops: k_trace<true>, a destructive loop's records
 hipError_t pe_launch_spread_tables(const pe::TgTables* t, uint32_t n_rec, uint32_t* delta, double* tab,
-                                   hipStream_t st);
+                                   hipStream_t st, bool absolute = false);   // absolute: delta holds the counts themselves

@@ -177,7 +177,8 @@ class DeviceStack:
         Select, Plan.AppendAlloc; a nil Select pops its stop and ends the run.
         With AllocMetric off the engine answers through
         pe_place_destructive_full, the one entry for windowed and full-pass
-        groups alike; with it on through pe_place_destructive_metrics. The plan
+        groups alike; with it on through pe_place_destructive_full_metrics,
+        which is that entry with the maps kept. The plan
         and the shim's mirror then take the stops and placements the call made,
         so the next _sync replays nothing. A run the engine refuses goes
         update by update through Select. `ids`: the new allocs' IDs. Returns
@@ -190,7 +191,7 @@ class DeviceStack:
         node_row = self.eng.state.alloc_table.node_row
         try:
             if getattr(self.eng, "_metrics_on", False):
-                records, _ = self.eng.PlaceDestructiveMetrics(ti, rows, fallback=False)
+                records, _ = self.eng.PlaceDestructiveFullMetrics(ti, rows, fallback=False)
             else:
                 records = self.eng.PlaceDestructiveFull(ti, rows, fallback=False)
         except Unsupported:

@@ -1385,9 +1385,43 @@ class GenericStack(_Stack):
             return records, None
         return records, (self.PlaceDestructiveMaps() if n else [])
 
+    def PlaceDestructiveFullMetrics(self, tg, allocs: Sequence[int], fallback: bool = True):
+        """pe_place_destructive_full_metrics: the one entry for every run of
+        destructive updates of a caller that keeps AllocMetric. A full-pass
+        group (node affinities, spreads, a latched limit) runs
+        PlaceDestructiveFull's loop with its maps; any other group is
+        PlaceDestructiveMetrics'; with EnableMetrics off the call is
+        PlaceDestructiveFull's. Returns (records, maps) in
+        PlaceDestructiveMetrics' shape (maps None with metrics off). A job the
+        batched path refuses (Unsupported) is answered by
+        place_destructive_metrics_by_select when `fallback`, else the refusal
+        propagates."""
+        allocs = [int(a) for a in allocs]
+        n = len(allocs)
+        try:
+            if not hasattr(self._lib, "pe_place_destructive_full_metrics"):
+                raise Unsupported(abi.PE_EUNSUPPORTED,
+                                  "no batched full-pass destructive update with metrics behind this ABI")
+            a = np.ascontiguousarray(np.asarray(allocs or [0], dtype=np.uint32))
+            out = (abi.pe_ranked_node * max(1, n))()
+            placed = C.c_uint32(0)
+            self._check(self._lib.pe_place_destructive_full_metrics(self._h, self._tg_index(tg),
+                                                                    a.ctypes.data_as(abi.u32p), n, out,
+                                                                    C.byref(placed)))
+        except Unsupported:
+            if not fallback:
+                raise
+            if not getattr(self, "_metrics_on", False):
+                return place_destructive_by_select(self, tg, allocs), None
+            return place_destructive_metrics_by_select(self, tg, allocs)
+        records = [RankedNode.from_c(out[i], self.nodes) for i in range(min(n, placed.value + 1))]
+        if not getattr(self, "_metrics_on", False):
+            return records, None
+        return records, (self.PlaceDestructiveMaps() if n else [])
+
     def PlaceDestructiveMaps(self) -> List[Dict]:
         """pe_place_destructive_maps: the maps of the last
-        PlaceDestructiveMetrics' records, one dict per record in LastMetrics' shape."""
+        PlaceDestructiveMetrics' or PlaceDestructiveFullMetrics' records, one dict per record in LastMetrics' shape."""
         c, sc = C.POINTER(abi.pe_metric_count)(), C.POINTER(abi.pe_metric_score)()
         co, so, n = abi.u32p(), abi.u32p(), C.c_uint32(0)
         self._check(self._lib.pe_place_destructive_maps(self._h, C.byref(c), C.byref(co), C.byref(sc), C.byref(so),
@@ -1395,8 +1429,8 @@ class GenericStack(_Stack):
         return [decode_metrics(self, c, co[k], co[k + 1], sc, so[k], so[k + 1]) for k in range(n.value)]
 
     def place_destructive_stats(self):
-        """(launches, synchronisations, uploads) of the last PlaceDestructive, PlaceDestructiveMetrics or
-        PlaceDestructiveFull call."""
+        """(launches, synchronisations, uploads) of the last PlaceDestructive, PlaceDestructiveMetrics,
+        PlaceDestructiveFull or PlaceDestructiveFullMetrics call."""
         out = (C.c_uint64 * 3)()
         self._check(self._lib.pe_place_destructive_stats(self._h, out))
         return tuple(int(x) for x in out)

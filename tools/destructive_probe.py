@@ -37,6 +37,19 @@ against the per-call sequence it replaces.
 
           python tools/destructive_probe.py --full [--out profiles/place_destructive_full/probe.json]
 
+  --full-metrics  --full's shape and protocol with pe_set_metrics on in both
+      handles: the call is pe_place_destructive_full_metrics
+      followed by pe_place_destructive_maps, the sequence reads
+      pe_last_metrics_bin after each pe_select; both legs copy the maps' bytes
+      out, and records and maps are compared in every pair (the maps after the
+      clock has stopped). A third handle with metrics off runs
+      pe_place_destructive_full once per pair, from an idle device as well: what
+      keeping the maps costs. With PE_METRICS_PROF set the call's host split
+      is read back from the engine's stderr lines, with the records walked on
+      the host, the traced entries and k_trace_top's path.
+
+          PE_METRICS_PROF=1 python tools/destructive_probe.py --full-metrics [--out profiles/place_destructive_full_metrics/probe.json]
+
   --headline PARENT_LIB  `bench.py --gpus 1 --steps N --warmup 20` in fresh
       processes, the parent commit's library (PE_ENGINE_LIB) and this tree's
       alternating, the order swapping every leg.
@@ -120,6 +133,13 @@ def call_vs_sequence(args):
             st.EnableMetrics(True)
         return st
     a, b = handle(), handle()
+    fm = args.full_metrics
+    plain = None
+    if fm:   # the third handle: metrics off
+        plain = GenericStack()
+        plain.SetState(nodes, allocs)
+        plain.SetJob(job)
+        plain_recs = (abi.pe_ranked_node * len(upd))()
     lib = a._lib
     lib.pe_flush.restype = C.c_int
     lib.pe_flush.argtypes = [C.c_void_p]
@@ -138,14 +158,14 @@ def call_vs_sequence(args):
     def prepare(st):
         st.ResetPlan()
         st.SetJob(job)
-        if args.metrics:
+        if args.metrics and st is not plain:
             st.EnableMetrics(True)
         st.SetNodes(perm)
         assert settle(st) == 0
 
     place = lib.pe_place_destructive_metrics if args.metrics else lib.pe_place_destructive
     if args.full:
-        place = lib.pe_place_destructive_full
+        place = lib.pe_place_destructive_full_metrics if fm else lib.pe_place_destructive_full
     mc, ms = C.POINTER(abi.pe_metric_count)(), C.POINTER(abi.pe_metric_score)()
     mco, mso, mn = abi.u32p(), abi.u32p(), C.c_uint32(0)
     lib.pe_last_metrics_bin.restype = C.c_int
@@ -153,6 +173,8 @@ def call_vs_sequence(args):
                                         C.POINTER(C.POINTER(abi.pe_metric_score)), abi.u32p]
     nc, ns = C.c_uint32(0), C.c_uint32(0)
     map_sizes = {}
+    csz, ssz = C.sizeof(abi.pe_metric_count), C.sizeof(abi.pe_metric_score)
+    kept = {"call": None, "sequence": []}     # --full-metrics: the maps' bytes, copied out inside the timed sections
 
     def run_call():
         prepare(a)
@@ -161,6 +183,10 @@ def call_vs_sequence(args):
         if args.metrics:
             rc = rc or lib.pe_place_destructive_maps(a._h, C.byref(mc), C.byref(mco), C.byref(ms), C.byref(mso),
                                                      C.byref(mn))
+        if fm and rc == 0:
+            k = mn.value
+            kept["call"] = (k, [mco[i] for i in range(k + 1)], [mso[i] for i in range(k + 1)],
+                            C.string_at(mc, csz * mco[k]), C.string_at(ms, ssz * mso[k]))
         rc = rc or settle(a)
         t1 = time.perf_counter()
         assert rc == 0, rc
@@ -173,6 +199,7 @@ def call_vs_sequence(args):
         done = 0
         sizes = [0, 0]
         map_sizes["sequence"] = sizes
+        kept["sequence"] = []
         t0 = time.perf_counter()
         for k in range(length):
             rc = lib.pe_plan_stop(b._h, one[k], 1) or lib.pe_select(b._h, 0, None, C.byref(seq[k]))
@@ -180,6 +207,8 @@ def call_vs_sequence(args):
                 rc = rc or lib.pe_last_metrics_bin(b._h, C.byref(mc), C.byref(nc), C.byref(ms), C.byref(ns))
                 sizes[0] += nc.value
                 sizes[1] += ns.value
+                if fm and rc == 0:
+                    kept["sequence"].append((C.string_at(mc, csz * nc.value), C.string_at(ms, ssz * ns.value)))
             assert rc == 0, rc
             done = k + 1
             if seq[k].row < 0:
@@ -192,7 +221,44 @@ def call_vs_sequence(args):
         assert rc == 0, rc
         return (t1 - t0) * 1e6, done
 
+    def run_plain():
+        prepare(plain)
+        t0 = time.perf_counter()
+        rc = lib.pe_place_destructive_full(plain._h, 0, arr.ctypes.data_as(abi.u32p), length, plain_recs,
+                                           C.byref(placed_plain))
+        rc = rc or settle(plain)
+        t1 = time.perf_counter()
+        assert rc == 0, rc
+        return (t1 - t0) * 1e6
+
+    placed_plain = C.c_uint32(0)
+    cdt, sdt = np.dtype(abi.pe_metric_count), np.dtype(abi.pe_metric_score)
+
+    def maps_equal():
+        """Record by record: the counts as (kind, key text, count) sets, the score items field by field."""
+        k, co, so, cb, sb = kept["call"]
+        if k != len(kept["sequence"]):
+            return False
+        cc, cs = np.frombuffer(cb, dtype=cdt), np.frombuffer(sb, dtype=sdt)
+        for r in range(k):
+            qb, tb = kept["sequence"][r]
+            qc, qs = np.frombuffer(qb, dtype=cdt), np.frombuffer(tb, dtype=sdt)
+            mine, theirs = cc[co[r]:co[r + 1]], cs[so[r]:so[r + 1]]
+            if len(mine) != len(qc) or len(theirs) != len(qs):
+                return False
+            if sorted((int(e["kind"]), a.MetricString(int(e["key"])), int(e["count"])) for e in mine) != \
+                    sorted((int(e["kind"]), b.MetricString(int(e["key"])), int(e["count"])) for e in qc):
+                return False
+            for x, y in zip(theirs, qs):
+                n_sc = int(x["n_scores"])
+                if (int(x["row"]), n_sc, float(x["norm"])) != (int(y["row"]), int(y["n_scores"]), float(y["norm"])) or \
+                        list(x["scorer"][:n_sc]) != list(y["scorer"][:n_sc]) or \
+                        list(x["score"][:n_sc]) != list(y["score"][:n_sc]):
+                    return False
+        return True
+
     pairs, same, counters = [], True, set()
+    maps_same = True if fm else None
     # PE_METRICS_PROF: the engine writes the call's host split to stderr; keep the process's stderr in a file
     prof = args.metrics and bool(os.environ.get("PE_METRICS_PROF"))
     saved_err = None
@@ -212,9 +278,16 @@ def call_vs_sequence(args):
                 t["sequence"], done = run_sequence()
         got = min(length, placed.value + 1)
         same = same and got == done and all(rec_key(recs[k]) == rec_key(seq[k]) for k in range(got))
+        if fm:
+            maps_same = maps_same and maps_equal()
+            t["plain"] = run_plain()
+            same = same and placed_plain.value == placed.value and \
+                all(rec_key(recs[k]) == rec_key(plain_recs[k]) for k in range(got))
         if r >= 3:
             pairs.append({"pair": r - 2, "order": order[0] + " first", "call_us": t["call"], "sequence_us": t["sequence"],
                           "difference_us": t["sequence"] - t["call"]})
+            if fm:
+                pairs[-1]["metrics_off_call_us"] = t["plain"]
     split = None
     if prof:
         C.CDLL(None).fflush(None)
@@ -222,7 +295,7 @@ def call_vs_sequence(args):
         os.close(saved_err)
         err_file.seek(0)
         lines = [ln for ln in err_file.read().decode(errors="replace").splitlines()
-                 if ln.startswith("place_destructive_metrics:")]
+                 if ln.startswith("place_destructive_full_metrics:" if fm else "place_destructive_metrics:")]
         rows = [[float(x) for x in re.search(r"walk ([\d.]+) us, trace ([\d.]+) us, maps ([\d.]+) us", ln).groups()]
                 for ln in lines][3:]                           # (the warm-ups' lines dropped)
         if rows:
@@ -240,12 +313,18 @@ def call_vs_sequence(args):
         extra = {"metrics": True, "call_records_counts_scores": list(map_sizes["call"]),
                  "sequence_counts_scores": list(map_sizes["sequence"]),
                  "call_host_split_PE_METRICS_PROF": split}
+    if fm:
+        off = np.asarray([p["metrics_off_call_us"] for p in pairs])
+        extra["maps_equal"] = bool(maps_same)
+        extra["metrics_off_call_us"] = {"min": float(off.min()), "median": float(np.median(off)), "max": float(off.max())}
+        extra["factor_between_medians"] = float(np.median(sequ) / np.median(call))
+        extra["call_below_sequence_in_every_pair_and_range"] = bool(call.max() < sequ.min())
     if args.full:
         opts = [r.nodes_evaluated - r.nodes_filtered - r.nodes_exhausted for r in recs[:min(length, placed.value + 1)]]
         extra["full"] = True
         extra["options_per_select"] = {"min": int(min(opts)), "max": int(max(opts))}
-    return {"tool": "tools/destructive_probe.py" + (" --metrics" if args.metrics else "") +
-            (" --full" if args.full else ""), "nodes": n,
+    return {"tool": "tools/destructive_probe.py" + (" --full-metrics" if fm else (" --metrics" if args.metrics else "") +
+                                                    (" --full" if args.full else "")), "nodes": n,
             "updates": length, "placed": int(placed.value), **extra,
             "records_equal": bool(same),
             "call_us": {"min": float(call.min()), "median": float(np.median(call)), "max": float(call.max())},
@@ -299,11 +378,14 @@ def main():
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--metrics", action="store_true")
     ap.add_argument("--full", action="store_true")
+    ap.add_argument("--full-metrics", action="store_true")
     ap.add_argument("--headline", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.full and args.metrics:
-        ap.error("--full has no metrics form")
+        ap.error("--full with metrics is --full-metrics")
+    if args.full_metrics:
+        args.full = args.metrics = True
     res = headline(args) if args.headline else call_vs_sequence(args)
     text = json.dumps(res, indent=1)
     print(text)
